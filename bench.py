@@ -17,11 +17,20 @@ BEV grids — runs INSIDE the timed region: after every forward each rank hands 
 ``streamingflow_amd.dist.gather_predictions`` on a side stream, overlapped with the next forward (``--no-gather`` to
 leave it out); its stand-alone time, byte count and the RCCL world size are reported (``multi_gpu``).
 
-Extra objects on the JSON line: ``roofline`` (dominant kernel of the forward, per-launch hipEvent timing in a dedicated
-pass of the same workload through libsfnative's profiler), ``roofline_ode_step`` (the kernel group of ONE GRU-ODE
-step — the unit SURVEY.md §8d defines: 728 C^2 h w FLOP, 16 C h w + eps + weights bytes — from >= 20 individually timed
-hipGraph replays: median and p95), ``batch1_forward`` (the same forward at the reference's own batch size) and
-``cpu_baseline`` (the oracle — a torch-CPU port of the reference path — on the host cores, rank 0, N=1 only).
+A plain run (``--gpus 1 --steps K --warmup W``) only sets up, warms up, times the K steps, writes the outputs of the last
+step when ``--dump-outputs DIR`` is given, and prints the headline line; the objects below that name a secondary figure
+stay null there.  ``--full`` adds every secondary measurement: ``roofline`` (dominant kernel of the forward, per-launch
+hipEvent timing in a dedicated pass of the same workload through libsfnative's profiler), ``roofline_ode_step`` (the
+kernel group of ONE GRU-ODE step — the unit SURVEY.md §8d defines: 728 C^2 h w FLOP, 16 C h w + eps + weights bytes —
+from >= 20 individually timed hipGraph replays: median and p95), ``batch1_forward`` (the same forward at the reference's
+own batch size), the component benches, the direct-form and bf16x3 forwards, BASELINE configs 4 and 5, the stand-alone
+all-gather figures at N > 1, and ``cpu_baseline`` (the oracle — a torch-CPU port of the reference path — on the host
+cores, rank 0, N=1 only).  ``--no-*`` and ``--headline-only`` trim a ``--full`` run.
+
+``--dump-outputs DIR``: after the timed steps, what the last one returned (the [B, T, C, H, W] fp32 predictions) as
+``DIR/predictions_sample.npy`` (a fixed, seeded sample of 8 Mi elements, float32) and ``DIR/predictions_mean_btc.npy``
+(the mean of every (sample, frame, channel) plane, float64); rank 0 only.  Inputs and weights are hashed and the
+in-kernel noise is keyed by torch's seed, which the bench fixes, so equal arguments give equal inputs from run to run.
 """
 import argparse
 import ctypes
@@ -46,15 +55,56 @@ def parse():
     ap.add_argument("--solver", default="euler")
     ap.add_argument("--batch", type=int, default=32, help="samples per forward on each GPU (the reference API "
                     "takes a batch and loops over it; here same-structure samples run through the kernels together)")
+    ap.add_argument("--full", action="store_true", help="also every secondary measurement (batch-1 latency, ODE rollout / step alone, roofline "
+                    "passes, component benches, direct form, bf16x3, other configs, CPU baselines, stand-alone all-gather); "
+                    "off: only the timed steps and the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the secondary sections (next-row components, ODE step alone)")
     ap.add_argument("--no-gather", action="store_true", help="N > 1: leave the all-gather of per-sample BEV grids out of the timed region")
-    ap.add_argument("--headline-only", action="store_true", help="only the timed workload and its roofline pass (profiling aid: the rocprofv3 "
+    ap.add_argument("--headline-only", action="store_true", help="with --full: only the timed workload and its roofline pass (profiling aid: the rocprofv3 "
                     "kernel statistics of such a run average over exactly the launches the roofline object describes)")
     ap.add_argument("--dry", action="store_true", help="no GPU: the launcher, the rendezvous, the sample sharding, the timed-region collectives "
                     "and the JSON relay on the gloo backend with a stub forward (tests/test_bench_launcher.py); the line says \"dry\": true")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.headline_only and not a.full:      # it names what a --full run keeps (the roofline pass among it): never drop that silently
+        ap.error("--headline-only trims a --full run: give --full as well")
+    if not a.full:      # a plain run: the timed workload alone
+        a.headline_only = a.no_roofline = a.no_extras = a.no_cpu_baseline = True
+    return a
+
+
+def host_threads():
+    """worker threads for host-side set-up: the cores this process may use, at most 16 (and at most OMP_NUM_THREADS where set)"""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
+    return max(1, min(n, 16))
+
+
+BENCH_SEED = 20240611      # torch's global seed for the run
+DUMP_SAMPLE = 8 << 20      # elements of the predictions written by --dump-outputs (32 MiB of float32)
+
+
+def dump_outputs(d, y):
+    """what the timed path returned in its last step: a fixed, seeded sample of the [B, T, C, H, W] predictions (float32) and
+    the mean of every (sample, frame, channel) plane (float64, every element counts)"""
+    import numpy as np
+    import torch
+    os.makedirs(d, exist_ok=True)
+    flat = y.reshape(-1)
+    n = flat.numel()
+    if n <= DUMP_SAMPLE:
+        sample = flat
+    else:
+        idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(BENCH_SEED)).sort().values
+        sample = flat[idx.to(flat.device)]
+    np.save(os.path.join(d, "predictions_sample.npy"), sample.float().cpu().numpy())
+    np.save(os.path.join(d, "predictions_mean_btc.npy"), y.mean(dim=(-2, -1), dtype=torch.float64).cpu().numpy())
 
 
 def launch_ranks(a, argv):
@@ -172,6 +222,7 @@ def main():
         return dry_run(a, world)
     import torch
     import torch.distributed as dist
+    torch.manual_seed(BENCH_SEED)      # the in-kernel noise is keyed by torch's seed (mixed with the rank): the same draws every run
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     # SF_BENCH_BACKEND=gloo + SF_BENCH_ONE_DEVICE=1: exercise the multi-rank path on a 1-GPU box
@@ -198,7 +249,9 @@ def main():
     net.load_state_dict(sd)
     net = net.to(dev)
     B = max(1, a.batch)
-    cams, lids = zip(*[cases.bev_inputs(C, H, W, cts.shape[1], lts.shape[1], seed=rank * 1000 + i) for i in range(B)])
+    from concurrent.futures import ThreadPoolExecutor      # the hash fill is numpy work that releases the GIL: one sample per thread
+    with ThreadPoolExecutor(max_workers=host_threads()) as ex:
+        cams, lids = zip(*ex.map(lambda i: cases.bev_inputs(C, H, W, cts.shape[1], lts.shape[1], seed=rank * 1000 + i), range(B)))
     cam, lid = cams[0], lids[0]
     cam_d, lid_d = torch.cat(cams, 0).to(dev), torch.cat(lids, 0).to(dev)     # B samples per rank
     cts_b, lts_b, tts_b = cts.repeat(B, 1), lts.repeat(B, 1), tts.repeat(B, 1)
@@ -247,8 +300,11 @@ def main():
     ms_per_step = 1e3 * el / a.steps
     value = n_ode * B * a.steps * world / el
 
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, y)
+
     multi = None
-    if world > 1:
+    if world > 1 and a.full:
         grid = y[0]
         gbytes = grid.numel() * 4
         gms = None
@@ -292,6 +348,9 @@ def main():
                  "devices": sorted({int(v) for v in _all_ranks(local, world, dev if backend == "nccl" else "cpu")}),
                  "what": "all_gather_into_tensor of one sample's [T, C, H, W] fp32 BEV grid per rank (streamingflow_amd.dist.gather_predictions), side stream, overlapped with the next forward"
                          + ("" if backend == "nccl" else " [gloo: staged through the host, the host blocks on it]") + "; metric counters: all_reduce(SUM)"}
+    elif world > 1:      # a plain run: what the timed region did (the stand-alone collectives above are --full figures)
+        multi = {"rccl_world": dist.get_world_size(), "backend": dist.get_backend(), "gather_in_timed_region": do_gather,
+                 "gather_bytes_per_rank": y[0].numel() * 4, "gather_bytes_total": y[0].numel() * 4 * world}
 
     # ---- single-sample latency of the same forward (batch 1) -----------------------------------------
     def forward1():

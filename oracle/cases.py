@@ -205,6 +205,15 @@ def voxel_points(tag):
     return p
 
 
+# the raw hard / dynamic voxelisation calls of the compiled reference kernel (tests/golden/voxelize_live.npz):
+# voxel_size, point_cloud_range, max_points, max_voxels of a 12^3 grid, and its 4000 random points
+VOXEL_LIVE = ([0.75, 0.75, 0.75], [-4.5, -4.5, -4.5, 4.5, 4.5, 4.5], 4, 300)
+
+
+def voxel_live_points():
+    return torch.rand((4000, 5), generator=torch.Generator().manual_seed(9)) * 12 - 6
+
+
 # ---- BEV Decoder --------------------------------------------------------------------------
 # tag -> in_channels, n_classes, n_present, n_hdmap, predict_gate, (b, s, h, w)
 DECODER_CASES = {

@@ -11,6 +11,7 @@ Only outputs (data) are stored; weights / inputs / eps are regenerated from thei
                   control flow (temporal_ode_bayes.py:508-620) with its numerics stubbed out
   big_stats.json  G7: statistics of the C=64, 200x200 forward (tensors are 72 MB)
   voxelize.npz    N2: mmdet3d Voxelization (hard voxelisation) outputs from the reference's C++ CPU kernel
+  voxelize_live.npz  N2: the raw hard / dynamic calls of that kernel on 4000 random points (with the points)
   unused_cells.npz a16: Dual_GRU / BiGRU (layers/temporal.py:59-249) and the dual cells with several present frames
   lift_splat.npz  N1: streamingflow.bev_pool / projection_to_birds_eye_view / get_geometry /
                   create_frustum / pose_vec2mat / mmdet3d bev_pool (+ QuickCumsum) outputs
@@ -383,6 +384,30 @@ def gen_voxel():
     np.savez_compressed(os.path.join(OUT, "voxelize.npz"), **out)
 
 
+def gen_voxel_live():
+    """the raw hard / dynamic voxelisation calls of the reference's compiled C++ CPU kernel on 4000 random points
+    (tests/test_voxel_oracle.py: the *_compiled_reference_live tests read them where the kernel is not built)"""
+    from . import build_ref
+    from . import voxelize as VZ
+    ext = build_ref.load_voxel_layer()
+    assert ext is not None, "oracle/_ref/voxel_layer is not built (python -m oracle.build_ref)"
+    vs, rng, mp, mv = cases.VOXEL_LIVE
+    pts = cases.voxel_live_points()
+    voxels = pts.new_zeros((mv, mp, 5))
+    coors = pts.new_zeros((mv, 3), dtype=torch.int)
+    num = pts.new_zeros((mv,), dtype=torch.int)
+    m = ext.hard_voxelize(pts, voxels, coors, num, vs, rng, mp, mv, 3, True)
+    dyn = pts.new_zeros((pts.shape[0], 3), dtype=torch.int)
+    ext.dynamic_voxelize(pts, dyn, vs, rng, 3)
+    out = {"points": _np(pts), "voxels": _np(voxels[:m]), "coors": coors[:m].numpy().astype(np.int32),
+           "num": num[:m].numpy().astype(np.int32), "dyn_coors": dyn.numpy().astype(np.int32)}
+    v, c, k = VZ.hard_voxelize(out["points"], vs, rng, mp, mv)
+    assert np.array_equal(out["voxels"], v) and np.array_equal(out["coors"], c) and np.array_equal(out["num"], k)
+    assert np.array_equal(out["dyn_coors"], VZ.dynamic_voxelize(out["points"], vs, rng))
+    print("voxel_live", m, "voxels")
+    np.savez_compressed(os.path.join(OUT, "voxelize_live.npz"), **out)
+
+
 def gen_decoder():
     """N3 (Decoder): the reference's Decoder class on the oracle's restatement of torchvision's resnet18 trunk."""
     from . import decoder_ref as DR
@@ -527,11 +552,14 @@ def main():
     a = ap.parse_args()
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
-    todo = a.only.split(",") if a.only else ["ops", "fpode", "schedules", "beverse", "lift", "voxel", "decoder", "temporal", "eval", "labels"]
+    todo = a.only.split(",") if a.only else ["ops", "fpode", "schedules", "beverse", "lift", "voxel", "voxel_live", "decoder", "temporal", "eval",
+                                             "labels"]
     if "lift" in todo:
         gen_lift()
     if "voxel" in todo:
         gen_voxel()
+    if "voxel_live" in todo:
+        gen_voxel_live()
     if "decoder" in todo:
         gen_decoder()
     if "temporal" in todo:
@@ -540,7 +568,7 @@ def main():
         gen_eval()
     if "labels" in todo:
         gen_labels()
-    if not set(todo) - {"lift", "voxel", "decoder", "temporal", "eval", "labels"} and not a.big:
+    if not set(todo) - {"lift", "voxel", "voxel_live", "decoder", "temporal", "eval", "labels"} and not a.big:
         return
     m = refimport.modules()
     if "ops" in todo:

@@ -21,12 +21,17 @@ def test_oracle_matches_reference_fixture(tag):
 
 
 def test_oracle_matches_compiled_reference_live():
+    """the reference kernel's outputs on 4000 random points as stored (tests/golden/voxelize_live.npz, `gen_golden --only
+    voxel_live`), and live as well where oracle/_ref holds the compiled kernel"""
     from oracle import build_ref
+    G = gold("voxelize_live.npz")
+    vs, rng, mp, mv = cases.VOXEL_LIVE        # 12^3 cells
+    v, c, k = VZ.hard_voxelize(G["points"], vs, rng, mp, mv)
+    assert np.array_equal(G["voxels"], v) and np.array_equal(G["coors"], c) and np.array_equal(G["num"], k)
     ext = build_ref.load_voxel_layer()
     if ext is None:
-        pytest.skip("oracle/_ref/voxel_layer not built (needs /root/reference)")
-    pts = torch.rand((4000, 5), generator=torch.Generator().manual_seed(9)) * 12 - 6
-    vs, rng, mp, mv = [0.75, 0.75, 0.75], [-4.5, -4.5, -4.5, 4.5, 4.5, 4.5], 4, 300        # 12^3 cells
+        return
+    pts = torch.from_numpy(G["points"])
     voxels = pts.new_zeros((mv, mp, 5))
     coors = pts.new_zeros((mv, 3), dtype=torch.int)
     num = pts.new_zeros((mv,), dtype=torch.int)
@@ -65,12 +70,15 @@ def test_dynamic_voxelize_oracle_matches_reference_fixture(tag):
 
 
 def test_dynamic_voxelize_oracle_matches_compiled_reference_live():
+    """as above for the dynamic call: stored per-point coordinates, and live where the compiled kernel is here"""
     from oracle import build_ref
+    G = gold("voxelize_live.npz")
+    vs, rng = cases.VOXEL_LIVE[:2]
+    assert np.array_equal(G["dyn_coors"], VZ.dynamic_voxelize(G["points"], vs, rng))
     ext = build_ref.load_voxel_layer()
     if ext is None:
-        pytest.skip("oracle/_ref/voxel_layer not built (needs /root/reference)")
-    pts = torch.rand((4000, 5), generator=torch.Generator().manual_seed(9)) * 12 - 6
-    vs, rng = [0.75, 0.75, 0.75], [-4.5, -4.5, -4.5, 4.5, 4.5, 4.5]
+        return
+    pts = torch.from_numpy(G["points"])
     coors = pts.new_zeros((pts.shape[0], 3), dtype=torch.int)
     ext.dynamic_voxelize(pts, coors, vs, rng, 3)
     assert np.array_equal(coors.numpy(), VZ.dynamic_voxelize(pts.numpy(), vs, rng))

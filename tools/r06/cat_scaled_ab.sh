@@ -14,7 +14,7 @@ for v in 0 1; do
   echo "== SF_WINO_CAT_SCALED=$v"; grep -E "in_scale=1|add_scale=1|epi=4" $out/summary_$v.txt
 done
 for v in 0 1 0 1; do
-  SF_WINO_CAT_SCALED=$v timeout 600 python bench.py --steps 10 --warmup 3 --headline-only > $out/bench_$v.json 2> $out/bench_$v.err
+  SF_WINO_CAT_SCALED=$v timeout 600 python bench.py --steps 10 --warmup 3 --full --headline-only > $out/bench_$v.json 2> $out/bench_$v.err
   python - <<PY
 import json
 d=json.loads(open("$out/bench_$v.json").read().strip().splitlines()[-1])

@@ -7,7 +7,7 @@ out=gpurun_out/${1:-ln7}
 mkdir -p $out
 timeout 900 python -m pytest tests/test_gpu_ops.py -x -q -m gpu -p no:cacheprovider -k "tap_groups or c64" 2>&1 | tail -15
 for v in 0 1; do
-  SF_WINO_LN7=$v timeout 600 python bench.py --steps 10 --warmup 3 --headline-only > $out/bench_$v.json 2> $out/bench_$v.err
+  SF_WINO_LN7=$v timeout 600 python bench.py --steps 10 --warmup 3 --full --headline-only > $out/bench_$v.json 2> $out/bench_$v.err
   python - <<PY
 import json
 d=json.loads(open("$out/bench_$v.json").read().strip().splitlines()[-1])

@@ -7,7 +7,7 @@ out=gpurun_out/${1:-smp}
 mkdir -p $out
 timeout 1500 python -m pytest tests/test_gpu_ops.py tests/test_gpu_conv_random.py tests/test_gpu_philox.py -x -q -m gpu -p no:cacheprovider -k "infer_state or epilogues_of_the_batched or c64 or golden or philox or noise" 2>&1 | tail -6
 for v in 0 1; do
-  SF_WINO_SAMPLE=$v timeout 600 python bench.py --steps 10 --warmup 3 --headline-only > $out/bench_$v.json 2> $out/bench_$v.err
+  SF_WINO_SAMPLE=$v timeout 600 python bench.py --steps 10 --warmup 3 --full --headline-only > $out/bench_$v.json 2> $out/bench_$v.err
   python - <<PY
 import json
 d=json.loads(open("$out/bench_$v.json").read().strip().splitlines()[-1])

@@ -19,7 +19,7 @@ for thr in 0 512 700 1000 1400 2600; do
   done
 done
 for thr in 0 512 2600; do
-  SF_WINO_SMALL_WGS=$thr timeout 600 python bench.py --steps 10 --warmup 3 --headline-only > $out/bench_$thr.json 2> $out/bench_$thr.err
+  SF_WINO_SMALL_WGS=$thr timeout 600 python bench.py --steps 10 --warmup 3 --full --headline-only > $out/bench_$thr.json 2> $out/bench_$thr.err
   python - <<PY
 import json
 d=json.loads(open("$out/bench_$thr.json").read().strip().splitlines()[-1])
