@@ -104,11 +104,6 @@ typedef struct sf_dual_w {
    * bias and the sigmoid, gates1_s = W[:, C:] on s with neither.  In a rollout the s half is accumulated beside the
    * previous infer_state (the state is known five launches before x is) and added to the x half's sums. */
   sf_conv_w gates1_x, gates1_s;
-  /* optional (w == NULL: unused), round 6: the two input halves of the trusting gate's 7x7 packed on their own — tg7_h = W[:, :C] on rnn_state1
-   * with the LayerNorm weight / bias, tg7_r = W[:, C:] on rnn_state2 with neither.  In a rollout rnn_state2 = conv_decoder_2(h2) is a
-   * function of the state alone: its half of the 7x7 (half of the longest launch of a step) runs on a forked stream beside the previous
-   * infer_state and is added to the rnn_state1 half's sums. */
-  sf_conv_w tg7_h, tg7_r;
 } sf_dual_w;
 
 /* ResBlock (streamingflow/layers/res_models.py:52-79) */
@@ -179,12 +174,12 @@ int sf_flow_errors(void* stream);
 /* ---- ABI guard ---------------------------------------------------------------------------------------------------------
  * The structs above are passed by pointer and sf_conv_w is embedded by value in every composite, so a host compiled
  * against an older header would hand the library mis-sized structs (round 3 grew sf_conv_w from 72 to 80 bytes and
- * sf_dual_w by two members).  SF_ABI_VERSION changes whenever a public struct changes layout.  A host calls
- * sf_abi_check_header() once after loading the library — it passes the sizes ITS compiler saw — and must not call
- * anything else unless it returns SF_OK; bindings without a C compiler (ctypes, cgo, JNI) compare their own struct sizes
+ * sf_dual_w by two members; version 6 added two more to sf_dual_w, the input halves of the trusting gate's 7x7, and version 7
+ * removed them again).  SF_ABI_VERSION changes whenever a public struct changes layout.  A host calls sf_abi_check_header()
+ * once after loading the library — it passes the sizes ITS compiler saw — and must not call anything else unless it returns SF_OK; bindings without a C compiler (ctypes, cgo, JNI) compare their own struct sizes
  * with sf_abi_sizeof() the same way (streamingflow_amd/_lib.py does, INTEGRATION.md shows it).  Hosts must zero-initialise
  * the structs (optional members are "NULL = absent") and recompile when SF_ABI_VERSION changes. */
-#define SF_ABI_VERSION 6
+#define SF_ABI_VERSION 7
 enum {
   SF_STRUCT_CONV_W = 0, SF_STRUCT_GRU_W, SF_STRUCT_DUAL_W, SF_STRUCT_RES_W, SF_STRUCT_PMODEL_W, SF_STRUCT_ENCODER_W,
   SF_STRUCT_DECODER_W, SF_STRUCT_CONVNEXT_W, SF_STRUCT_DEEPLAB_W, SF_STRUCT_BOTTLENECK_W, SF_STRUCT_BOTTLE_W, SF_STRUCT_COUNT

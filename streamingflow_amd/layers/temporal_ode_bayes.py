@@ -114,9 +114,6 @@ class _DualCell(PackedModule):
         bb = self.trusting_gate[0]
         L = bb.layers
         s.tg7 = packing.conv_w(pk, L[0].weight, C, C, scale=L[1].weight, bias=L[1].bias)
-        # its two input halves on their own (rollout: the rnn_state2 half is accumulated on a forked stream beside the previous infer_state)
-        s.tg7_h = packing.conv_w(pk, L[0].weight[:, :C], C, scale=L[1].weight, bias=L[1].bias)
-        s.tg7_r = packing.conv_w(pk, L[0].weight[:, C:], C)
         s.tg1 = packing.conv_w(pk, L[3].weight, C, scale=L[4].weight, bias=L[4].bias)
         s.tg3 = packing.conv_w(pk, L[6].weight, C, scale=L[7].weight, bias=L[7].bias)
         s.tgproj = packing.conv_w(pk, bb.projection[0].weight, C, C)

@@ -25,10 +25,12 @@ def test_build_and_symbols():
     assert lib.sf_dual_cell_ws_bytes(64, 1, 50, 50) >= 10 * 64 * 2500 * 4
 
 
-def test_struct_sizes_match_header_layout():
+def test_struct_sizes_match_abi7_header_layout():
     from streamingflow_amd import _lib
+    assert _lib.SF_ABI_VERSION == 7      # the layout below is version 7's: a layout change bumps the version and this test with it
     assert ctypes.sizeof(_lib.ConvW) == 3 * 8 + 12 * 4 + 2 * 8  # 3 pointers + 11 int32 + 1 reserved + the optional split-bf16 and Winograd weight pointers
-    assert ctypes.sizeof(_lib.DualW) == 13 * ctypes.sizeof(_lib.ConvW) + 16      # + gates1_x / gates1_s (round 3), tg7_h / tg7_r (round 6)
+    assert ctypes.sizeof(_lib.DualW) == 11 * ctypes.sizeof(_lib.ConvW) + 16      # + gates1_x / gates1_s (round 3)
+    assert [f[0] for f in _lib.DualW._fields_][-2:] == ["gates1_x", "gates1_s"]
     assert ctypes.sizeof(_lib.GruW) == 3 * ctypes.sizeof(_lib.ConvW)
     assert ctypes.sizeof(_lib.ResW) == 3 * ctypes.sizeof(_lib.ConvW)
 
