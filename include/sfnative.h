@@ -294,6 +294,46 @@ int sf_nnfo_rollout_philox_fwd(const sf_dual_w* gru_c, const sf_dual_w* gru_obs,
                                const int32_t* ops, int n_ops, const float* hx_obs, const uint64_t* philox_state, const float* coef,
                                int coef_per_image, const int32_t* sel_nops, int n_targets, float* out_states, float* final_state,
                                int n_img, int H, int W, float* ws, size_t ws_bytes, void* stream);
+/* Resumable forms: the same rollout cut into SEGMENTS that separate calls run one after the other (a streaming caller appends one
+ * observation per call and forks predictions from the carried state; streamingflow_amd.StreamSession).  The arguments of the entry
+ * points above, plus:
+ *   state_in, p_in  [n_img][H*W][C]: latent state and imputed input the segment starts from; NULL = zeros (both NULL, draw_base 0 and
+ *                   the three outputs below NULL: exactly the entry points above, which are implemented that way).  Never written.
+ *   draw_base       index of the segment's first noise draw in the numbering of the whole rollout.  The Philox form keys draw k of the
+ *                   segment by draw_base + k under the same {seed, offset} record.  eps is the segment's OWN tensor — the caller passes
+ *                   the whole rollout's pointer advanced by draw_base draws — and draw k of the segment reads eps[k].
+ *   p_out           [n_img][H*W][C] or NULL: the imputed input after the last op.  Non-NULL keeps the infer_state pass of the last op,
+ *                   which the entry points above skip; the next segment may start with a step that reads it.
+ *   carry_in/_out   sf_nnfo_rollout_carry_bytes each, or NULL.  With IMPUTE the unsplit rollout computes part of the ODE cell that follows
+ *                   an infer_state inside that infer_state's launches, and the launch grouping fixes the split-K summation order.  A segment
+ *                   given carry_out (needs p_out) does the same for the cell behind the boundary and the next segment, given it as
+ *                   carry_in (needs state_in and p_in of the same boundary), consumes it when its first op is a step: the segments then
+ *                   reproduce the unsplit rollout BITWISE.  With NULL the boundary cell is computed on its own: same arithmetic,
+ *                   a different summation order (differences of rounding size).  Opaque; valid only next to the state_in / p_in it was
+ *                   written with.
+ * sel_nops counts the ops of THIS segment (1-based); n_targets may be 0 (sel_nops, out_states NULL).  hx_obs holds the segment's
+ * own observations (a jump's argument indexes it) and may be NULL for a segment without jumps.  n_ops may be 0: final_state and
+ * p_out are then copies of state_in and p_in, and carry_out must be NULL (SF_ERR_INVALID: there is no infer_state to compute it
+ * beside; keep the carry the boundary already has).
+ * Aliasing: final_state may be state_in, p_out may be p_in and carry_out may be carry_in (in-place update of a carried boundary): the
+ * inputs are consumed by the segment's first cell, the outputs written after its last.  Otherwise outputs must not overlap inputs,
+ * out_states or the workspace.
+ * Enqueue only (no allocation, no synchronisation): a segment is captured into a graph like any rollout.
+ * Persistent flow (sf_set_flow_mode / SF_PERSIST): a call with state_in, p_in or p_out runs in the launch-per-layer form whatever the
+ * switch says (never from zeros, never with bounded waits); sf_flow_errors then reports SF_ERR_INVALID as for any launch-path rollout.
+ * The forked 7x7 stream (SF_FORK7) no longer exists in the library, so there is no second rollout form a segment could take. */
+int sf_nnfo_rollout_resume_fwd(const sf_dual_w* gru_c, const sf_dual_w* gru_obs, const sf_pmodel_w* pm, int solver, int impute,
+                               const int32_t* ops, int n_ops, const float* hx_obs, const float* eps, const float* coef,
+                               int coef_per_image, const int32_t* sel_nops, int n_targets, float* out_states, float* final_state,
+                               const float* state_in, const float* p_in, const float* carry_in, int draw_base, float* p_out,
+                               float* carry_out, int n_img, int H, int W, float* ws, size_t ws_bytes, void* stream);
+int sf_nnfo_rollout_resume_philox_fwd(const sf_dual_w* gru_c, const sf_dual_w* gru_obs, const sf_pmodel_w* pm, int solver, int impute,
+                                      const int32_t* ops, int n_ops, const float* hx_obs, const uint64_t* philox_state,
+                                      const float* coef, int coef_per_image, const int32_t* sel_nops, int n_targets, float* out_states,
+                                      float* final_state, const float* state_in, const float* p_in, const float* carry_in,
+                                      int draw_base, float* p_out, float* carry_out, int n_img, int H, int W, float* ws,
+                                      size_t ws_bytes, void* stream);
+size_t sf_nnfo_rollout_carry_bytes(int C, int n_img, int H, int W);
 int sf_infer_state_philox_fwd(const sf_pmodel_w* w, const float* s, const uint64_t* philox_state, int draw, float* p_out, float* q_out,
                               int n_img, int H, int W, float* ws, size_t ws_bytes, void* stream);
 

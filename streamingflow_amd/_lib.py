@@ -116,6 +116,11 @@ SIGNATURES = {
                                  _vp, _i, i32p, _i, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
     "sf_nnfo_rollout_philox_fwd": (_i, [C.POINTER(DualW), C.POINTER(DualW), C.POINTER(PModelW), _i, _i, i32p, _i, _vp, _vp,
                                         _vp, _i, i32p, _i, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
+    "sf_nnfo_rollout_resume_fwd": (_i, [C.POINTER(DualW), C.POINTER(DualW), C.POINTER(PModelW), _i, _i, i32p, _i, _vp, _vp,
+                                        _vp, _i, i32p, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
+    "sf_nnfo_rollout_resume_philox_fwd": (_i, [C.POINTER(DualW), C.POINTER(DualW), C.POINTER(PModelW), _i, _i, i32p, _i, _vp, _vp,
+                                               _vp, _i, i32p, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
+    "sf_nnfo_rollout_carry_bytes": (_sz, [_i, _i, _i, _i]),
     "sf_infer_state_philox_fwd": (_i, [C.POINTER(PModelW), _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
     "sf_nnfo_rollout_ws_bytes": (_sz, [_i, _i, _i, _i]),
     "sf_small_encoder_fwd": (_i, [C.POINTER(EncoderW), _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),

@@ -1654,6 +1654,23 @@ struct Stage {
   int op_end;      // index of the op this stage completes (-1: an inner solver stage)
 };
 
+// What a resumed segment takes over from / hands on to its neighbours besides the state and the imputed input: the carried branch 2
+// of the ODE cell that follows the boundary (struct Carry), [g2 2PC | g1s 2PC | rs2 PC | h2 PC] in caller memory.
+struct ResumeCarry {
+  const float* in = nullptr;         // written by the segment before this one (first op an ODE step: consumed)
+  float* out = nullptr;              // written beside the last infer_state of this segment
+  const sf_dual_w* next_w = nullptr; // the cell after the boundary (gru_c)
+  bool allow_flow = true;            // false: launch-per-layer form whatever SF_PERSIST / sf_set_flow_mode say
+  int draw0 = 0;                     // number of the segment's first draw: eps holds the segment's own draws, Philox is keyed by the number
+};
+size_t carry_floats(size_t PC) { return 2 * al(2 * PC) + 2 * al(PC); }
+Carry carry_view(float* base, size_t PC) {
+  Carry c;
+  c.g2 = base; c.g1s = base + al(2 * PC); c.rs2 = base + 2 * al(2 * PC); c.h2 = c.rs2 + al(PC);
+  return c;
+}
+bool carries_gates1_s(const sf_dual_w& w) { return w.gates1_x.w && w.gates1_s.w && tune().pipe >= 2; }
+
 size_t rollout_ws_floats(int C, int P) {
   const size_t cellw = dual_ws_floats(C, P), inf = infer_ws_floats(C, P);
   // the persistent flow's tables and counters (5 MB) only where the flow form is switched on at the time of the query: the size query and
@@ -1663,14 +1680,15 @@ size_t rollout_ws_floats(int C, int P) {
 }
 
 int run_stages(const std::vector<Stage>& stages, const sf_pmodel_w& pm, const float* eps, const unsigned long long* philox, int coef_stride,
-               const int32_t* sel_nops, int n_targets, float* out_states, int B, int H, int W, Arena& A, hipStream_t st, const unsigned** flow_err) {
+               const int32_t* sel_nops, int n_targets, float* out_states, int B, int H, int W, Arena& A, hipStream_t st, const unsigned** flow_err,
+               const ResumeCarry& rc = ResumeCarry()) {
   const size_t PC = (size_t)B * H * W * pm.C;
   // buffers of the carried branch 2 (outside the per-stage arenas: written during one stage's infer_state, read by the next cell)
   Carry cb, cnow;
   cb.g2 = A.take(2 * PC); cb.rs2 = A.take(PC); cb.h2 = A.take(PC); cb.g1s = A.take(2 * PC);
   cnow = cb;
   // one latent: the launch groups of the stages become phases of ONE persistent flow launch (conv_sp.hip: sp_flow_kernel)
-  const bool persist = (g_flow_mode < 0 ? tune().persist : g_flow_mode) && B == 1 && (long)B * H * W < tune().sp_max_p && tune().sp && g_split != nullptr;
+  const bool persist = rc.allow_flow && (g_flow_mode < 0 ? tune().persist : g_flow_mode) && B == 1 && (long)B * H * W < tune().sp_max_p && tune().sp && g_split != nullptr;
   unsigned char* table = persist ? reinterpret_cast<unsigned char*>(A.take(FLOW_TABLE_BYTES / 4)) : nullptr;
   unsigned* done = persist ? reinterpret_cast<unsigned*>(A.take(FLOW_DONE_COUNTERS + 64)) : nullptr;
   if (!A.ok()) return SF_ERR_WORKSPACE;
@@ -1683,6 +1701,13 @@ int run_stages(const std::vector<Stage>& stages, const sf_pmodel_w& pm, const fl
   if (persist) SF_HIP(zero_fill(done, (FLOW_DONE_COUNTERS + 64) * sizeof(unsigned), st));
   *flow_err = persist ? done + FLOW_DONE_COUNTERS : nullptr;
   bool carried = false;
+  // a resumed segment that starts with an ODE step: branch 2 of its first cell was computed beside the infer_state that closed the
+  // segment before it (rc.in), exactly as the unsplit rollout computes it beside the infer_state of the op before
+  if (rc.in && !stages.empty() && stages[0].derivative && carry_ok(*stages[0].w, pm, B, H, W)) {
+    cnow = carry_view(const_cast<float*>(rc.in), PC);
+    if (!carries_gates1_s(*stages[0].w)) cnow.g1s = nullptr;
+    carried = true;
+  }
   for (size_t j = 0; j < stages.size(); ++j) {
     const Stage& g = stages[j];
     Arena Ac = A;
@@ -1700,29 +1725,38 @@ int run_stages(const std::vector<Stage>& stages, const sf_pmodel_w& pm, const fl
       Arena Ai = A;
       Side sd = {};
       const Stage* nx = j + 1 < stages.size() ? &stages[j + 1] : nullptr;
-      const bool pipe = nx && nx->s == g.out && carry_ok(*nx->w, pm, B, H, W);
+      // the last infer_state of a segment that hands its boundary on (rc.out): the side problems of the ODE cell that follows it
+      const sf_dual_w* nw = nx ? (nx->s == g.out ? nx->w : nullptr) : (rc.out ? rc.next_w : nullptr);
+      const bool pipe = nw && carry_ok(*nw, pm, B, H, W);
       if (pipe) {
-        side_problems(*nx->w, g.out, cb, B, H, W, sd);
+        side_problems(*nw, g.out, nx ? cb : carry_view(rc.out, PC), B, H, W, sd);
         cnow = cb;
         if (sd.n < 3) cnow.g1s = nullptr;
       }
-      SF_TRY(infer_state(pm, g.out, eps ? eps + (size_t)g.draw * PC : nullptr, g.p_out, nullptr, B, H, W, Ai, st, philox, g.draw, pipe ? &sd : nullptr));
-      carried = pipe;
+      SF_TRY(infer_state(pm, g.out, eps ? eps + (size_t)(g.draw - rc.draw0) * PC : nullptr, g.p_out, nullptr, B, H, W, Ai, st, philox, g.draw, pipe ? &sd : nullptr));
+      carried = pipe && nx;
     }
   }
   return seg_flush();
 }
 
 size_t sf_nnfo_rollout_ws_bytes(int C, int n_img, int H, int W) { return rollout_ws_floats(C, n_img * H * W) * sizeof(float); }
+size_t sf_nnfo_rollout_carry_bytes(int C, int n_img, int H, int W) { return carry_floats((size_t)n_img * H * W * C) * sizeof(float); }
+// One segment of the rollout.  state_in / p_in (NULL: zeros) are read, never written; draws are numbered from draw_base; p_out != NULL
+// keeps the infer_state of the last op.  The one-shot entry points are this with (NULL, NULL, NULL, 0, NULL, NULL).
 static int rollout_core(const sf_dual_w* gru_c, const sf_dual_w* gru_obs, const sf_pmodel_w* pm, int solver, int impute,
                         const int32_t* ops, int n_ops, const float* hx_obs, const float* eps, const unsigned long long* philox,
                         const float* coef, int coef_per_image, const int32_t* sel_nops, int n_targets, float* out_states,
-                        float* final_state, int n_img, int H, int W, float* ws, size_t ws_bytes, void* stream) {
-  if (!gru_c || !gru_obs || !pm || !ops || !hx_obs || (!eps && !philox) || !sel_nops || !out_states || n_img < 1) return SF_ERR_INVALID;
+                        float* final_state, const float* state_in, const float* p_in, const float* carry_in, int draw_base,
+                        float* p_out, float* carry_out, int n_img, int H, int W, float* ws, size_t ws_bytes, void* stream) {
+  if (!gru_c || !gru_obs || !pm || (!ops && n_ops > 0) || (!eps && !philox) || n_img < 1 || n_ops < 0 || n_targets < 0 || draw_base < 0) return SF_ERR_INVALID;
+  if (n_targets > 0 && (!sel_nops || !out_states)) return SF_ERR_INVALID;
+  if ((carry_in && (!state_in || !p_in)) || (carry_out && (!p_out || n_ops == 0))) return SF_ERR_INVALID;      // (no op: no infer_state to compute the carry beside)
   if (gru_c->C > 128 || (gru_c->C % 8)) return SF_ERR_UNSUPPORTED;
   if (solver != SF_SOLVER_EULER && solver != SF_SOLVER_MIDPOINT && solver != SF_SOLVER_RK4) return SF_ERR_INVALID;
   const int C = gru_c->C, B = n_img;
   const size_t PC = (size_t)B * H * W * C;
+  const bool resumed = state_in || p_in || p_out;
   Arena A(ws, ws_bytes);
   SplitScope sp(A, (hipStream_t)stream);
   float* zeros = A.take(PC);
@@ -1735,9 +1769,12 @@ static int rollout_core(const sf_dual_w* gru_c, const sf_dual_w* gru_obs, const 
   if (!A.ok()) return SF_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   SF_HIP(zero_fill(zeros, al(PC) * sizeof(float), st));
-  SF_HIP(zero_fill(sbuf[0], al(PC) * sizeof(float), st));   // state = zeros  (temporal_ode_bayes.py:507)
-  SF_HIP(zero_fill(pbuf[0], al(PC) * sizeof(float), st));   // input: overwritten by the first jump (:565,574)
-  int si = 0, pi = 0, draw = 0;
+  if (!state_in) SF_HIP(zero_fill(sbuf[0], al(PC) * sizeof(float), st));   // state = zeros  (temporal_ode_bayes.py:507)
+  if (!p_in) SF_HIP(zero_fill(pbuf[0], al(PC) * sizeof(float), st));       // input: overwritten by the first jump (:565,574)
+  // the carried state / input are read where they lie (the first op writes sbuf[1] / pbuf[1]); nothing below writes through s_cur / p_cur
+  const float* s_cur = state_in ? state_in : sbuf[0];
+  const float* p_cur = p_in ? p_in : pbuf[0];
+  int si = 0, pi = 0, draw = draw_base;
   const int cstride = coef_per_image ? SF_COEF_STRIDE : 0;
   const size_t step_stride = (size_t)SF_COEF_STRIDE * (coef_per_image ? B : 1);
   std::vector<Stage> stages;
@@ -1745,15 +1782,21 @@ static int rollout_core(const sf_dual_w* gru_c, const sf_dual_w* gru_obs, const 
     const int kind = ops[2 * i], arg = ops[2 * i + 1];
     // the imputed input this op leaves behind is only read by a following ODE step (:446-455); a jump ignores it
     // (:327-344) and then overwrites it (:574), and nothing reads it after the last op: those infer_state passes
-    // are skipped (their noise draw keeps its index)
+    // are skipped (their noise draw keeps its index) — unless the caller takes it over as p_out
     const bool next_is_step = (i + 1 < n_ops) && ops[2 * (i + 1)] == SF_OP_STEP;
-    const bool need_p = impute && next_is_step;
-    float* s = sbuf[si]; float* s2 = sbuf[si ^ 1];
-    float* p = pbuf[pi]; float* p2 = pbuf[pi ^ 1];
+    const bool last = i + 1 == n_ops;
+    const bool need_p = (impute && next_is_step) || (last && p_out);
+    const float* s = s_cur; float* s2 = sbuf[si ^ 1];
+    const float* p = p_cur; float* p2 = (last && p_out) ? p_out : pbuf[pi ^ 1];
     if (kind == SF_OP_JUMP) {   // :562-574
-      stages.push_back(Stage{gru_obs, hx_obs + (size_t)arg * PC, s, s2, 0, nullptr, nullptr, nullptr, 0, need_p, draw, p, i});
+      // (the jump's imputed input replaces the current one in place; p_in itself is never written)
+      float* pj = (last && p_out) ? p_out : pbuf[pi];
+      if (!hx_obs) return SF_ERR_INVALID;      // (NULL is fine for a segment without jumps)
+      stages.push_back(Stage{gru_obs, hx_obs + (size_t)arg * PC, s, s2, 0, nullptr, nullptr, nullptr, 0, need_p, draw, pj, i});
       draw += 1;
       si ^= 1;
+      s_cur = s2;
+      if (need_p) p_cur = pj;
     } else if (kind == SF_OP_STEP) {
       if (!coef) return SF_ERR_INVALID;
       const float* cf = coef + (size_t)arg * step_stride;
@@ -1779,13 +1822,26 @@ static int rollout_core(const sf_dual_w* gru_c, const sf_dual_w* gru_obs, const 
       }
       si ^= 1;
       pi ^= 1;
+      s_cur = s2;
+      p_cur = p2;
     } else {
       return SF_ERR_INVALID;
     }
   }
   const unsigned* flow_err = nullptr;
-  SF_TRY(run_stages(stages, *pm, eps, philox, cstride, sel_nops, n_targets, out_states, B, H, W, A, st, &flow_err));
-  if (final_state) SF_HIP(copy_floats(sbuf[si], final_state, PC, st));
+  ResumeCarry rc;
+  // The boundary of an IMPUTE rollout lies between an infer_state and the ODE cell that reads its sample: the unsplit rollout
+  // computes branch 2 of that cell beside the infer_state (struct Carry), and the launch grouping decides the split-K summation
+  // order — so a segment that hands p_out on computes the same side problems into carry_out, and the next one consumes them.
+  // Without IMPUTE no cell follows an infer_state it depends on (a step reads zeros): nothing is carried.
+  rc.in = impute ? carry_in : nullptr;
+  rc.out = impute ? carry_out : nullptr;
+  rc.next_w = gru_c;
+  rc.draw0 = draw_base;
+  rc.allow_flow = !resumed;      // a resumed segment always runs in the launch-per-layer form (sfnative.h)
+  SF_TRY(run_stages(stages, *pm, eps, philox, cstride, sel_nops, n_targets, out_states, B, H, W, A, st, &flow_err, rc));
+  if (final_state && final_state != s_cur) SF_HIP(copy_floats(s_cur, final_state, PC, st));
+  if (p_out && n_ops == 0 && p_out != p_cur) SF_HIP(copy_floats(p_cur, p_out, PC, st));
   if (flow_err) {      // the flow kernel's bounded waits: a timeout must not pass as a result
     hipLaunchKernelGGL(flow_poison_kernel, dim3(256), dim3(256), 0, st, flow_err, out_states, (size_t)n_targets * PC, final_state, final_state ? PC : 0);
     SF_HIP(hipGetLastError());
@@ -1799,18 +1855,39 @@ int sf_nnfo_rollout_fwd(const sf_dual_w* gru_c, const sf_dual_w* gru_obs, const 
                         const int32_t* ops, int n_ops, const float* hx_obs, const float* eps, const float* coef,
                         int coef_per_image, const int32_t* sel_nops, int n_targets, float* out_states,
                         float* final_state, int n_img, int H, int W, float* ws, size_t ws_bytes, void* stream) {
+  if (!eps || !ops || !hx_obs || !sel_nops || !out_states) return SF_ERR_INVALID;
+  return rollout_core(gru_c, gru_obs, pm, solver, impute, ops, n_ops, hx_obs, eps, nullptr, coef, coef_per_image, sel_nops, n_targets,
+                      out_states, final_state, nullptr, nullptr, nullptr, 0, nullptr, nullptr, n_img, H, W, ws, ws_bytes, stream);
+}
+// resumable form: see sfnative.h.  eps holds the segment's own draws (draw k of the segment reads eps[k]); draw_base keys the Philox form
+int sf_nnfo_rollout_resume_fwd(const sf_dual_w* gru_c, const sf_dual_w* gru_obs, const sf_pmodel_w* pm, int solver, int impute,
+                               const int32_t* ops, int n_ops, const float* hx_obs, const float* eps, const float* coef,
+                               int coef_per_image, const int32_t* sel_nops, int n_targets, float* out_states, float* final_state,
+                               const float* state_in, const float* p_in, const float* carry_in, int draw_base, float* p_out,
+                               float* carry_out, int n_img, int H, int W, float* ws, size_t ws_bytes, void* stream) {
   if (!eps) return SF_ERR_INVALID;
   return rollout_core(gru_c, gru_obs, pm, solver, impute, ops, n_ops, hx_obs, eps, nullptr, coef, coef_per_image, sel_nops, n_targets,
-                      out_states, final_state, n_img, H, W, ws, ws_bytes, stream);
+                      out_states, final_state, state_in, p_in, carry_in, draw_base, p_out, carry_out, n_img, H, W, ws, ws_bytes, stream);
+}
+int sf_nnfo_rollout_resume_philox_fwd(const sf_dual_w* gru_c, const sf_dual_w* gru_obs, const sf_pmodel_w* pm, int solver, int impute,
+                                      const int32_t* ops, int n_ops, const float* hx_obs, const uint64_t* philox_state, const float* coef,
+                                      int coef_per_image, const int32_t* sel_nops, int n_targets, float* out_states, float* final_state,
+                                      const float* state_in, const float* p_in, const float* carry_in, int draw_base, float* p_out,
+                                      float* carry_out, int n_img, int H, int W, float* ws, size_t ws_bytes, void* stream) {
+  if (!philox_state) return SF_ERR_INVALID;
+  return rollout_core(gru_c, gru_obs, pm, solver, impute, ops, n_ops, hx_obs, nullptr, reinterpret_cast<const unsigned long long*>(philox_state),
+                      coef, coef_per_image, sel_nops, n_targets, out_states, final_state, state_in, p_in, carry_in, draw_base, p_out, carry_out,
+                      n_img, H, W, ws, ws_bytes, stream);
 }
 // the same with the Gaussian noise of infer_state generated in the sampling epilogue (Philox4x32-10, csrc/sf_math.h)
 int sf_nnfo_rollout_philox_fwd(const sf_dual_w* gru_c, const sf_dual_w* gru_obs, const sf_pmodel_w* pm, int solver, int impute,
                                const int32_t* ops, int n_ops, const float* hx_obs, const uint64_t* philox_state, const float* coef,
                                int coef_per_image, const int32_t* sel_nops, int n_targets, float* out_states, float* final_state,
                                int n_img, int H, int W, float* ws, size_t ws_bytes, void* stream) {
-  if (!philox_state) return SF_ERR_INVALID;
+  if (!philox_state || !ops || !hx_obs || !sel_nops || !out_states) return SF_ERR_INVALID;
   return rollout_core(gru_c, gru_obs, pm, solver, impute, ops, n_ops, hx_obs, nullptr, reinterpret_cast<const unsigned long long*>(philox_state),
-                      coef, coef_per_image, sel_nops, n_targets, out_states, final_state, n_img, H, W, ws, ws_bytes, stream);
+                      coef, coef_per_image, sel_nops, n_targets, out_states, final_state, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
+                      n_img, H, W, ws, ws_bytes, stream);
 }
 int sf_infer_state_philox_fwd(const sf_pmodel_w* w, const float* s, const uint64_t* philox_state, int draw, float* p_out, float* q_out,
                               int n_img, int H, int W, float* ws, size_t ws_bytes, void* stream) {

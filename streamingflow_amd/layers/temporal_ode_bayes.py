@@ -507,6 +507,12 @@ class NNFOwithBayesianJumps(nn.Module):
                     L.sf_set_flow_mode(int(bool(was)) if _pk._FLOW[0] is not None else -1)
         return (out[:, 0], final[0]) if one else (out, final)
 
+    def stream(self, delta_t, history=16, **kw):
+        """Open a streaming session on this module (streamingflow_amd.stream.StreamSession): the latent state carried across
+        ``observe(t, hx)`` calls, ``predict(targets)`` from a fork of it."""
+        from ..stream import StreamSession
+        return StreamSession(self, delta_t, history=history, **kw)
+
     def make_schedule(self, times, delta_t, T):
         return sched.build_schedule([float(t) for t in times], [float(t) for t in T], delta_t,
                                     self.use_variable_ode_step, self.solver)

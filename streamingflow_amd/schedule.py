@@ -104,3 +104,137 @@ def build_schedule(times, targets, delta_t, variable, solver="euler") -> Schedul
         sch.sel_nops.append(path_n[idx])
     sch.path_t = path_t
     return sch
+
+
+@dataclass
+class Branch:
+    """What ``StreamSchedule.predict`` returns: the steps of the target loop as a segment (``seg.sel_nops`` counts the ops of
+    the segment, one entry per target the branch itself answers) and, per target in the order given, where its state comes from."""
+    seg: Schedule
+    sel_nops: List[int]          # per target: ops applied since reset() — the one-shot schedule's ``sel_nops``
+    source: List[Tuple[str, int]]  # per target: ("trunk", index into the kept path entries) | ("branch", row of the segment's out_states)
+    base_ops: int                # ops / draws of the trunk the branch forks from
+    base_draws: int
+
+
+class StreamSchedule:
+    """``build_schedule`` in incremental form, for a caller that learns one observation per call (StreamSession).
+
+    ``observe(t)`` returns the segment the observation loop (temporal_ode_bayes.py:539-581) appends for an observation at ``t``:
+    the steps of :541-549 from the carried ``current_time``, then the jump.  ``predict(targets)`` runs the target loop (:585-604)
+    and the selection (:606-620) on a COPY of ``current_time``: the trunk is not advanced, so any number of predicts may lie
+    between two observes.  Concatenating the segments of every ``observe`` and of a final ``predict`` gives exactly the ops, the
+    float64 step sizes and the selection of ``build_schedule(times, targets, ...)`` — the observation loop never looks at the
+    targets (tests/test_stream_schedule.py pins this on the 44 reference-captured schedules).
+
+    The selection runs over the path entries the trunk recorded (one per observation) plus the ones the branch adds.  Only the
+    last ``history`` trunk entries are kept (None: all); ``predict`` raises ValueError when an evicted entry could be the answer:
+    when no kept or branch entry lies within half a delta_t of the target (the reference then takes the nearest entry of the WHOLE
+    path, the first one on ties) and an evicted entry may be as near as the nearest kept one.  Evicted entries are older than every
+    kept one and a window match takes the LATEST entry, so a target with a kept entry in its window never depends on them.
+
+    A segment numbers its steps and its single observation from 0; ``n_ops`` / ``n_draws`` are the totals since ``reset()``.
+    """
+
+    def __init__(self, delta_t, variable, solver="euler", history=None):
+        if history is not None and int(history) < 1:
+            raise ValueError("history must be at least 1 path entry (or None for all)")
+        self.delta_t, self.variable, self.per_step = float(delta_t), bool(variable), DRAWS_PER_STEP[solver]
+        self.history = None if history is None else int(history)
+        self.reset()
+
+    def reset(self):
+        self.current_time = None
+        self.n_ops = self.n_draws = self.n_obs = 0
+        self.path_t, self.path_n = [], []        # kept trunk path entries
+        self.evicted, self.evicted_tmax = 0, None
+
+    @property
+    def last_time(self):
+        """Time of the latest observation (None before the first): the next one must not be earlier."""
+        return self.path_t[-1] if self.path_t else None
+
+    def plan_observe(self, t) -> Schedule:
+        """The segment an observation at ``t`` appends, WITHOUT advancing the trunk: a caller that may fail while enqueuing it
+        (StreamSession) commits afterwards.  The segment carries the advanced time in ``path_t``."""
+        t = float(t)
+        if self.path_t and t < self.path_t[-1]:
+            raise ValueError(f"observation at {t} after one at {self.path_t[-1]}: a stream cannot be sorted afterwards "
+                             "(the reference sorts the whole window); feed observations in time order")
+        seg = Schedule()
+        ct = t if self.current_time is None else self.current_time             # :508, times.min() of a sorted stream
+        while ct <= (t - self.delta_t):                                        # :541
+            dt = (t - ct) if self.variable else self.delta_t                   # :546-549
+            seg.ops.append((OP_STEP, len(seg.dts)))
+            seg.dts.append(dt)
+            seg.n_draws += self.per_step
+            ct = ct + dt                                                       # :458
+        seg.ops.append((OP_JUMP, 0))                                           # :565
+        seg.n_draws += 1                                                       # :574
+        seg.path_t = [t, ct]
+        return seg
+
+    def commit_observe(self, seg):
+        """Advance the trunk by a segment ``plan_observe`` returned (for the trunk as it was then)."""
+        t, ct = seg.path_t
+        self.current_time = ct
+        self.n_ops += len(seg.ops)
+        self.n_draws += seg.n_draws
+        self.n_obs += 1
+        self.path_t.append(t)                                                  # :578-581
+        self.path_n.append(self.n_ops)
+        seg.path_t = [t]
+        while self.history is not None and len(self.path_t) > self.history:
+            self.evicted_tmax = self.path_t.pop(0)
+            self.path_n.pop(0)
+            self.evicted += 1
+
+    def observe(self, t) -> Schedule:
+        seg = self.plan_observe(t)
+        self.commit_observe(seg)
+        return seg
+
+    def predict(self, targets) -> Branch:
+        if self.current_time is None:
+            raise RuntimeError("predict before any observation: the rollout starts at the first observation's time")
+        targets = [float(x) for x in targets]
+        dt_, seg = self.delta_t, Schedule()
+        ct = self.current_time                                                 # a copy: the trunk is not advanced
+        bt, bn = [], []
+        for predict_time in targets:                                           # :585
+            while ct < predict_time:                                           # :586
+                dt = (predict_time - ct) if self.variable else dt_             # :590-593
+                seg.ops.append((OP_STEP, len(seg.dts)))
+                seg.dts.append(dt)
+                seg.n_draws += self.per_step
+                ct = ct + dt
+                if predict_time - 0.5 * dt_ < ct < predict_time + 0.5 * dt_:
+                    bt.append(ct)                                              # :601-604
+                    bn.append(self.n_ops + len(seg.ops))
+        n_trunk = len(self.path_t)
+        pt = np.array(self.path_t + bt)
+        pn = self.path_n + bn
+        sel, source, rows = [], [], {}
+        for ts in targets:                                                     # :610-620
+            A = np.where(pt > ts - 0.5 * dt_)[0]
+            B = np.where(pt < ts + 0.5 * dt_)[0]
+            both = A[np.isin(A, B)]
+            if both.size:
+                idx = int(np.max(both))
+            else:
+                dist = np.abs(pt - ts)
+                idx = int(np.argmin(dist))
+                if self.evicted and not (ts > self.evicted_tmax and ts - self.evicted_tmax > float(dist[idx])):
+                    raise ValueError(f"target {ts}: no kept path entry within delta_t/2 and an evicted observation state (the last one "
+                                     f"at t={self.evicted_tmax}) may be the nearest: raise `history` (now {self.history})")
+            sel.append(pn[idx])
+            if idx < n_trunk:
+                source.append(("trunk", idx))
+            else:
+                local = pn[idx] - self.n_ops
+                if local not in rows:
+                    rows[local] = len(seg.sel_nops)
+                    seg.sel_nops.append(local)
+                source.append(("branch", rows[local]))
+        seg.path_t = bt
+        return Branch(seg, sel, source, self.n_ops, self.n_draws)

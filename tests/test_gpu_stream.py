@@ -1,0 +1,449 @@
+"""GPU: the resumable rollout (sf_nnfo_rollout_resume_*_fwd) and the streaming sessions built on it.
+
+Latent level: the one-shot rollout and the same ops run as resumed segments are BITWISE equal — the segments run the same kernels on
+the same sizes in the same order, the reductions are fixed-order, and the boundary carries what the next cell needs (state, imputed
+input, carried branch 2).  Model level: the only difference to ``forward`` is the launch shape of the encoder (one frame instead of
+all), so the limit is the one test_config2_batch32_equals_single_sample sets for that: 1e-4 max-abs."""
+import copy
+
+import numpy as np
+import pytest
+import torch
+
+from util import cases, hashfill, gold, maxabs, build_pair, oracle_rollout
+from streamingflow_amd import _lib, runtime, schedule as S
+from streamingflow_amd._lib import OP_JUMP
+from streamingflow_amd.runtime import ptr
+
+pytestmark = pytest.mark.gpu
+TOL_E2E = 1e-3          # test_fpode_golden's limit for forward against the fixtures
+TOL_SHAPE = 1e-4        # same arithmetic, different launch shape
+C64, LAT = 64, 50
+
+
+def _stream40(solver, impute):
+    cts, lts, tts, dt = cases.timeset("stream40")
+    net, sd = build_pair(C64, solver, impute, True, dt)
+    times, _ = S.merge_observations(cts[0].tolist(), lts[0].tolist())
+    targets = tts[0].tolist()
+    sc = S.build_schedule(times, targets, dt, True, solver)
+    return net, sd, times, targets, dt, sc
+
+
+def _segment(ode, sc, a, b, hx, eps, philox, coef, state, p, carry, draw_base, last, dev, outs=None):
+    """Ops [a, b) of `sc` as one resumed call on the carried (state, p, carry) — updated in place unless `last`, or written to
+    `outs` = (state, p, carry) buffers of the next segment when given.  Returns ({target index: state}, final state or None)."""
+    h, w, C = hx.shape[-3:]
+    L = _lib.lib()
+    ops = sc.ops_array()[2 * a:2 * b].copy()              # jumps / steps keep their indices into the whole hx / coef tensors
+    tg = [t for t, n in enumerate(sc.sel_nops) if a < n <= b]
+    sel = np.asarray([sc.sel_nops[t] - a for t in tg], dtype=np.int32)
+    out = torch.empty((max(1, len(tg)), h, w, C), dtype=torch.float32, device=dev)
+    final = torch.empty((h, w, C), dtype=torch.float32, device=dev) if last else (outs[0] if outs else state)
+    p_o, carry_o = (outs[1], outs[2]) if outs else (p, carry)
+    ws = runtime.workspace(L.sf_nnfo_rollout_ws_bytes(C, 1, h, w), dev)
+    head = (ode.gru_c.packed().struct, ode.gru_obs.gru_d.packed().struct, ode.p_model.packed().struct, _lib.SOLVER[ode.solver],
+            int(bool(ode.impute)), ops.ctypes.data_as(_lib.i32p), b - a, ptr(hx))
+    tail = (ptr(coef), 0, sel.ctypes.data_as(_lib.i32p) if len(tg) else None, len(tg), ptr(out) if len(tg) else None, ptr(final),
+            ptr(state), ptr(p), ptr(carry), draw_base, None if last else ptr(p_o), None if last else ptr(carry_o), 1, h, w,
+            ptr(ws), ws.numel() * 4, runtime.stream_ptr(dev))
+    if philox is not None:
+        _lib.check(L.sf_nnfo_rollout_resume_philox_fwd(*head, ptr(philox), *tail), "resume_philox")
+    else:
+        _lib.check(L.sf_nnfo_rollout_resume_fwd(*head, ptr(eps[draw_base:]), *tail), "resume")
+    return {t: out[i].clone() for i, t in enumerate(tg)}, (final if last else None)
+
+
+def _draws(sc, ode, a, b):
+    per = S.DRAWS_PER_STEP[ode.solver]
+    return sum(1 if k == OP_JUMP else per for k, _ in sc.ops[a:b])
+
+
+@pytest.mark.parametrize("split", ["observations", "observations+mid_targets"])
+@pytest.mark.parametrize("noise", ["eps", "philox"])
+@pytest.mark.parametrize("impute", [True, False])
+@pytest.mark.parametrize("solver", ["euler", "midpoint", "rk4"])
+def test_resumed_segments_equal_one_shot_bitwise(solver, impute, noise, split):
+    net, _, times, targets, dt, sc = _stream40(solver, impute)
+    ode, dev = net.gru_ode, torch.device("cuda")
+    ode.use_graph = False
+    hx = (hashfill.normal("shx", (len(times), LAT, LAT, C64), 41) * 0.5).cuda()
+    coef = torch.from_numpy(sc.coef_array()).cuda()
+    L = _lib.lib()
+    eps = philox = None
+    if noise == "eps":
+        eps = hashfill.normal("seps", (sc.n_draws, LAT, LAT, C64), 42).cuda()
+        want, want_final = ode.rollout_nhwc(hx, sc, eps)
+    else:
+        philox = torch.tensor([0x5EED5EED, 3], dtype=torch.int64, device=dev)
+        want = torch.empty((len(sc.sel_nops), LAT, LAT, C64), dtype=torch.float32, device=dev)
+        want_final = torch.empty((LAT, LAT, C64), dtype=torch.float32, device=dev)
+        ws = runtime.workspace(L.sf_nnfo_rollout_ws_bytes(C64, 1, LAT, LAT), dev)
+        sel = np.asarray(sc.sel_nops, dtype=np.int32)
+        ops = sc.ops_array()
+        _lib.check(L.sf_nnfo_rollout_philox_fwd(
+            ode.gru_c.packed().struct, ode.gru_obs.gru_d.packed().struct, ode.p_model.packed().struct, _lib.SOLVER[solver], int(impute),
+            ops.ctypes.data_as(_lib.i32p), len(sc.ops), ptr(hx), ptr(philox), ptr(coef), 0, sel.ctypes.data_as(_lib.i32p), len(sel),
+            ptr(want), ptr(want_final), 1, LAT, LAT, ptr(ws), ws.numel() * 4, runtime.stream_ptr(dev)), "one-shot philox")
+    cuts = [i + 1 for i, (k, _) in enumerate(sc.ops) if k == OP_JUMP]        # (a) after every observation
+    assert len(cuts) == len(times)
+    if split.endswith("mid_targets"):
+        cuts.append((cuts[-1] + len(sc.ops)) // 2)                           # (b) once in the middle of the target loop
+    if cuts[-1] != len(sc.ops):
+        cuts.append(len(sc.ops))
+    state = torch.zeros((LAT, LAT, C64), dtype=torch.float32, device=dev)
+    p = torch.zeros_like(state)
+    carry = torch.zeros(L.sf_nnfo_rollout_carry_bytes(C64, 1, LAT, LAT) // 4, dtype=torch.float32, device=dev)
+    got, a, base, final = {}, 0, 0, None
+    for b in cuts:
+        last = b == len(sc.ops)
+        before = (state.clone(), p.clone()) if last else None
+        sel, final = _segment(ode, sc, a, b, hx, eps, philox, coef, state, p, carry, base, last, dev)
+        if last:      # state_in / p_in are inputs only
+            assert torch.equal(state, before[0]) and torch.equal(p, before[1])
+        got.update(sel)
+        base += _draws(sc, ode, a, b)
+        a = b
+    assert base == sc.n_draws and sorted(got) == list(range(len(targets)))
+    assert torch.isfinite(want).all()
+    for t in range(len(targets)):
+        assert torch.equal(got[t], want[t]), (t, maxabs(got[t], want[t]))
+    assert torch.equal(final, want_final), maxabs(final, want_final)
+
+
+@pytest.mark.parametrize("solver", ["euler", "rk4"])
+def test_segments_out_of_place_leave_their_inputs_alone(solver):
+    """Every boundary handed on through separate buffers (no aliasing): state_in / p_in / carry_in are bitwise untouched by every
+    segment, and the result is the in-place one's, i.e. the one-shot rollout's."""
+    net, _, times, targets, dt, sc = _stream40(solver, True)
+    ode, dev = net.gru_ode, torch.device("cuda")
+    ode.use_graph = False
+    hx = (hashfill.normal("shx", (len(times), LAT, LAT, C64), 41) * 0.5).cuda()
+    eps = hashfill.normal("seps", (sc.n_draws, LAT, LAT, C64), 42).cuda()
+    coef = torch.from_numpy(sc.coef_array()).cuda()
+    want, want_final = ode.rollout_nhwc(hx, sc, eps)
+    cuts = [i + 1 for i, (k, _) in enumerate(sc.ops) if k == OP_JUMP]
+    cuts += [(cuts[-1] + len(sc.ops)) // 2, len(sc.ops)]
+    n_carry = _lib.lib().sf_nnfo_rollout_carry_bytes(C64, 1, LAT, LAT) // 4
+
+    def bufs():
+        return (torch.zeros((LAT, LAT, C64), dtype=torch.float32, device=dev), torch.zeros((LAT, LAT, C64), dtype=torch.float32, device=dev),
+                torch.zeros(n_carry, dtype=torch.float32, device=dev))
+    cur, got, a, base, final = bufs(), {}, 0, 0, None
+    for b in cuts:
+        last = b == len(sc.ops)
+        nxt = None if last else tuple(torch.full_like(t, float("nan")) for t in cur)
+        before = tuple(t.clone() for t in cur)
+        sel, final = _segment(ode, sc, a, b, hx, eps, None, coef, cur[0], cur[1], cur[2], base, last, dev, outs=nxt)
+        assert all(torch.equal(x, y) for x, y in zip(cur, before)), f"segment [{a}, {b}) wrote one of its inputs"
+        got.update(sel)
+        base += _draws(sc, ode, a, b)
+        a = b
+        if not last:
+            assert torch.isfinite(nxt[0]).all() and torch.isfinite(nxt[1]).all()
+            cur = nxt
+    for t in range(len(targets)):
+        assert torch.equal(got[t], want[t]), (t, maxabs(got[t], want[t]))
+    assert torch.equal(final, want_final)
+
+
+def test_segment_argument_rules():
+    """A segment without jumps takes hx_obs = NULL, one with a jump refuses it; an empty segment copies the boundary and refuses
+    carry_out; carry_in needs the state and the input it belongs to."""
+    net, _, times, targets, dt, sc = _stream40("euler", True)
+    ode, dev, L = net.gru_ode, torch.device("cuda"), _lib.lib()
+    st = torch.randn((LAT, LAT, C64), device=dev)
+    p = torch.randn((LAT, LAT, C64), device=dev)
+    carry = torch.zeros(L.sf_nnfo_rollout_carry_bytes(C64, 1, LAT, LAT) // 4, device=dev)
+    eps = torch.randn((2, LAT, LAT, C64), device=dev)
+    coef = torch.from_numpy(S.Schedule(dts=[0.05]).coef_array()).cuda()
+    ws = runtime.workspace(L.sf_nnfo_rollout_ws_bytes(C64, 1, LAT, LAT), dev)
+    so, po = torch.empty_like(st), torch.empty_like(p)
+
+    def call(ops, hx, state_in, p_in, carry_in, p_out, carry_out):
+        arr = np.asarray(ops, dtype=np.int32).reshape(-1)
+        return L.sf_nnfo_rollout_resume_fwd(
+            ode.gru_c.packed().struct, ode.gru_obs.gru_d.packed().struct, ode.p_model.packed().struct, 0, 1,
+            arr.ctypes.data_as(_lib.i32p) if len(ops) else None, len(ops), ptr(hx), ptr(eps), ptr(coef), 0, None, 0, None, ptr(so),
+            ptr(state_in), ptr(p_in), ptr(carry_in), 0, ptr(p_out), ptr(carry_out), 1, LAT, LAT, ptr(ws), ws.numel() * 4,
+            runtime.stream_ptr(dev))
+    assert call([(1, 0)], None, st, p, None, po, None) == 0                      # a step alone: no observation needed
+    assert torch.isfinite(so).all() and torch.isfinite(po).all()
+    assert call([(0, 0)], None, st, p, None, po, None) == -1                     # a jump without observations
+    assert call([], None, st, p, None, po, None) == 0                            # empty: the boundary is copied
+    assert torch.equal(so, st) and torch.equal(po, p)
+    assert call([], None, st, p, None, po, carry) == -1                          # ... and has no carry to write
+    assert call([(1, 0)], None, None, None, carry, po, None) == -1               # a carry without its boundary
+    assert call([(1, 0)], None, st, p, None, None, carry) == -1                  # carry_out without p_out
+
+
+def _feed(sess, times, hx, upto=None):
+    for i, t in enumerate(times[:upto]):
+        sess.observe(t, hx[i])
+
+
+@pytest.mark.parametrize("solver", ["euler", "midpoint"])
+def test_session_equals_one_shot_bitwise_graph_and_eager(solver):
+    """A session fed observation by observation == the one-shot rollout over the same observations, bitwise, replayed from its
+    graphs and eagerly; predict twice gives equal tensors; observe after predict == observe without it; the path history answers
+    past targets."""
+    net, _, times, targets, dt, sc = _stream40(solver, True)
+    ode = net.gru_ode
+    hx = (hashfill.normal("shx", (len(times), LAT, LAT, C64), 41) * 0.5).cuda()
+    tg = [times[0], times[-1]] + targets           # two past targets: answered by kept observation states
+    sc2 = S.build_schedule(times, tg, dt, True, solver)
+    ode.noise, ode.use_graph = hashfill.HashedNoise(5), False
+    want, want_final = ode.rollout_nhwc(hx, sc2)
+    res = {}
+    for mode in (False, None, True):               # eager, auto (graphs: 2500 pixels), forced graphs
+        plain = ode.stream(dt, noise=hashfill.HashedNoise(5), use_graph=mode)
+        poked = ode.stream(dt, noise=hashfill.HashedNoise(5), use_graph=mode)
+        for i, t in enumerate(times):
+            plain.observe(t, hx[i])
+            poked.observe(t, hx[i])
+            if i in (2, 5):
+                poked.predict(targets[:7])         # a branch between two observes leaves the trunk alone
+                poked.predict(targets[:3])
+            assert torch.equal(plain.state, poked.state)
+        a = poked.predict(tg).clone()
+        b = poked.predict(tg).clone()
+        c = plain.predict(tg).clone()
+        assert torch.equal(a, b) and torch.equal(a, c)
+        assert torch.equal(plain.state, poked.state) and torch.equal(plain.state, want[1])
+        if mode is not False:
+            assert len(plain._graphs) > 0 and len(plain._graphs) <= plain.GRAPH_CACHE_MAX
+        else:
+            assert len(plain._graphs) == 0
+        assert len(ode._graphs) == 0               # the module's one-shot graph cache is not touched
+        res[mode] = a
+        plain.drop_graphs()
+        poked.drop_graphs()
+    for mode, a in res.items():
+        assert torch.equal(a, want), (mode, maxabs(a, want))
+    # after reset() the same stream again gives the same answer (a new epoch of the injected source)
+    s = ode.stream(dt, noise=hashfill.HashedNoise(5))
+    _feed(s, times, hx, 3)
+    s.reset()
+    s.noise = hashfill.HashedNoise(5)
+    _feed(s, times, hx)
+    assert torch.equal(s.predict(tg), want)
+    s.drop_graphs()
+
+
+def test_two_interleaved_sessions_equal_two_sequential_ones():
+    net, _, times, targets, dt, sc = _stream40("euler", True)
+    ode = net.gru_ode
+    hx_a = (hashfill.normal("shxa", (len(times), LAT, LAT, C64), 43) * 0.5).cuda()
+    hx_b = (hashfill.normal("shxb", (len(times), LAT, LAT, C64), 44) * 0.5).cuda()
+    seq = []
+    for hx, seed in ((hx_a, 7), (hx_b, 8)):
+        s = ode.stream(dt, noise=hashfill.HashedNoise(seed))
+        _feed(s, times, hx)
+        seq.append(s.predict(targets).clone())
+        s.drop_graphs()
+    sa, sb = ode.stream(dt, noise=hashfill.HashedNoise(7)), ode.stream(dt, noise=hashfill.HashedNoise(8))
+    got_a = got_b = None
+    for i, t in enumerate(times):
+        sa.observe(t, hx_a[i])
+        sb.observe(t, hx_b[i])
+        if i == 4:
+            sa.predict(targets[:5])
+            sb.predict(targets[:9])
+    got_a, got_b = sa.predict(targets).clone(), sb.predict(targets).clone()
+    assert torch.equal(got_a, seq[0]) and torch.equal(got_b, seq[1])
+    assert not torch.equal(got_a, got_b)
+    sa.drop_graphs()
+    sb.drop_graphs()
+
+
+def test_in_kernel_noise_session_matches_one_shot_numbering():
+    """Philox: one `call` number per epoch and the trunk counter as draw_base — the draws the one-shot call gives the same ops —
+    so the session equals the one-shot rollout under the same {seed, call} record bitwise; two predicts draw the same noise,
+    fresh_noise=True draws another."""
+    net, _, times, targets, dt, sc = _stream40("euler", True)
+    ode = net.gru_ode
+    hx = (hashfill.normal("shx", (len(times), LAT, LAT, C64), 41) * 0.5).cuda()
+    ode.noise, ode.use_graph = None, False
+    ode.seed_noise(1234)
+    want, _ = ode.rollout_nhwc(hx, sc)             # call number 1
+    ode.seed_noise(1234)
+    s = ode.stream(dt)                             # the epoch takes call number 1 here ...
+    assert s._in_kernel()
+    ode.rollout_nhwc(hx, sc)                       # ... so a one-shot call before the first observe (number 2) does not shift it
+    _feed(s, times, hx)
+    a, b = s.predict(targets), s.predict(targets)
+    assert torch.equal(a, b) and torch.equal(a, want), maxabs(a, want)
+    c = s.predict(targets, fresh_noise=True)
+    assert torch.isfinite(c).all() and not torch.equal(c, a)
+    assert torch.equal(s.predict(targets), a)
+    s.reset()                                      # a new epoch: another call number, other noise
+    _feed(s, times, hx)
+    d = s.predict(targets)
+    assert torch.isfinite(d).all() and not torch.equal(d, a)
+
+
+def test_failed_observe_does_not_advance_the_trunk():
+    """An observe whose segment could not be enqueued (here: the noise source raises) leaves the host schedule where it was and
+    the session refuses to answer from possibly half-written buffers until reset()."""
+    net, _, times, targets, dt, sc = _stream40("euler", True)
+    ode = net.gru_ode
+    hx = (hashfill.normal("shx", (len(times), LAT, LAT, C64), 41) * 0.5).cuda()
+    src = hashfill.HashedNoise(5)
+
+    def dry(shape, dtype, device):
+        if src.k >= 2:
+            raise IndexError("noise source ran dry")
+        return src(shape, dtype, device)
+    s = ode.stream(dt, noise=dry)
+    s.observe(times[0], hx[0])
+    n_obs, n_draws, now = s.n_observations, s.n_draws, s.current_time
+    with pytest.raises(IndexError):
+        s.observe(times[1], hx[1])                 # a step and a jump: needs draws 1 and 2
+    assert (s.n_observations, s.n_draws, s.current_time) == (n_obs, n_draws, now)
+    with pytest.raises(RuntimeError, match="reset"):
+        s.predict(targets[:3])
+    with pytest.raises(RuntimeError, match="reset"):
+        s.observe(times[1], hx[1])
+    s.reset()
+    s.noise = hashfill.HashedNoise(5)
+    _feed(s, times, hx)
+    ode.noise, ode.use_graph = hashfill.HashedNoise(5), False
+    want, _ = ode.rollout_nhwc(hx, sc)
+    assert torch.equal(s.predict(targets), want)
+    s.drop_graphs()
+
+
+def test_session_vs_oracle_stream40():
+    """The 46-step streaming case against the oracle's latent-level composition: <= 1e-3, the limit
+    test_c64_stream40_rollout_vs_oracle sets for the one-shot rollout."""
+    net, sd, times, targets, dt, sc = _stream40("euler", True)
+    ode = net.gru_ode
+    hx = hashfill.normal("orhx", (len(times), LAT, LAT, C64), 71) * 0.5
+    eps = hashfill.normal("oreps", (sc.n_draws, LAT, LAT, C64), 72)
+    ref, ref_final = oracle_rollout(sd, sc, hx, eps, "euler")
+    rows = iter(eps)
+    s = ode.stream(dt, noise=lambda shape, dtype, device: next(rows).permute(2, 0, 1)[None].contiguous())
+    _feed(s, times, hx.cuda())
+    got = s.predict(targets)
+    err = maxabs(got, ref)
+    print(f"session vs oracle (stream40, C=64, 50x50): max-abs {err:.3e}")
+    assert err <= 1e-3, err
+    s.drop_graphs()
+
+
+# ---- model level ------------------------------------------------------------------------------------------------------------
+def _feed_frames(sess, cam, lid, cts, lts):
+    cam_ts = cts[0].tolist() if cam is not None and cam.shape[1] else []
+    lid_ts = lts[0].tolist() if lid is not None and lid.shape[1] else []
+    times, order = S.merge_observations(cam_ts, lid_ts)
+    for t, (src, i) in zip(times, order):          # camera before LiDAR on equal times: merge_observations' tie rule
+        sess.observe(t, (cam if src == 0 else lid)[0, i].cuda(), "camera" if src == 0 else "lidar")
+
+
+@pytest.mark.parametrize("name", list(cases.FPODE_CASES))
+def test_model_session_equals_forward_and_fixture(name):
+    C, H, W, ts, solver, impute, variable, eps0 = cases.FPODE_CASES[name]
+    cts, lts, tts, dt = cases.timeset(ts)
+    net, _ = build_pair(C, solver, impute, variable, dt)
+    cam, lid = cases.bev_inputs(C, H, W, cts.shape[1], lts.shape[1])
+    net.gru_ode.noise = hashfill.HashedNoise(cases.EPS_SEED, zero=eps0)
+    y, _ = net(cases.present_input(cam, lid).cuda(), cam.cuda(), lid.cuda(), cts, lts, tts)
+    s = net.stream(noise=hashfill.HashedNoise(cases.EPS_SEED, zero=eps0))
+    _feed_frames(s, cam, lid, cts, lts)
+    got = s.predict(tts)
+    assert got.shape == y.shape
+    d_fwd, d_fix = maxabs(got, y), maxabs(got, gold("fpode.npz")[name + "/out"])
+    print(f"{name}: session vs forward {d_fwd:.3e}, vs fixture {d_fix:.3e}")
+    assert d_fwd <= TOL_SHAPE, d_fwd
+    assert d_fix <= TOL_E2E, d_fix
+    s.latent.drop_graphs()
+
+
+def test_model_session_full_size_equals_forward():
+    C, H, W = 64, 200, 200
+    cts, lts, tts, dt = cases.timeset("shipped")
+    net, _ = build_pair(C, "euler", True, True, dt)
+    cam, lid = cases.bev_inputs(C, H, W, 3, 5)
+    net.gru_ode.noise = hashfill.HashedNoise(cases.EPS_SEED)
+    y, _ = net(cases.present_input(cam, lid).cuda(), cam.cuda(), lid.cuda(), cts, lts, tts)
+    s = net.stream(noise=hashfill.HashedNoise(cases.EPS_SEED))
+    _feed_frames(s, cam, lid, cts, lts)
+    got = s.predict(tts)
+    d = maxabs(got, y)
+    print(f"C=64 200x200 shipped: session vs forward {d:.3e}")
+    assert got.shape == y.shape == (1, tts.shape[1], C, H, W)
+    assert d <= TOL_SHAPE, d
+    # history: a past target whose entry is kept equals forward, one whose entry was evicted raises
+    short = net.stream(history=3, noise=hashfill.HashedNoise(cases.EPS_SEED))
+    _feed_frames(short, cam, lid, cts, lts)
+    kept = torch.tensor([[0.0, 0.5, 1.0]], dtype=torch.float64)
+    net.gru_ode.noise = hashfill.HashedNoise(cases.EPS_SEED)
+    yk, _ = net(cases.present_input(cam, lid).cuda(), cam.cuda(), lid.cuda(), cts, lts, kept)
+    assert maxabs(short.predict(kept), yk) <= TOL_SHAPE
+    with pytest.raises(ValueError, match="history"):
+        short.predict(torch.tensor([[-1.0, 0.5]], dtype=torch.float64))
+    s.latent.drop_graphs()
+    short.latent.drop_graphs()
+
+
+def test_model_session_bev_size_not_divisible_by_four():
+    C, H, W = 8, 50, 38
+    cts, lts, tts, dt = cases.timeset("camera_only")
+    net, _ = build_pair(C, "euler", True, True, dt)
+    cam, _ = cases.bev_inputs(C, H, W, cts.shape[1], 0)
+    net.gru_ode.noise = hashfill.HashedNoise(cases.EPS_SEED)
+    y, _ = net(cam[:, -1:].cuda(), cam.cuda(), None, cts, None, tts)
+    s = net.stream(noise=hashfill.HashedNoise(cases.EPS_SEED))
+    _feed_frames(s, cam, None, cts, None)
+    got = s.predict(tts)
+    assert got.shape == y.shape == (1, 3, C, 48, 36)
+    assert maxabs(got, y) <= TOL_SHAPE
+
+
+def test_refusals_repack_and_copies():
+    C, H, W = 8, 16, 16
+    cts, lts, tts, dt = cases.timeset("shipped")
+    net, sd = build_pair(C, "euler", True, True, dt)
+    cam, lid = cases.bev_inputs(C, H, W, 3, 5)
+    s = net.stream(noise=hashfill.HashedNoise(1))
+    with pytest.raises(RuntimeError):
+        s.predict(tts)                                             # before any observation
+    with pytest.raises(RuntimeError):
+        s.observe(-1.0, cam[0, 0])                                 # CPU tensor
+    g = cam[0, 0].cuda().requires_grad_(True)
+    with pytest.raises(RuntimeError):
+        s.observe(-1.0, g)                                         # grad-enabled input
+    with pytest.raises(ValueError):
+        s.observe(-1.0, cam[0, 0].cuda(), source="radar")
+    s.observe(-1.0, cam[0, 0].cuda())
+    s.observe(-0.8, lid[0, 0].cuda(), "lidar")
+    with pytest.raises(ValueError):
+        s.observe(-0.9, cam[0, 1].cuda())                          # earlier than the previous observation
+    before = s.latent.state
+    y0 = s.predict(tts).clone()
+    assert torch.equal(before, s.latent.state)
+    # a deep copy of the module carries no session and no device buffers of one; the session itself refuses to be copied
+    twin = copy.deepcopy(net)
+    assert not any(isinstance(v, type(s)) or isinstance(v, type(s.latent)) for m in twin.modules() for v in vars(m).values())
+    with pytest.raises(TypeError):
+        copy.deepcopy(s)
+    # .train() is refused
+    net.train()
+    with pytest.raises(RuntimeError):
+        s.observe(-0.6, lid[0, 1].cuda(), "lidar")
+    with pytest.raises(RuntimeError):
+        s.predict(tts)
+    net.eval()
+    assert torch.equal(s.predict(tts), y0)
+    # a re-pack between observes: the session raises until reset(), then streams again
+    net.load_state_dict({k: v.clone() for k, v in net.state_dict().items()})
+    with pytest.raises(RuntimeError, match="re-packed"):
+        s.observe(-0.6, lid[0, 1].cuda(), "lidar")
+    with pytest.raises(RuntimeError, match="re-packed"):
+        s.predict(tts)
+    s.reset()
+    s.latent.noise = hashfill.HashedNoise(1)
+    s.observe(-1.0, cam[0, 0].cuda())
+    s.observe(-0.8, lid[0, 0].cuda(), "lidar")
+    assert torch.equal(s.predict(tts), y0)
+    s.latent.drop_graphs()
