@@ -30,6 +30,7 @@ hipError_t set_stamp_buffer_wino(unsigned long long*) { return hipErrorNotSuppor
 #endif
 
 constexpr int WN_THREADS = 512;
+constexpr long SF_WINO_SPLIT_WGS_DEFAULT = 512;      // launch_conv_wino: remainder launches from this many workgroups
 typedef __attribute__((address_space(3))) void wn_lds_void;
 
 __device__ __forceinline__ f32x4 wn_lds_read128(const float* p) {
@@ -232,9 +233,11 @@ __global__ __launch_bounds__(WN_THREADS, TH_ == 2 ? 6 : 4) void conv_wino5_kerne
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int H = P.Hout, W = P.Wout;
   const WnAxis ax(DIL ? W : 2, DIL ? P.dil : 1), ay(DIL ? H : 2, DIL ? P.dil : 1);
-  const int tiles_x = DIL ? ax.nt : (W + 1) >> 1, tiles_y = DIL ? ay.nt : (H + 1) >> 1;
+  const int tiles_x = DIL ? ax.nt : (W + 1) >> 1;
   const int tpi = tiles_x;
-  const int nbx = ((CAT ? P.n_img * tiles_x : tiles_x) + TW - 1) / TW, nby = (tiles_y + TH - 1) / TH;
+  // the blocks tile the launch's window of tile rows (L.wn_ty0, L.wn_nty: the whole image, or a part of a split layer); every range
+  // check below is against the image itself
+  const int nbx = ((CAT ? P.n_img * tiles_x : tiles_x) + TW - 1) / TW, nby = (L.wn_nty + TH - 1) / TH;
   // 1-D grid, XCD-aware (as conv_wino_kernel): every XCD owns a contiguous range of tile blocks, the cout blocks of a tile block are
   // consecutive workgroups of that XCD
   const int ncb = P.cout_pad / COUT_T;
@@ -264,7 +267,7 @@ __global__ __launch_bounds__(WN_THREADS, TH_ == 2 ? 6 : 4) void conv_wino5_kerne
 #endif
   const int ct0 = CAT ? bx * TW - img * tpi : 0;
   const int cn0 = CAT ? (tpi - ct0 < TW ? tpi - ct0 : TW) : TW;
-  const int ty0 = by * TH, tx0 = CAT ? ct0 : bx * TW;
+  const int ty0 = L.wn_ty0 + by * TH, tx0 = CAT ? ct0 : bx * TW;
   int px0 = 0, pt0 = 0, py0 = 0, qt0 = 0;
   if constexpr (DIL) { ax.decode(tx0, px0, pt0); ay.decode(ty0, py0, qt0); }
   SF_STAMP_AT(L, 0);
@@ -962,7 +965,14 @@ static bool wino_cat(const ConvProblem& q) {
   static const int cat_scaled = [] { const char* v = std::getenv("SF_WINO_CAT_SCALED"); return v ? std::atoi(v) : 1; }();      // round 6: SE scales of both images of a block
   if (!on || q.dil != 1 || q.in_up || q.n_img < 2 || tpi < 8 || q.bias_per_img || ((q.in_scale || q.add_scale) && !cat_scaled)) return false;
   const int plain = (tpi + 7) / 8 * 8;
-  if (plain * 100 < tpi * 110) return false;      // less than 10 % empty columns: keep the plain form
+  // less than 10 % empty columns: the plain form, whose patch is two columns narrower — except at 128 or more output channels and at
+  // least 4 % empty columns (100 tile columns run 104: the 200x200 gates and 128 -> 128 layers), where CAT measured 1.7 - 2.8 % faster and
+  // the 64-channel layers within +-1 % (SF_WINO_CAT_WIDE=0: the 10 % rule alone.  Read at every such launch: tests compare both)
+  if (plain * 100 < tpi * 110) {
+    if (q.cout_pad < 128 || plain * 100 < tpi * 104) return false;
+    const char* const v = std::getenv("SF_WINO_CAT_WIDE");
+    if (v && std::atoi(v) == 0) return false;
+  }
   const double img_bytes = 4.0 * q.Hin * q.Win;
   const int cs = q.in0_cs > q.in1_cs ? q.in0_cs : q.in1_cs;
   const int co = q.out_cs > q.add_cs ? q.out_cs : q.add_cs;
@@ -982,15 +992,17 @@ double wino_tiles(const ConvProblem& q) {
   if (q.dil > 1) return (double)q.n_img * WnAxis(q.Hout, q.dil).nt * WnAxis(q.Wout, q.dil).nt;
   return (double)q.n_img * ((q.Hout + 1) / 2) * ((q.Wout + 1) / 2);
 }
-// workgroups a launch of the group would have with 32-tile blocks (the choice between the two block sizes)
-static long wino5_wgs32(const ConvLaunch& L, bool cat) {
+// workgroups a launch of the group has over `rows` tile rows of every image with blocks of `th` tile rows (the choice between the two block
+// sizes and the split rule count the window a launch covers, not the layer)
+static long wino5_wgs(const ConvLaunch& L, bool cat, int rows, int th) {
   const ConvProblem& P = L.p[0];
-  const int tiles_x = (P.Wout + 1) / 2, tiles_y = (P.Hout + 1) / 2;
-  const long blocks = cat ? (long)((tiles_y + 3) / 4) * (((long)P.n_img * tiles_x + 7) / 8) : (long)P.n_img * ((tiles_y + 3) / 4) * ((tiles_x + 7) / 8);
+  const int tiles_x = (P.Wout + 1) / 2;
+  const long nby = (rows + th - 1) / th;
+  const long blocks = cat ? nby * (((long)P.n_img * tiles_x + 7) / 8) : (long)P.n_img * nby * ((tiles_x + 7) / 8);
   return ((blocks + 7) / 8) * 8 * (P.cout_pad / 64) * L.nprob;
 }
 template <int EPI, bool DIL = false, bool CAT = false, int TH_ = 4, int GRP = 1>
-static hipError_t launch_wino5_t(const ConvLaunch& L, hipStream_t stream) {
+static hipError_t launch_wino5_t(const ConvLaunch& L, hipStream_t stream, const int row0 = 0, const int rows = -1) {
   typedef Wino5Geo<DIL, CAT, TH_> G;
   auto kern = conv_wino5_kernel<EPI, DIL, CAT, TH_, GRP>;
   constexpr int lds = G::LDS_FLOATS * 4;
@@ -1003,7 +1015,10 @@ static hipError_t launch_wino5_t(const ConvLaunch& L, hipStream_t stream) {
     attr_done[dev] = true;
   }
   const ConvProblem& P = L.p[0];
-  const int tiles_x = DIL ? WnAxis(P.Wout, P.dil).nt : (P.Wout + 1) / 2, tiles_y = DIL ? WnAxis(P.Hout, P.dil).nt : (P.Hout + 1) / 2;
+  const int tiles_x = DIL ? WnAxis(P.Wout, P.dil).nt : (P.Wout + 1) / 2, tiles_all = DIL ? WnAxis(P.Hout, P.dil).nt : (P.Hout + 1) / 2;
+  // the window of tile rows [row0, row0 + rows) (rows < 0: the whole image); a window that does not end with the image is whole blocks
+  const int tiles_y = rows < 0 ? tiles_all : rows;
+  if (row0 < 0 || tiles_y < 1 || row0 + tiles_y > tiles_all || (DIL && tiles_y != tiles_all) || (row0 + tiles_y < tiles_all && tiles_y % G::TH)) return hipErrorInvalidValue;
   const long blocks = CAT ? (long)((tiles_y + G::TH - 1) / G::TH) * (((long)P.n_img * tiles_x + G::TW - 1) / G::TW)
                           : (long)P.n_img * ((tiles_y + G::TH - 1) / G::TH) * ((tiles_x + G::TW - 1) / G::TW);
   const long grid1 = ((blocks + 7) / 8) * 8 * (P.cout_pad / G::COUT_T), grid = grid1 * L.nprob;
@@ -1011,6 +1026,7 @@ static hipError_t launch_wino5_t(const ConvLaunch& L, hipStream_t stream) {
   ConvLaunch L2 = L;
   L2.wg_base[0] = 0;
   L2.wg_base[1] = (int)grid1;
+  L2.wn_ty0 = row0; L2.wn_nty = tiles_y;
   // reciprocals of the block decode's divisors (conv_wino5_kernel): ceil(2^32 / d), 0 for d = 1; exact while dividend x d < 2^32
   const long nbx = ((CAT ? (long)P.n_img * tiles_x : tiles_x) + G::TW - 1) / G::TW, nby = (tiles_y + G::TH - 1) / G::TH, ncb = P.cout_pad / G::COUT_T;
   auto magic = [](long d) { return d <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned long long)d - 1) / (unsigned long long)d); };
@@ -1057,16 +1073,34 @@ hipError_t launch_conv_wino(const ConvLaunch& L, int epi, hipStream_t stream) {
   // 2.841, forward 7.44 -> 7.27 ms; at two samples per forward 13.18 -> 13.14; above ~1 400 workgroups the 32-tile form wins (every workgroup
   // loads the whole U of its 64 output channels whatever its tile count: 16 tiles double the load instructions per MFMA)
   static const long small_wgs = [] { const char* v = std::getenv("SF_WINO_SMALL_WGS"); return v ? std::atol(v) : 1000L; }();
-  const bool small = (var == 2 || var == 4) && wino5_wgs32(L, var == 4) < small_wgs && !(var == 4 && L.p[0].in_scale);      // (SE-scaled CAT: 32-tile form only)
-  switch (var) {
-    case 2:
-      if (small) return affine ? launch_wino5_t<EPI_AFFINE, false, false, 2>(L, stream) : launch_wino5_t<EPI_BLEND, false, false, 2>(L, stream);
-      return affine ? launch_wino5_t<EPI_AFFINE>(L, stream) : launch_wino5_t<EPI_BLEND>(L, stream);
-    case 3: return affine ? launch_wino5_t<EPI_AFFINE, true>(L, stream) : hipErrorInvalidValue;
-    case 4:
-      if (small) return affine ? launch_wino5_t<EPI_AFFINE, false, true, 2>(L, stream) : launch_wino5_t<EPI_BLEND, false, true, 2>(L, stream);
-      return affine ? launch_wino5_t<EPI_AFFINE, false, true>(L, stream) : launch_wino5_t<EPI_BLEND, false, true>(L, stream);
+  if (var == 3) return affine ? launch_wino5_t<EPI_AFFINE, true>(L, stream) : hipErrorInvalidValue;
+  if (var != 2 && var != 4) return hipErrorInvalidValue;
+  const bool cat = var == 4;
+  const bool only32 = cat && L.p[0].in_scale;      // (SE-scaled CAT: 32-tile form only)
+  auto launch = [&](const bool small, const int row0, const int rows) -> hipError_t {
+    if (cat) {
+      if (small) return affine ? launch_wino5_t<EPI_AFFINE, false, true, 2>(L, stream, row0, rows) : launch_wino5_t<EPI_BLEND, false, true, 2>(L, stream, row0, rows);
+      return affine ? launch_wino5_t<EPI_AFFINE, false, true>(L, stream, row0, rows) : launch_wino5_t<EPI_BLEND, false, true>(L, stream, row0, rows);
+    }
+    if (small) return affine ? launch_wino5_t<EPI_AFFINE, false, false, 2>(L, stream, row0, rows) : launch_wino5_t<EPI_BLEND, false, false, 2>(L, stream, row0, rows);
+    return affine ? launch_wino5_t<EPI_AFFINE>(L, stream, row0, rows) : launch_wino5_t<EPI_BLEND>(L, stream, row0, rows);
+  };
+  const int tiles_y = (L.p[0].Hout + 1) / 2;
+  const bool small = !only32 && wino5_wgs(L, cat, tiles_y, 4) < small_wgs;
+  // Vertical remainder band: 25 / 50 tile rows end in a band of four with one / two real rows.  Such a layer runs as two launches: rows
+  // [0, 4 floor(tiles_y / 4)) on 32-tile blocks, the rest on 16-tile blocks (28 -> 26 / 52 -> 50 tile rows executed) — where the remainder
+  // launch has at least SF_WINO_SPLIT_WGS workgroups (default 512; 0: never, the layer stays whole).  Measured: the encoder / decoder
+  // layers of 224 - 256 images (704 - 3 200 remainder workgroups) gain 3 - 6 %, the rollout's 32-image layers (208) nothing: every workgroup loads
+  // the whole U and the launch has one more tail.  The sampling layer, the tap groups and SE-scaled concatenated images
+  // have no 16-tile form and stay whole.  (Read at every launch: tests compare both forms in one process.)
+  const char* const sv = std::getenv("SF_WINO_SPLIT_WGS");
+  const long split_wgs = sv ? std::atol(sv) : SF_WINO_SPLIT_WGS_DEFAULT;
+  const int main_rows = tiles_y & ~3, rem_rows = tiles_y - main_rows;
+  if (!small && !only32 && split_wgs > 0 && rem_rows > 0 && main_rows > 0 && wino5_wgs(L, cat, rem_rows, 2) >= split_wgs) {
+    const hipError_t e = launch(wino5_wgs(L, cat, main_rows, 4) < small_wgs, 0, main_rows);
+    return e != hipSuccess ? e : launch(true, main_rows, rem_rows);
   }
+  return launch(small, 0, -1);
   return hipErrorInvalidValue;
 }
 
