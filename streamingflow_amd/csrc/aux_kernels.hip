@@ -1,7 +1,7 @@
 // Small HBM/LDS-bound helper kernels around the implicit-GEMM conv: layout transposes at the
 // NCHW API boundary, 2x2 max-pool, nearest x2 upsample, SE gate, depthwise 7x7 + LayerNorm
 // (ConvNeXt block head), ASPP global-pool branch.  gfx950 only, NHWC fp32 internally.
-#include "sf_device.h"
+#include "sf_launch.h"
 
 namespace sf {
 

@@ -18,6 +18,7 @@
 //   i.e. four consecutive channels of one pixel => NHWC float4 stores, and per-pixel channel
 //   reductions (LayerNorm, 1x1->2 logits) are in-register sums + two xor-shuffles (16, 32).
 #include "sf_math.h"
+#include "sf_launch.h"
 
 #include <type_traits>
 #include <cstdlib>
@@ -1178,7 +1179,7 @@ __global__ __launch_bounds__(64 * WM * WN, (B3 && !SF_B3_DEEP && WM * WN >= 8 ? 
 
 template <int MT, int NT, int WM, int WN, int EPI, bool SCALE, bool B3>
 static hipError_t launch_glds_tb(const ConvLaunch& L, hipStream_t stream);
-// bf16x3 (opt-in math mode): every problem of the launch carries split weights (api.hip decides); block-uniform host switch
+// bf16x3 (opt-in math mode): every problem of the launch carries split weights (dispatch.hip decides); block-uniform host switch
 template <int MT, int NT, int WM, int WN, int EPI, bool SCALE = false>
 static hipError_t launch_glds_t(const ConvLaunch& L, hipStream_t stream) {
   bool b3 = L.nprob > 0;

@@ -27,6 +27,7 @@
 // What bounds it: the fp32 MFMA shares the vector ALU — every DMA instruction costs ~60 cycles of matrix
 // time, every VALU instruction 4-8; the shipped loop runs at ~70 % of the MFMA rate on 64x64 tiles.
 #include "sf_math.h"
+#include "sf_launch.h"
 
 #include <cstring>
 #include <type_traits>
@@ -1741,7 +1742,7 @@ constexpr int sp_launch_lds(bool fused) {
 template <int EPI, bool SCALE, int NT, bool B3>
 static hipError_t launch_sp_tb(const ConvLaunch& L, hipStream_t stream);
 template <int EPI, bool SCALE, int NT>
-static hipError_t launch_sp_t(const ConvLaunch& L, hipStream_t stream) {      // bf16x3: every problem carries split weights (api.hip decides)
+static hipError_t launch_sp_t(const ConvLaunch& L, hipStream_t stream) {      // bf16x3: every problem carries split weights (dispatch.hip decides)
   bool b3 = L.nprob > 0;
   for (int i = 0; i < L.nprob; ++i) b3 = b3 && L.p[i].w3 != nullptr && L.p[i].use_w3;
   return b3 ? launch_sp_tb<EPI, SCALE, NT, true>(L, stream) : launch_sp_tb<EPI, SCALE, NT, false>(L, stream);

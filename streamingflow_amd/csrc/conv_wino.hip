@@ -16,6 +16,7 @@
 // LDS rows are 16 floats (64 B); the 16-byte slot s of row r lives at slot s ^ ((r >> 2) & 2): conflict-free for the ds_read_b128
 // lane groups of a 16-row fragment (MI355X_MICROARCH.md, LDS table).
 #include "sf_math.h"
+#include "sf_launch.h"
 
 #include <cstdlib>
 #include <type_traits>
@@ -1029,7 +1030,6 @@ static hipError_t launch_wino5_t(const ConvLaunch& L, hipStream_t stream, const 
   L2.wn_ty0 = row0; L2.wn_nty = tiles_y;
   // reciprocals of the block decode's divisors (conv_wino5_kernel): ceil(2^32 / d), 0 for d = 1; exact while dividend x d < 2^32
   const long nbx = ((CAT ? (long)P.n_img * tiles_x : tiles_x) + G::TW - 1) / G::TW, nby = (tiles_y + G::TH - 1) / G::TH, ncb = P.cout_pad / G::COUT_T;
-  auto magic = [](long d) { return d <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned long long)d - 1) / (unsigned long long)d); };
   if ((grid1 / 8 + 1) * ncb >= 0x100000000L || (blocks + 8) * nbx >= 0x100000000L || (blocks + 8) * nby >= 0x100000000L ||
       (nbx * G::TW + G::TW) * tiles_x >= 0x100000000L)
     return hipErrorInvalidValue;
@@ -1101,7 +1101,6 @@ hipError_t launch_conv_wino(const ConvLaunch& L, int epi, hipStream_t stream) {
     return e != hipSuccess ? e : launch(true, main_rows, rem_rows);
   }
   return launch(small, 0, -1);
-  return hipErrorInvalidValue;
 }
 
 }  // namespace sf

@@ -18,7 +18,7 @@
 // gfx950 only.
 #include <hip/hip_runtime.h>
 
-#include "sf_device.h"
+#include "sf_launch.h"
 #include "sf_math.h"
 
 namespace sf {

@@ -1,0 +1,149 @@
+// Conv dispatch, "which kernel, how tiled" (dispatch.hip): what the modules and entry points of api.hip need from it.  Host only.
+// The mutable state behind it (profiler, split-K scratch, persistent flow, stamp slots) is private to dispatch.hip; the entry points reach
+// it through the scopes and functions below.
+#pragma once
+#include "sf_launch.h"
+#include "../../include/sfnative.h"
+
+#include <algorithm>
+#include <functional>
+
+#define SF_TRY(expr) do { int _st = (expr); if (_st != SF_OK) return _st; } while (0)
+#define SF_HIP(expr) do { if ((expr) != hipSuccess) return SF_ERR_LAUNCH; } while (0)
+
+namespace sf {
+
+struct Arena {
+  float* base;
+  size_t cap, off;
+  Arena(float* b, size_t bytes) : base(b), cap(bytes / sizeof(float)), off(0) {}
+  float* take(size_t n) {
+    size_t a = (n + 63) & ~size_t(63);
+    if (!base || off + a > cap) { off = cap + 1; return nullptr; }
+    float* p = base + off;
+    off += a;
+    return p;
+  }
+  bool ok() const { return off <= cap; }
+};
+inline size_t al(size_t n) { return (n + 63) & ~size_t(63); }
+
+// Switches, read once per process from the environment (experiments and A/B aids only; defaults are the shipped choice).  geti is the only
+// reader; isset: a debugging aid that is on when its variable is set at all.
+int geti(const char* name, int dflt);
+inline bool isset(const char* name) { return geti(name, INT32_MIN) != INT32_MIN; }
+struct Tune {
+  // 1: one latent: the launches of a rollout run as phases of ONE persistent flow kernel per cell boundary (conv_sp.hip: sp_flow_kernel;
+  // workgroups flow from one layer's tile to the next on per-tile dependency counters, every wait bounded: sf_flow_errors).  Bitwise equal
+  // to the launch-per-layer path in the same form of the layers, <= 1e-3 against the oracle (tests/test_gpu_persistent.py).  Round 6,
+  // both measured in one session (profiles/r06_z_bench.json): 174.2 us per steady-state step against 141.5 for the launch path, whose
+  // 3x3 / 7x7 layers run in the Winograd form the flow kernel does not have.  Off by default
+  int persist = geti("SF_PERSIST", 0);
+  int b3_small_tiles = geti("SF_B3_SMALL_TILES", 0);   // experiment: bf16x3 layers with 128-multiple cout on 64 x 128 tiles (3 workgroups per CU) instead of 128 x 128 (2)
+  int wide64 = geti("SF_WIDE64", 0);               // 1: 64-cout layers at >= 131072 pixels on 64 x 256 tiles (variant 10) instead of 64 x 128
+  int seg_maxph = geti("SF_SEG_MAXPH", 1 << 30);   // diagnostic: at most this many phases per persistent flow launch (1: every phase its own launch of the flow kernel)
+  int wino = geti("SF_WINO", 1);                   // layers packed with Winograd weights run conv_wino.hip from wino_min_p pixels (0: direct form everywhere)
+  int wino_min_p = geti("SF_WINO_MIN_P", 14000);   // measured (profiles/r04_zz_wino_min_p_sweep.txt, r04_zz_step_min_p_batched_latents.txt): 6 or more batched 50x50 latents
+                                                   // and one 200x200 latent gain 6-11 % per ODE step, 5 latents / one 100x100 latent lose 4-7 %; 32 latents +1.6 % on the headline
+  int wino_sp = geti("SF_WINO_SP", 1);             // one latent (small-P kernel, launch path): its 3x3 layers run in the Winograd form too (conv_sp.hip; 0: direct form — the round-5 step)
+  int wino_sp7 = geti("SF_WINO_SP7", 1);           // ... and the trusting gate's 7x7 as nine Winograd 3x3 sub-kernels (144 instead of 196 products per 2x2 outputs; 0: direct form)
+  int sp_short_tail = geti("SF_SP_SHORT_TAIL", 1); // ... short trailing problems of a group do not count against the 256-workgroup cap (see sp_plan)
+  int wsp_minsub = geti("SF_WSP_MINSUB", 1);       // ... a K slice of such a layer is at least this many 32-channel sub-chunks (measured: 1 -> 148.2 us per step, 2 -> 150.3)
+  int flow_timeout = geti("SF_FLOW_TIMEOUT", 1 << 22);   // polls before a dependency wait of the flow kernel gives up (~1 us each: seconds); bring-up runs use a small value
+  int fenced = geti("SF_HANDOFF_FENCED", 0);       // 1: split-K hand-offs also run the agent-scope release / acquire fences of round 1 (known-good reference for the fence-free sc1 form; gfx950 only either way)
+  int b3 = geti("SF_BF16X3", 1);                   // layers packed with split-bf16 weights (opt-in at pack time) run the bf16x3 K loop where a kernel has one (0: exact fp32 even then)
+  int pipe = geti("SF_PIPE", 2);                   // one latent: branch 2 of the NEXT dual cell (gates2 -> cand2, functions of the state only) rides in the launches of infer_state, its conv_decoder_2 in the candidate launch (0: every cell on its own, 5 launches)
+  int sp = geti("SF_SP", 1);                       // small pixel counts: the loader / consumer kernel of conv_sp.hip (0: the round-1 kernels)
+  int sp_xcd = geti("SF_SP_XCD", 1);               // ... bit 0: compact 1-D grid (no idle workgroups: step 198 -> 195 us); bit 1: XCD-contiguous logical ids (measured: fabric traffic 156 -> 144 MB per step but 195 -> 203 us; tile-major 133 MB and 218 us — the round-robin spread of a layer's workgroups over the XCDs is the fast one)
+  int sp_split_wgs = geti("SF_SP_SPLIT_WGS", 240); // ... K ranges are split across about this many workgroups per launch
+  int sp_bn = geti("SF_SP_BN", 0);                 // ... pixels per tile (0: by the amount of work, see sp_bn)
+  int sp_max_p = geti("SF_SP_MAX_P", 4096);        // ... used below this many pixels (one 50x50 latent; measured: from two samples on the round-1 kernels are as fast or faster)
+  int sp_fuse_se = geti("SF_SP_FUSE_SE", 1);       // ... SE gates computed in the consuming layer's prologue (one sample)
+  int sp_wide_work = geti("SF_SP_WIDE_WORK", 1000);// ... 64-pixel tiles + split K from this many (64x64 tile) x (64-deep chunk) units per launch
+  int sp_magic = geti("SF_SP_MAGIC", 1);           // ... its block / pixel decode divides by multiplication with host-made reciprocals (0: divides)
+  int direct = geti("SF_DIRECT", 1);               // 0 disables the direct-fragment kernel
+  int mt = geti("SF_DIRECT_MT", 0);                // ... force its tile height
+  int ks = geti("SF_DIRECT_KS", 0);                // ... force its K-group count
+  int chunks_per_wave = std::max(1, geti("SF_DIRECT_CPW", 5));   // ... its target chunks per wave
+  int split = geti("SF_SPLIT", 1);                 // cross-workgroup split-K on 64x64 tiles (small P)
+  int split_target = geti("SF_SPLIT_WGS", 1024);   // round 2 (sc1 hand-off): 512 -> 1024, batch-8 step 754 -> 701 us    // aim for this many workgroups per launch
+  int split_min_chunks = geti("SF_SPLIT_MINCH", 2);
+  int mid_tiles = geti("SF_MID_TILES", 1300);      // round 2: 640 -> 1300 (the 200x200 latent splits its 7x7 too: 1364 -> 1311 us)
+  int glds = geti("SF_GLDS", 15);                  // LDS-DMA staging for large plain layers: bit 0 = 128-cout tiles, bit 1 = 64-cout tiles, bit 2 = LayerNorm-epilogue tiles, bit 3 = cross-workgroup split-K launches (0: register staging everywhere)
+  int glds_var = geti("SF_GLDS_VAR", -1);          // -1: shipped choice; 0..8: force a variant of launch_conv_glds (experiments)
+  int small_dma = geti("SF_SMALL_DMA", 1);         // >= 0: plain layers below LARGE_P run on the LDS-DMA kernel (32x32 tiles); bit 0: GRU candidates too (pre-gated state)
+  int narrow = geti("SF_NARROW", 9);               // tile variant for layers with <= 32 output channels (32 cout x 128 px; -1: the 64-row tiles)
+  int large_p = geti("SF_LARGE_P", 8192);          // measured: a 4-sample rollout (10000 px) is 18 % faster on the small-P kernels, 8 samples (20000 px) on the large tiles
+  int mid_minch_ln = geti("SF_MID_MINCH_LN", 1);   // LayerNorm-epilogue layers at mid P take the 64x64 tiles from this many K chunks (the 1x1 of the trusting gate: 4-sample step 415 -> 408 us; 8: the round-1 rule, 64x128 tiles for short K)
+  int sp_fuse_1x1 = geti("SF_SP_FUSE_1X1", 1);     // small-P kernel: the trusting gate's 1x1 layer runs inside the 7x7 layer's launch
+  int split_cfg = geti("SF_SPLIT_CFG", 4);         // tile config of the mid-P split-K launches without a LayerNorm epilogue (4 | 1)
+  int split_from = geti("SF_SPLIT_FROM", 100);     // only layers with at least this many K chunks (the 7x7)
+  int wino_group = geti("SF_WINO_GROUP", 1);       // Winograd layers of identical geometry (the two branches of a dual cell) share ONE launch: their tails merge
+  bool wino_list = isset("SF_WINO_LIST");          // debugging aid (tools/r05/wino_layers.py): every Winograd launch timed by itself on stderr — SYNCHRONISES the stream
+  bool wino_why = isset("SF_WINO_WHY");            // debugging aid: which large 3x3 launches keep the direct form
+  int upsample_fused = geti("SF_UPSAMPLE_FUSED", 1);   // the upsampled identity skip of a residual block is read by the Winograd epilogue (0: the caller materialises it)
+  int pool_fused = geti("SF_POOL_FUSED", 1);       // MaxPool2d(2) behind a residual block runs in the Winograd epilogue (0: a pooling launch)
+  int mlp_fused = geti("SF_MLP_FUSED", 1);         // the ConvNeXt pointwise MLP runs as one launch (convnext_mlp.hip; 0: two)
+  bool prof_dump = isset("SF_PROF_DUMP");          // debugging aid: one line per profiled launch on stderr, in launch order
+};
+const Tune& tune();
+#define LARGE_P tune().large_p   // pixels from which the 64x64 / 64x128 tiles are used
+
+// Fill a problem from a packed layer + geometry.  Output spatial size follows the conv formula.
+ConvProblem problem(const sf_conv_w& w, const float* in0, const float* in1, float* out, int n_img, int Hin, int Win, int in_up = 0);
+// Launch a group of independent layers (1..SF_MAX_GROUP problems, one epilogue family) on the kernel family that takes it
+int run(const ConvProblem* ps, int n, int epi, hipStream_t st);
+inline int run1(const ConvProblem& p, int epi, hipStream_t st) { return run(&p, 1, epi, st); }
+// what run() will decide, for the modules that shape their launch groups by it
+bool wino_runs(const ConvProblem& q, int epi);                        // this problem runs on the Winograd kernel of the large launches
+bool sp_takes(const ConvProblem* ps, int n, int epi);                 // this group runs on the small-P kernel
+int chansum_tile_px(const ConvProblem* group, int n, int epi);
+bool pregate(long P, const sf_conv_w& cand);
+// zero fill / device-to-device copy as kernels (graph nodes like everything around them)
+hipError_t zero_fill(void* p, size_t bytes, hipStream_t st);
+hipError_t copy_floats(const float* src, float* dst, size_t n, hipStream_t st);
+
+// ---- profiled launches: `launch` runs as it is while the profiler is off; while it is on, it is bracketed by two pooled events and
+// recorded as `cost()` = {key (_lib.py KERNEL_NAMES), flops, bytes}.  Returns the launch's status (a failed launch records nothing)
+struct Cost { int key; double flops, bytes; };
+bool prof_on();
+hipError_t prof_timed(const Cost& c, const std::function<hipError_t()>& launch, hipStream_t st);
+template <class Launch, class CostFn>
+hipError_t timed(Launch&& launch, CostFn&& cost, hipStream_t st) { return prof_on() ? prof_timed(cost(), launch, st) : launch(); }
+void prof_enable(bool on);
+int prof_collect(int32_t* calls, double* ms, double* flops, double* bytes);      // sf_prof_collect
+int debug_stamps(void* buf);                                                     // sf_debug_stamps
+
+// Scratch for the cross-workgroup split-K path, carved from the caller's workspace by the top-level entry points for the duration of one
+// call (RAII; the pointer to it is thread-local inside dispatch.hip, no global allocation)
+struct SplitCtx { float* slab; size_t slab_floats; unsigned* counters; int ncounters; };
+constexpr size_t SPLIT_SLAB_FLOATS = size_t(8) << 20;   // 32 MB: 2048 (tile, slice) pairs of 64x64 fp32
+constexpr int SPLIT_COUNTERS = 4096;
+constexpr size_t SPLIT_WS_FLOATS = SPLIT_SLAB_FLOATS + SPLIT_COUNTERS + 128;
+struct SplitScope {
+  SplitCtx ctx;
+  SplitCtx* prev;
+  SplitScope(Arena& A, hipStream_t st);
+  ~SplitScope();
+};
+
+// ---- persistent flow (one latent inside a rollout, SF_PERSIST=1 / sf_set_flow_mode): while a FlowScope is active, run() records its
+// small-P launch groups as phases of ONE persistent launch instead of launching them (dispatch.hip: FlowBuilder)
+struct FlowBuilder;
+struct FlowScope {
+  FlowBuilder* fb = nullptr;
+  int status = SF_OK;
+  // `allow` and the flow mode and a split-K scratch: carves the tables and counters from A (check A.ok(), then status) and zeroes the counters
+  FlowScope(bool allow, Arena& A, hipStream_t st);
+  ~FlowScope();
+  const unsigned* err() const;      // error word of the flow's bounded waits (null: no flow)
+};
+size_t flow_ws_floats();            // workspace of a FlowScope under the flow mode in force now (0: off)
+int seg_flush();                    // anything that is not a small-P launch first sends the recorded phases on their way (stream order)
+int flow_copy_out(const float* src, float* dst, size_t n, hipStream_t st);      // state copy-out: rides in the next phase, or a copy launch
+// end of a rollout: NaN over both outputs if a bounded wait of its flow timed out (err != null), and remember err for flow_errors()
+int flow_close(const unsigned* err, float* a, size_t na, float* b, size_t nb, hipStream_t st);
+int set_flow_mode(int on);          // sf_set_flow_mode
+int flow_errors(hipStream_t st);    // sf_flow_errors
+
+}  // namespace sf

@@ -64,12 +64,9 @@ struct ConvProblem {
   // transpose launch): element (image i, pixel p, channel c) goes to out + (i / pl_div) * pl_sa + (i % pl_div) * pl_sb + c * HW + p
   int out_planar, pl_div;
   size_t pl_sa, pl_sb;
-  // AFFINE, Winograd kernel only (even Hout, Wout): `out` is the 2x2 max-pooled tensor [n][Hout/2][Wout/2][out_cs] — a thread of the
-  // epilogue holds exactly one pooling window (its tile), so the pool costs three maxima and the full-size tensor is never written
-  // (res_models.py:101-105: every encoder block is followed by MaxPool2d(2))
   // small-P kernel: ceil(2^32 / d) of the divisors its block decode and its loaders' pixel decode use (0: divide) — tiles of the
   // problem, pixel tiles, pixels per image, output width, 32-deep sub-chunks per tap, kernel width — and the chunks per K slice.
-  // Filled by api.hip once the tile width and the split are chosen: an integer division is a ~25-instruction reciprocal sequence
+  // Filled by dispatch.hip (sp_plan) once the tile width and the split are chosen: an integer division is a ~25-instruction reciprocal sequence
   // through the vector unit, eight of them sat in front of the first DMA of every launch of a step
   unsigned sp_m_tiles, sp_m_npt, sp_m_hw, sp_m_w, sp_m_kcpt, sp_m_kw;
   int sp_cps, sp_bn;
@@ -77,6 +74,9 @@ struct ConvProblem {
   // its K slices then count 32-channel sub-chunks (sp_cps of them per slice) and sp_m_tw is ceil(2^32 / (Wout / 2)) (0: divide)
   int sp_wino;
   unsigned sp_m_tw;
+  // AFFINE, Winograd kernel only (even Hout, Wout): `out` is the 2x2 max-pooled tensor [n][Hout/2][Wout/2][out_cs] — a thread of the
+  // epilogue holds exactly one pooling window (its tile), so the pool costs three maxima and the full-size tensor is never written
+  // (res_models.py:101-105: every encoder block is followed by MaxPool2d(2))
   int pool2;
   // AFFINE, Winograd kernel only: `add` is a half-resolution tensor [n][Hout/2][Wout/2][add_cs] read with nearest x2 upsampling — the
   // four pixels of a tile share one source pixel (the identity skip of a residual block whose input is upsampled on read)
@@ -90,12 +90,12 @@ struct ConvProblem {
   // drop out of a tile: models/sparse_encoder.py); dropped taps would have gathered zero rows, the sums are bitwise the same
   const unsigned* tap_mask;
   int tap_mask_n;
-  // small-P kernel, one image: the SE gate of the input (res_models.py:161-165) is computed in the consuming layer's
-  // prologue from the per-tile channel sums the producer wrote: scale = sigmoid(fc2 relu(fc0 mean)), every workgroup
-  // for itself; workgroup 0 also stores it to se_out (the residual of the next layer is scaled by it)
   // SAMPLE epilogue without an eps tensor (e0 == null): {seed, offset} record on the device + the draw index of this call
   const unsigned long long* philox;
   int draw;
+  // small-P kernel, one image: the SE gate of the input (res_models.py:161-165) is computed in the consuming layer's
+  // prologue from the per-tile channel sums the producer wrote: scale = sigmoid(fc2 relu(fc0 mean)), every workgroup
+  // for itself; workgroup 0 also stores it to se_out (the residual of the next layer is scaled by it)
   const float* se_sum;    // [se_nt][c0] per-tile channel sums (null: in_scale holds the gate, or no gate)
   const float* se_fc0;    // [se_cr][c0]
   const float* se_fc2;    // [c0][se_cr]
@@ -150,7 +150,7 @@ struct ConvLaunch {
 // space (scalar loads).  One 768-thread workgroup per CU stays resident and runs item `wg` of every phase in order.  Ordering
 // is by dataflow, not by a grid barrier: finished tiles are counted per (phase, pixel tile) in `done`, and an item starts when
 //   (1) every tile of phase q-2 is done (covers every input older than the previous phase and every buffer-reuse hazard:
-//       api.hip's scratch aliasing has a reuse distance of >= 2 phases), and
+//       the modules' scratch aliasing (api.hip) has a reuse distance of >= 2 phases), and
 //   (2) the tiles of phase q-1 under its halo are done (all of them for an SE gate, which is a global reduction).
 #define SP_FLOW_MAX_TILES 80         // pixel tiles of one phase (one 50x50 latent on 32-pixel tiles: 79)
 #define SP_PHASE_CONV 0

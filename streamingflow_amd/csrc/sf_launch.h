@@ -1,0 +1,40 @@
+// Host launchers of the kernel files, declared once: every .hip file that defines one and every caller includes this header, so a changed
+// signature fails to compile instead of failing to link.
+#pragma once
+#include "sf_device.h"
+
+namespace sf {
+hipError_t launch_conv(const ConvLaunch& L, int epi, int cfg, hipStream_t stream);
+hipError_t launch_conv_direct(const ConvLaunch& L, int epi, int mt, int ks, hipStream_t stream);
+hipError_t launch_conv_glds(const ConvLaunch& L, int epi, int tile, int variant, hipStream_t stream);
+hipError_t set_stamp_buffer(unsigned long long* p);
+int glds_occupancy(int which);
+hipError_t set_stamp_buffer_sp(unsigned long long* p);
+hipError_t set_stamp_buffer_wino(unsigned long long* p);
+hipError_t launch_conv_sp(const ConvLaunch& L, int epi, bool scaled, int bn, hipStream_t stream);
+hipError_t launch_conv_wino(const ConvLaunch& L, int epi, hipStream_t stream);
+bool wino_takes(const ConvProblem& q, int epi);
+bool wino_same_geometry(const ConvProblem& a, const ConvProblem& b);
+int wino_variant(const ConvProblem& q);
+double wino_tiles(const ConvProblem& q);
+hipError_t launch_sp_flow(const SpFlow& F, int grid, bool b3, hipStream_t stream);
+hipError_t launch_flow_write(const void* host_src, void* dev_dst, size_t bytes, hipStream_t stream);
+bool sp_flow_has(int epi, bool scaled, int bn);
+int sp_flow_capacity(bool b3);
+hipError_t launch_convnext_mlp(const float* t, const float* x, float* out, const float* w1, const float* s1, const float* b1, const float* w2, const float* s2, const float* b2, long P, hipStream_t stream);
+hipError_t launch_transpose(const float* in, float* out, int n, int rows, int cols, hipStream_t s);
+hipError_t launch_transpose_strided(const float* in, float* out, int n, int rows, int cols, size_t in_stride, size_t out_stride, hipStream_t s);
+hipError_t launch_maxpool2(const float* in, float* out, int n, int Hin, int Win, int C, int ceil_pad, hipStream_t s);
+hipError_t launch_mean_from_partials(const float* part, float* out, int n, int nslab, int C, int hw, hipStream_t s);
+hipError_t launch_logsigmoid(const float* in, float* out, size_t n, hipStream_t s);
+hipError_t launch_upsample2(const float* in, float* out, int n, int Hin, int Win, int C, hipStream_t s);
+hipError_t launch_broadcast_channels(const float* vec, float* out, int n, int HW, int k, int out_cs, int out_co, hipStream_t s);
+hipError_t launch_upsample_bilinear2_add(const float* in, const float* skip, float* out, int n, int Hin, int Win, int C, hipStream_t s);
+hipError_t launch_se_fc(const float* chansum, int ntile, int C, int Cr, int hw, const float* fc0, const float* fc2, float* scale, int n_img, hipStream_t s);
+hipError_t launch_chan_partial(const float* in, float* part, int n, int HW, int C, int nslab, hipStream_t s);
+hipError_t launch_dwconv7_ln(const float* in, float* out, const float* wdw, const float* bdw, const float* lnw, const float* lnb, int n, int H, int W, int C, float eps, hipStream_t s);
+hipError_t launch_aspp_pool(const float* in, float* part, float* bias_img, int n, int HW, int C, int hid, const float* w1, const float* s1, const float* b1, const float* wp, const float* ps, const float* pb, int nslab, hipStream_t s);
+
+// ceil(2^32 / d) for the kernels' divisions by multiplication (0 for d <= 1: "divide"); exact while dividend x d < 2^32
+inline unsigned magic(long d) { return d <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned long long)d - 1) / (unsigned long long)d); }
+}  // namespace sf

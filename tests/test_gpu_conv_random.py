@@ -1,7 +1,7 @@
 """GPU: randomised parity sweep of the fused convolution entry points (sf_conv2d_ex_fwd) against torch CPU fp32:
 random channel splits (two concatenated inputs), kernel sizes, strides, dilations, paddings, batch sizes, odd
 spatial sizes, channel-sliced inputs / outputs, residual before or after the activation.  The seeds are fixed:
-the same 48 configurations every run; they cover every tile configuration the dispatcher can choose
+the same 48 configurations every run; they cover every tile configuration the dispatcher (csrc/dispatch.hip: run) can choose
 (direct-fragment, split-K, 64x64, 128x128)."""
 import ctypes
 import os
