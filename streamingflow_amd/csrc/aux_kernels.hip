@@ -486,11 +486,11 @@ hipError_t launch_dwconv7_ln(const float* in, float* out, const float* wdw, cons
   static const bool pk = [] { const char* v = std::getenv("SF_DWCONV_PK"); return v ? std::atoi(v) != 0 : true; }();
   if (pk && C == 64 && (long)n * H * W >= 65536 && (double)H * W * C * 4.0 < 1073741824.0) {
     // two channels per lane, two strips per wave: strips of an image must come in pairs
-    int seg = 40;
-    const int nrb = (H + 1) / 2;
-    if ((nrb * ((W + seg - 1) / seg)) & 1) seg = W;      // one strip per row pair ...
-    if (((nrb * ((W + seg - 1) / seg)) & 1) == 0) {      // ... (an odd number of row pairs of one strip each keeps the one-channel kernel)
-      const int nseg = (W + seg - 1) / seg;
+    const int seg = 40;
+    const int nrb = (H + 1) / 2, nseg = (W + seg - 1) / seg;
+    // an odd number of strips per image (odd row pairs x odd segments) keeps the one-channel kernel; one whole-width segment per
+    // row pair would not help: the number of row pairs is odd whenever the product is
+    if (((nrb * nseg) & 1) == 0) {
       const long per_img = (long)nrb * nseg, waves = ((long)n * per_img) / 2;
       auto magic = [](long d) { return d <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned long long)d - 1) / (unsigned long long)d); };
       if ((double)n * per_img * per_img < 4.0e9) {      // exact quotients (dividend x divisor < 2^32)
