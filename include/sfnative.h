@@ -514,7 +514,17 @@ int sf_sparse_to_dense_fwd(const float* feats, const int32_t* coords, int n, int
  *   exact integer sums of (row, col) and — when flow [F][2][H][W] and warped_fx are given — sums of (row + flow0,
  *   col + flow1) in 2^-20 fixed point (int64).  Integer atomics only, so the sums do not depend on the arrival order:
  *   the masked means of instance.py:213-236 for every frame of a sequence at once.
- * sf_confusion_frames_fwd — sf_confusion_fwd per frame of F equally sized label-map pairs: out[F][K][K]. */
+ * sf_confusion_frames_fwd — sf_confusion_fwd per frame of F equally sized label-map pairs: out[F][K][K].
+ * sf_instance_seq_fwd — get_instance_segmentation_and_centers (instance.py:119-144) for F frames at once: center [F][H][W],
+ *   offsets [F][2][H][W], foreground [F][H][W] bytes.  Per frame: the centres as sf_instance_centers_fwd finds them (one flag
+ *   pass and one exclusive scan over all F*H*W pixels; rank within a frame = scan value - the frame's first scan value) cut to
+ *   the first `cap` -> centers [F][cap][2] (row, col), rows past min(n, cap) zero, and the UNCAPPED count -> n_centers [F];
+ *   the grouping of sf_group_pixels_fwd over the frame's own min(n, cap) centres (a frame without centres is all zeros); ids
+ *   made consecutive in the order of their values (lut[v] = number of present values < v, so a frame without a background
+ *   pixel starts at 0, as the reference's does) -> instance [F][H][W] int64, every id <= cap.  Enqueues only: no allocation,
+ *   no synchronisation, nothing read back.  SF_ERR_INVALID: a NULL pointer, F / H / W / cap < 1, F*H*W or F*(cap+1) >= 2^31,
+ *   or F * ceil(H*W / 256) * 256 >= 2^32 (the grouping launch pads each frame to whole workgroups of 256 pixels);
+ *   SF_ERR_WORKSPACE: ws_bytes < sf_instance_seq_ws_bytes(F, H, W, cap) (exactly that size is enough; 0 for invalid sizes). */
 /* sf_warp_affine_fwd — warp_features (utils/geometry.py:196-236): F.affine_grid(theta [B][2][3], align_corners=False)
  *   + F.grid_sample(mode nearest | bilinear, padding zeros, align_corners=False) on NCHW maps x [B][C][H][W]. */
 int sf_warp_affine_fwd(const float* x, const float* theta, int B, int C, int H, int W, int bilinear, float* out,
@@ -529,6 +539,10 @@ int sf_instance_moments_fwd(const int64_t* instance, const float* flow, int F, i
                             int64_t* warped_fx, int32_t* counts, void* stream);
 int sf_confusion_frames_fwd(const int64_t* a, const int64_t* b, long n_per_frame, int F, int K, int64_t* out, int32_t* bad,
                             void* stream);
+size_t sf_instance_seq_ws_bytes(int F, int H, int W, int cap);
+int sf_instance_seq_fwd(const float* center, const float* offsets, const uint8_t* foreground, int F, int H, int W,
+                        float conf_threshold, int cap, int32_t* centers, int32_t* n_centers, int64_t* instance, void* ws,
+                        size_t ws_bytes, void* stream);
 
 /* hipGraph capture of whatever the caller enqueues between begin and end on `stream` (must not be
  * the legacy default stream). */

@@ -10,6 +10,8 @@
 //                             of make_instance_id_temporally_consistent (instance.py:213-236), all frames in one launch,
 //                             integer atomics only (order-independent)
 //   sf_confusion_frames_fwd   the joint histogram per frame of a whole label sequence in one launch
+//   sf_instance_seq_fwd       centres, grouping and consecutive ids (get_instance_segmentation_and_centers, instance.py:119-144)
+//                             of a whole sequence of frames: a fixed number of launches, nothing read back by the host
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -131,6 +133,116 @@ __global__ void confusion_frames_kernel(const long long* __restrict__ a, const l
   }
 }
 
+// ---- the same post-processing for F frames [F][H][W] at once (sf_instance_seq_fwd) -------------------------------------------
+// One flag / scan / compaction over all F*H*W pixels: a centre's rank within its frame is its scan value minus the scan value of
+// the frame's first pixel, so each frame fills its own [cap][2] table and an overflowing frame never reaches the next one.
+__global__ void seq_center_flag_kernel(const float* __restrict__ c, int F, int H, int W, float thr, int* __restrict__ flag) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int plane = H * W;
+  if (idx >= (long)F * plane) return;
+  const int f = (int)(idx / plane), pix = (int)(idx - (long)f * plane);
+  const int i = pix / W, j = pix - i * W;
+  const float* cf = c + (size_t)f * plane;
+  auto val = [&](int y, int x) -> float {
+    if (y < 0 || y >= H || x < 0 || x >= W) return -INFINITY;       // max_pool2d pads with -inf
+    const float v = cf[y * W + x];
+    return v > thr ? v : -1.f;                                       // F.threshold(x, thr, -1)
+  };
+  const float v = val(i, j);
+  float m = v;
+#pragma unroll
+  for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+    for (int dx = -1; dx <= 1; ++dx) m = fmaxf(m, val(i + dy, j + dx));
+  flag[idx] = (v == m && v > 0.f) ? 1 : 0;
+}
+
+__global__ void seq_center_compact_kernel(const int* __restrict__ flag, const int* __restrict__ scan, int F, int H, int W, int cap,
+                                          int* __restrict__ centers, int* __restrict__ n_out) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int plane = H * W;
+  if (idx >= (long)F * plane) return;
+  const int f = (int)(idx / plane), pix = (int)(idx - (long)f * plane);
+  const int base = scan[(size_t)f * plane];
+  if (pix == plane - 1) n_out[f] = scan[idx] + flag[idx] - base;   // uncapped
+  if (!flag[idx]) return;
+  const int r = scan[idx] - base;
+  if (r >= cap) return;
+  int* row = centers + ((size_t)f * cap + r) * 2;
+  row[0] = pix / W;
+  row[1] = pix % W;
+}
+
+// group_pixels_kernel per frame: a workgroup serves 256 pixels of ONE frame and walks that frame's min(n, cap) centres through LDS
+// in pieces of SEQ_CHUNK (ascending, so the first minimum still wins ties).  Also marks which raw ids 0..cap the frame holds.
+constexpr int SEQ_CHUNK = 128;
+__global__ void seq_group_pixels_kernel(const int* __restrict__ centers, const int* __restrict__ n_centers, int cap, const float* __restrict__ off,
+                                        const unsigned char* __restrict__ fg, int H, int W, int blocks_per_frame,
+                                        long long* __restrict__ inst, int* __restrict__ present) {
+  __shared__ int tab[2 * SEQ_CHUNK];
+  const int f = blockIdx.x / blocks_per_frame;
+  const int plane = H * W;
+  const int pix = (blockIdx.x - f * blocks_per_frame) * blockDim.x + threadIdx.x;
+  const bool live = pix < plane;
+  const int nc = min(n_centers[f], cap);
+  const int* table = centers + (size_t)f * cap * 2;
+  const float* of = off + (size_t)f * 2 * plane;
+  const int i = pix / W, j = pix - i * W;
+  float lx = 0.f, ly = 0.f;
+  if (live) { lx = __fadd_rn((float)i, of[pix]); ly = __fadd_rn((float)j, of[plane + pix]); }
+  float best = INFINITY;
+  int arg = 0;
+  for (int k0 = 0; k0 < nc; k0 += SEQ_CHUNK) {       // nc is uniform over the workgroup: every thread reaches the barriers
+    const int m = min(SEQ_CHUNK, nc - k0);
+    __syncthreads();
+    for (int e = threadIdx.x; e < 2 * m; e += blockDim.x) tab[e] = table[2 * k0 + e];
+    __syncthreads();
+    for (int k = 0; k < m; ++k) {
+      const float dx = __fsub_rn((float)tab[2 * k], lx), dy = __fsub_rn((float)tab[2 * k + 1], ly);
+      const float d = __fsqrt_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)));
+      if (d < best) { best = d; arg = k0 + k; }
+    }
+  }
+  if (!live) return;
+  const int id = (nc > 0 && fg[(size_t)f * plane + pix]) ? arg + 1 : 0;     // a frame without centres is all background
+  inst[(size_t)f * plane + pix] = (long long)id;
+  present[(size_t)f * (cap + 1) + id] = 1;                                  // every writer stores the same value
+}
+
+// lut[f][v] = number of present values of frame f smaller than v (make_instance_seg_consecutive: the inverse index of a sorted
+// unique; a frame without background pixels has present[0] == 0, so its first instance becomes 0, as in the reference).
+// One workgroup of 256 per frame, 256 values per round: ballot prefix inside a wave, wave totals through LDS.
+__global__ void seq_lut_kernel(const int* __restrict__ present, int cap, int* __restrict__ lut) {
+  __shared__ int wave_sum[4];
+  const int f = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int* p = present + (size_t)f * (cap + 1);
+  int* l = lut + (size_t)f * (cap + 1);
+  int carry = 0;
+  for (int v0 = 0; v0 <= cap; v0 += 256) {
+    const int v = v0 + threadIdx.x;
+    const bool on = v <= cap && p[v] != 0;
+    const unsigned long long b = __ballot(on);
+    const int before = __popcll(b & ((1ULL << lane) - 1ULL));
+    __syncthreads();
+    if (lane == 0) wave_sum[wave] = __popcll(b);
+    __syncthreads();
+    int prior = carry, total = 0;
+    for (int w = 0; w < 4; ++w) {
+      if (w < wave) prior += wave_sum[w];
+      total += wave_sum[w];
+    }
+    if (v <= cap) l[v] = prior + before;
+    carry += total;
+  }
+}
+
+__global__ void seq_relabel_kernel(const int* __restrict__ lut, int cap, long plane, long total, long long* __restrict__ inst) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  const long f = idx / plane;
+  inst[idx] = (long long)lut[f * (cap + 1) + inst[idx]];
+}
+
 // warp_features (utils/geometry.py:196-236): affine_grid(theta, align_corners=False) + grid_sample(mode, zeros
 // padding, align_corners=False) on NCHW maps.  theta [b][6] row major (2 x 3).
 //   base grid   x_j = (2j + 1)/W - 1,  y_i = (2i + 1)/H - 1
@@ -226,6 +338,64 @@ int sf_group_pixels_fwd(const int32_t* centers, int n_centers, const float* offs
   if (!centers || !offsets || !foreground || !instance || n_centers < 1 || H < 1 || W < 1) return SF_ERR_INVALID;
   hipLaunchKernelGGL(group_pixels_kernel, dim3((H * W + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), centers, n_centers,
                      offsets, foreground, H, W, reinterpret_cast<long long*>(instance));
+  return hipGetLastError() == hipSuccess ? SF_OK : SF_ERR_LAUNCH;
+}
+
+// workspace of sf_instance_seq_fwd: flags, scan (F*H*W ints each), rocPRIM's scan storage, present and lut ((cap + 1) ints per frame each).
+// The one place the sizes are checked and the layout is laid out: both entry points below go through it.
+struct SeqLayout {
+  size_t n, tab, a, at, tb, total;
+  int bpf;      // workgroups of 256 pixels per frame
+};
+static bool seq_layout(int F, int H, int W, int cap, hipStream_t st, SeqLayout* L) {
+  if (F < 1 || H < 1 || W < 1 || cap < 1) return false;
+  L->n = (size_t)F * H * W;
+  L->tab = (size_t)F * ((size_t)cap + 1);
+  if (L->n >= (size_t(1) << 31) || L->tab >= (size_t(1) << 31)) return false;
+  L->bpf = (int)(((size_t)H * W + 255) / 256);
+  // the grouping launch pads every frame to whole workgroups: its thread count has to stay a 32-bit number too
+  if ((size_t)F * L->bpf * 256 >= (size_t(1) << 32)) return false;
+  L->a = a256e(L->n * 4);
+  L->at = a256e(L->tab * 4);
+  size_t tb = 0;
+  (void)rocprim::exclusive_scan(nullptr, tb, (const int*)nullptr, (int*)nullptr, 0, L->n, rocprim::plus<int>(), st);
+  L->tb = a256e(tb);
+  L->total = 2 * L->a + L->tb + 2 * L->at;
+  return true;
+}
+
+size_t sf_instance_seq_ws_bytes(int F, int H, int W, int cap) {
+  SeqLayout L;
+  return seq_layout(F, H, W, cap, nullptr, &L) ? L.total : 0;
+}
+
+int sf_instance_seq_fwd(const float* center, const float* offsets, const uint8_t* foreground, int F, int H, int W, float conf_threshold,
+                        int cap, int32_t* centers, int32_t* n_centers, int64_t* instance, void* ws, size_t ws_bytes, void* stream) {
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  SeqLayout L;
+  if (!center || !offsets || !foreground || !centers || !n_centers || !instance || !ws || !seq_layout(F, H, W, cap, st, &L))
+    return SF_ERR_INVALID;
+  if (ws_bytes < L.total) return SF_ERR_WORKSPACE;
+  const size_t n = L.n, tab = L.tab, a = L.a, at = L.at, tb = L.tb;
+  char* p = static_cast<char*>(ws);
+  int* flag = reinterpret_cast<int*>(p);
+  int* scan = reinterpret_cast<int*>(p + a);
+  void* tmp = p + 2 * a;
+  int* present = reinterpret_cast<int*>(p + 2 * a + tb);
+  int* lut = reinterpret_cast<int*>(p + 2 * a + tb + at);
+  // rows of the centre tables past a frame's count stay zero: the outputs are a function of the inputs alone
+  if (hipMemsetAsync(centers, 0, (size_t)F * cap * 2 * sizeof(int32_t), st) != hipSuccess) return SF_ERR_LAUNCH;
+  if (hipMemsetAsync(present, 0, tab * sizeof(int), st) != hipSuccess) return SF_ERR_LAUNCH;
+  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+  hipLaunchKernelGGL(seq_center_flag_kernel, grid, block, 0, st, center, F, H, W, conf_threshold, flag);
+  size_t scan_bytes = tb;
+  if (rocprim::exclusive_scan(tmp, scan_bytes, (const int*)flag, scan, 0, n, rocprim::plus<int>(), st) != hipSuccess) return SF_ERR_LAUNCH;
+  hipLaunchKernelGGL(seq_center_compact_kernel, grid, block, 0, st, flag, scan, F, H, W, cap, centers, n_centers);
+  const int bpf = L.bpf;
+  hipLaunchKernelGGL(seq_group_pixels_kernel, dim3((unsigned)((size_t)F * bpf)), block, 0, st, centers, n_centers, cap, offsets, foreground,
+                     H, W, bpf, reinterpret_cast<long long*>(instance), present);
+  hipLaunchKernelGGL(seq_lut_kernel, dim3((unsigned)F), block, 0, st, present, cap, lut);
+  hipLaunchKernelGGL(seq_relabel_kernel, grid, block, 0, st, lut, cap, (long)H * W, (long)n, reinterpret_cast<long long*>(instance));
   return hipGetLastError() == hipSuccess ? SF_OK : SF_ERR_LAUNCH;
 }
 

@@ -1,19 +1,25 @@
 """Instance post-processing of StreamingFlow's evaluation on the MI355X.
 
-Drop-in for the functions of ``streamingflow/utils/instance.py`` that ``evaluate.py`` reaches (``find_instance_centers``
-:80-92, ``group_pixels`` :95-116, ``get_instance_segmentation_and_centers`` :119-140, ``update_instance_ids`` :143-160,
-``make_instance_seg_consecutive`` :163-168, ``make_instance_id_temporally_consistent`` :171-263,
-``predict_instance_segmentation_and_trajectories`` :370-428): same names, arguments and results.
+Drop-in for the functions of ``streamingflow/utils/instance.py`` that ``evaluate.py`` and ``evaluate_streaming.py`` reach
+(``find_instance_centers`` :80-92, ``group_pixels`` :95-116, ``get_instance_segmentation_and_centers`` :119-140,
+``update_instance_ids`` :143-160, ``make_instance_seg_consecutive`` :163-168, ``make_instance_id_temporally_consistent``
+:171-263, ``make_instance_id_temporally_consistent_short_interval`` :272-368, ``predict_instance_segmentation_and_trajectories``
+:370-428, ``predict_instance_segmentation_and_trajectories_short_interval`` :432-490): same names, arguments and results.
 
 How it is computed here.
-  * Centres, pixel grouping: one kernel each (``sf_instance_centers_fwd``, ``sf_group_pixels_fwd``).
-  * Relabelling is a look-up table gathered on the device; "make ids consecutive" is the inverse index of a sorted
-    unique.
+  * One frame — centres, pixel grouping: one kernel each (``sf_instance_centers_fwd``, ``sf_group_pixels_fwd``);
+    relabelling is a look-up table gathered on the device; "make ids consecutive" is the inverse index of a sorted unique.
+  * A sequence — ``instance_segmentation_sequence``: centres, grouping and consecutive ids of all B*T frames by
+    ``sf_instance_seq_fwd`` (a fixed number of launches, nothing read back; ids are at most ``max_n_instance_centers``).
+    Both ``predict_*`` functions go this way: one sequence call, one moments launch and one device->host copy for all
+    frames, the host matching per sample, one gather.  The host round trips of a call do not depend on B or T.
   * Temporal consistency.  The ids a frame ends up with are a relabelling of its own raw instances, so everything the
     matching needs — each raw instance's pixel count, centre, and centre displaced by the predicted flow — is computed
     for ALL frames by one launch (``sf_instance_moments_fwd``: integer atomics, order-independent) and copied to the
-    host once.  The frame-to-frame assignment (Hungarian method on a handful of centres, ``scipy``) then only produces
-    one small table per frame, and the whole sequence is relabelled by a single gather.
+    host once.  The frame-to-frame assignment (Hungarian method on a handful of centres, ``scipy``,
+    ``_consistent_tables``) then only produces one small table per frame, and the whole sequence is relabelled by a
+    single gather.  The regular matcher compares frame t+1 with the flow-displaced centres of frame t (closer than 3
+    pixels); the short-interval one ignores the flow and compares with the plain centres (closer than 10).
 CUDA tensors only.
 """
 from typing import Tuple
@@ -26,6 +32,7 @@ from . import _lib, runtime
 from .runtime import ptr
 
 MOMENT_SCALE = 1.0 / 1048576.0      # sf_instance_moments_fwd: flow-warped sums are 2^-20 fixed point
+MAX_N_INSTANCE_CENTERS = 100        # the reference's default cut of a frame's centre list; raw ids of a frame are at most this
 
 
 def find_instance_centers(center_prediction: torch.Tensor, conf_threshold: float = 0.1, nms_kernel_size: float = 3):
@@ -78,7 +85,7 @@ def make_instance_seg_consecutive(instance_seg):
 
 
 def get_instance_segmentation_and_centers(center_predictions, offset_predictions, foreground_mask, conf_threshold: float = 0.1,
-                                          nms_kernel_size: float = 3, max_n_instance_centers: int = 100) -> Tuple[torch.Tensor, torch.Tensor]:
+                                          nms_kernel_size: float = 3, max_n_instance_centers: int = MAX_N_INSTANCE_CENTERS) -> Tuple[torch.Tensor, torch.Tensor]:
     """One frame: ([1, H, W] int64 instance map with consecutive ids, [n, 2] centres)."""
     H, W = center_predictions.shape[-2:]
     heat = center_predictions.reshape(1, H, W)
@@ -90,39 +97,83 @@ def get_instance_segmentation_and_centers(center_predictions, offset_predictions
     return make_instance_seg_consecutive(ids), peaks
 
 
+def instance_segmentation_sequence(center, offset, foreground, conf_threshold: float = 0.1, nms_kernel_size: float = 3,
+                                   max_n_instance_centers: int = MAX_N_INSTANCE_CENTERS, return_centers: bool = False):
+    """``get_instance_segmentation_and_centers`` of F frames at once: center [F, 1, H, W] or [F, H, W], offset [F, 2, H, W],
+    foreground [F, H, W] -> [F, H, W] int64 with consecutive ids per frame (at most ``max_n_instance_centers``).  Nothing is
+    copied to the host, unless ``return_centers``: then also a list of the frames' [n, 2] int64 (row, col) centres."""
+    if nms_kernel_size != 3:
+        raise NotImplementedError("only the 3x3 non-maximum suppression the reference uses is built")
+    runtime.require_cuda(center, offset, foreground)
+    if center.dim() == 4:
+        if center.shape[1] != 1:
+            raise AssertionError("center must be [F, 1, H, W] or [F, H, W]")
+        center = center[:, 0]
+    F, H, W = center.shape
+    if tuple(offset.shape) != (F, 2, H, W) or tuple(foreground.shape) != (F, H, W):
+        raise AssertionError("offset must be [F, 2, H, W] and foreground [F, H, W]")
+    cap = int(max_n_instance_centers)
+    heat, votes = runtime.f32c(center), runtime.f32c(offset)
+    inside = (foreground != 0).to(torch.uint8).contiguous()
+    dev = heat.device
+    found = torch.empty((F, cap, 2), dtype=torch.int32, device=dev)
+    count = torch.empty((F,), dtype=torch.int32, device=dev)
+    ids = torch.empty((F, H, W), dtype=torch.int64, device=dev)
+    L = _lib.lib()
+    ws = runtime.workspace(L.sf_instance_seq_ws_bytes(F, H, W, cap), dev)
+    _lib.check(L.sf_instance_seq_fwd(ptr(heat), ptr(votes), ptr(inside), F, H, W, float(conf_threshold), cap, ptr(found), ptr(count), ptr(ids),
+                                     ptr(ws), ws.numel() * 4, runtime.stream_ptr(dev)), "instance_seq")
+    if not return_centers:
+        return ids
+    kept = count.cpu().clamp(max=cap).tolist()
+    return ids, [found[f, :n].long() for f, n in enumerate(kept)]
+
+
+def _moments_to_host(ids, flow, top):
+    """ids [F, H, W] int64 with values <= ``top``, flow [F, 2, H, W] or None -> numpy (counts [F, K] int32, position sums
+    [F, K, 2] int64, flow-warped sums [F, K, 2] int64 in 2^-20 fixed point or None), K = top + 1: one launch, ONE copy."""
+    F, H, W = ids.shape
+    K = top + 1
+    dev = ids.device
+    n = F * K
+    fl = runtime.f32c(flow).view(F, 2, H, W) if flow is not None else None
+    parts = 2 if fl is not None else 1
+    buf = torch.empty((2 * n * parts + (n + 1) // 2,), dtype=torch.int64, device=dev)      # sums, then the int32 counts
+    pos = buf[:2 * n]
+    moved = buf[2 * n:4 * n] if fl is not None else None
+    cnt = buf[2 * n * parts:].view(torch.int32)
+    _lib.check(_lib.lib().sf_instance_moments_fwd(ptr(ids), ptr(fl), F, H, W, top, ptr(pos), ptr(moved), ptr(cnt), runtime.stream_ptr(dev)),
+               "instance_moments")
+    host = buf.cpu().numpy()
+    counts = host[2 * n * parts:].view(np.int32)[:n].reshape(F, K)
+    sums = host[:2 * n].reshape(F, K, 2)
+    warped = host[2 * n:4 * n].reshape(F, K, 2) if fl is not None else None
+    return counts, sums, warped
+
+
+def _means(counts, sums, scale=1.0):
+    """Integer sums / pixel count in float64, then float32 (rows of absent ids are NaN)."""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return (sums * scale / counts[..., None].astype(np.float64)).astype(np.float32)
+
+
 def instance_moments(instance_seq, flow_seq=None):
     """instance_seq [F, H, W] int64, flow_seq [F, 2, H, W] or None -> numpy (counts [F, K], centres [F, K, 2] float32,
     flow-displaced centres [F, K, 2] float32 or None), K = largest id + 1; rows of absent ids are NaN."""
     runtime.require_cuda(instance_seq)
-    F, H, W = instance_seq.shape
     ids = instance_seq.to(torch.int64).contiguous()
-    top = int(ids.max().item())
-    dev = ids.device
-    pos = torch.empty((F, top + 1, 2), dtype=torch.int64, device=dev)
-    cnt = torch.empty((F, top + 1), dtype=torch.int32, device=dev)
-    fl = runtime.f32c(flow_seq).view(F, 2, H, W) if flow_seq is not None else None
-    moved = torch.empty_like(pos) if fl is not None else None
-    _lib.check(_lib.lib().sf_instance_moments_fwd(ptr(ids), ptr(fl), F, H, W, top, ptr(pos), ptr(moved), ptr(cnt), runtime.stream_ptr(dev)),
-               "instance_moments")
-    counts = cnt.cpu().numpy()
-    with np.errstate(invalid="ignore", divide="ignore"):
-        denom = counts[..., None].astype(np.float64)
-        centres = (pos.cpu().numpy() / denom).astype(np.float32)
-        displaced = (moved.cpu().numpy() * MOMENT_SCALE / denom).astype(np.float32) if moved is not None else None
-    return counts, centres, displaced
+    counts, sums, warped = _moments_to_host(ids, flow_seq, int(ids.max().item()))
+    return counts, _means(counts, sums), _means(counts, warped, MOMENT_SCALE) if warped is not None else None
 
 
-def make_instance_id_temporally_consistent(pred_inst, future_flow, matching_threshold=3.0):
-    """pred_inst [1, T, h, w] per-frame instance maps, future_flow [1, T, 2, h, w] -> [1, T, h, w] with ids that follow the
-    instances through time: an instance of frame t+1 inherits the id of the frame-t instance whose flow-displaced centre
-    it is assigned to (Hungarian method) when they are closer than ``matching_threshold``; otherwise it gets a new id."""
-    assert pred_inst.shape[0] == 1, "Assumes batch size = 1"
-    runtime.require_cuda(pred_inst, future_flow)
-    frames = pred_inst[0]
-    T = frames.shape[0]
-    counts, centres, displaced = instance_moments(frames, future_flow[0])
-    K = counts.shape[1]
-    tables = np.tile(np.arange(K, dtype=np.int64), (T, 1))      # tables[t][raw id] = consistent id; frame 0 keeps its ids
+def _consistent_tables(counts, centres, anchors, matching_threshold):
+    """The frame-to-frame matching of ONE sample, on the host.  counts [T, K] pixels of each raw id, centres [T, K, 2] of the
+    raw instances, anchors [T, K, 2] the frame-t positions that the centres of frame t+1 are matched against (the
+    flow-displaced centres for the regular matcher, the plain centres for the short-interval one) -> tables [T, K] int64,
+    tables[t][raw id] = consistent id.  An instance of frame t+1 inherits the id of the frame-t instance it is assigned to
+    (Hungarian method) when they are closer than ``matching_threshold``; otherwise it gets a new id."""
+    T, K = counts.shape
+    tables = np.tile(np.arange(K, dtype=np.int64), (T, 1))      # frame 0 keeps its ids
     next_new = int(np.flatnonzero(counts[0]).max(initial=0))      # largest id of the first frame
     for t in range(T - 1):
         raw_prev = np.flatnonzero(counts[t][1:]) + 1
@@ -133,7 +184,7 @@ def make_instance_id_temporally_consistent(pred_inst, future_flow, matching_thre
         raw_prev = raw_prev[order]
         carried = tables[t][raw_prev]
         n_next = int(raw_next.max())                              # raw ids are consecutive 1..n_next
-        gap = np.linalg.norm(centres[t + 1, 1:n_next + 1][None, :, :] - displaced[t, raw_prev][:, None, :], axis=-1)
+        gap = np.linalg.norm(centres[t + 1, 1:n_next + 1][None, :, :] - anchors[t, raw_prev][:, None, :], axis=-1)
         rows, cols = linear_sum_assignment(gap)
         close = gap[rows, cols] < matching_threshold
         table = tables[t + 1]
@@ -141,33 +192,89 @@ def make_instance_id_temporally_consistent(pred_inst, future_flow, matching_thre
         unmatched = np.setdiff1d(raw_next, cols[close] + 1)       # ascending
         table[unmatched] = next_new + 1 + np.arange(unmatched.size)
         next_new += int(unmatched.size)
+    return tables
+
+
+def _relabel(frames, tables):
+    """frames [F, h, w] raw ids, tables [F, K] (numpy) -> [F, h, w]: one gather."""
     lut = torch.from_numpy(tables).to(frames.device)
-    return torch.gather(lut, 1, frames.reshape(T, -1).long()).view_as(frames).unsqueeze(0)
+    return torch.gather(lut, 1, frames.reshape(frames.shape[0], -1).long()).view_as(frames)
+
+
+def make_instance_id_temporally_consistent(pred_inst, future_flow, matching_threshold=3.0):
+    """pred_inst [1, T, h, w] per-frame instance maps, future_flow [1, T, 2, h, w] -> [1, T, h, w] with ids that follow the
+    instances through time: an instance of frame t+1 inherits the id of the frame-t instance whose flow-displaced centre
+    it is assigned to (Hungarian method) when they are closer than ``matching_threshold``; otherwise it gets a new id."""
+    assert pred_inst.shape[0] == 1, "Assumes batch size = 1"
+    runtime.require_cuda(pred_inst, future_flow)
+    frames = pred_inst[0]
+    counts, centres, displaced = instance_moments(frames, future_flow[0])
+    return _relabel(frames, _consistent_tables(counts, centres, displaced, matching_threshold)).unsqueeze(0)
+
+
+def make_instance_id_temporally_consistent_short_interval(pred_inst, future_flow=None, matching_threshold=10.0):
+    """The matcher of the streaming evaluator: as ``make_instance_id_temporally_consistent``, but ``future_flow`` is
+    ignored — an instance of frame t+1 is matched against the plain centres of the frame-t instances — and matches up
+    to 10 pixels are accepted."""
+    assert pred_inst.shape[0] == 1, "Assumes batch size = 1"
+    runtime.require_cuda(pred_inst)
+    frames = pred_inst[0]
+    counts, centres, _ = instance_moments(frames)
+    return _relabel(frames, _consistent_tables(counts, centres, centres, matching_threshold)).unsqueeze(0)
+
+
+def _predict(output, compute_matched_centers, make_consistent, vehicles_id, short_interval):
+    """Both ``predict_*`` functions: the sequence kernels on all B*T frames, one moments launch and host copy, the host
+    matching per sample, one gather."""
+    vehicles = output["segmentation"].detach().argmax(dim=2) == vehicles_id
+    B, T, H, W = vehicles.shape
+    cap = MAX_N_INSTANCE_CENTERS                                    # the reference calls with the default
+    raw = instance_segmentation_sequence(output["instance_center"].detach().reshape(B * T, H, W),
+                                         output["instance_offset"].detach().reshape(B * T, 2, H, W), vehicles.reshape(B * T, H, W),
+                                         max_n_instance_centers=cap)
+    if make_consistent and output["instance_flow"] is None:
+        output["instance_flow"] = torch.zeros_like(output["instance_offset"])
+    if not make_consistent and not compute_matched_centers:
+        return raw.view(B, T, H, W)
+    flow = output["instance_flow"].detach().reshape(B * T, 2, H, W) if make_consistent and not short_interval else None
+    counts, sums, warped = _moments_to_host(raw, flow, cap)        # raw ids are <= cap by construction
+    if make_consistent:
+        centres = _means(counts, sums)
+        anchors = centres if short_interval else _means(counts, warped, MOMENT_SCALE)
+        thr = 10.0 if short_interval else 3.0
+        tables = np.concatenate([_consistent_tables(counts[b * T:(b + 1) * T], centres[b * T:(b + 1) * T], anchors[b * T:(b + 1) * T], thr)
+                                 for b in range(B)])
+        tracked = _relabel(raw, tables).view(B, T, H, W)
+    else:
+        tables = np.tile(np.arange(cap + 1, dtype=np.int64), (B * T, 1))
+        tracked = raw.view(B, T, H, W)
+    if not compute_matched_centers:
+        return tracked
+    assert B == 1
+    # moments of the consistent ids from those of the raw ids (integer sums: exact)
+    top = int(tables.max())
+    t_idx = np.repeat(np.arange(T), cap + 1)
+    c_cnt = np.zeros((T, top + 1), dtype=np.int64)
+    c_sum = np.zeros((T, top + 1, 2), dtype=np.int64)
+    np.add.at(c_cnt, (t_idx, tables.ravel()), counts.ravel())
+    np.add.at(c_sum, (t_idx, tables.ravel()), sums.reshape(-1, 2))
+    centres = _means(c_cnt, c_sum)
+    tracks = {}
+    for ident in (np.flatnonzero(c_cnt[0][1:]) + 1).tolist():       # the instances of the first frame, wherever they reappear
+        seen = c_cnt[:, ident] > 0
+        tracks[ident] = centres[seen, ident][:, ::-1]               # (row, col) -> (x, y)
+    return tracked, tracks
 
 
 def predict_instance_segmentation_and_trajectories(output, compute_matched_centers=False, make_consistent=True, vehicles_id=1):
     """Decoder output dict (``segmentation`` [b, T, classes, H, W], ``instance_center`` [b, T, 1, H, W], ``instance_offset`` and
     ``instance_flow`` [b, T, 2, H, W]) -> [b, T, H, W] int64 instance ids (+ {id: [n, 2] (x, y) centre track} of the
     instances of the first frame when ``compute_matched_centers``, batch size 1)."""
-    labels = output["segmentation"].detach().argmax(dim=2)
-    vehicles = labels == vehicles_id
-    B, T = labels.shape[:2]
-    centre_maps, offsets = output["instance_center"].detach(), output["instance_offset"].detach()
-    per_frame = torch.stack([torch.stack([get_instance_segmentation_and_centers(centre_maps[b, t], offsets[b, t], vehicles[b, t])[0][0]
-                                          for t in range(T)]) for b in range(B)])
-    if make_consistent:
-        if output["instance_flow"] is None:
-            output["instance_flow"] = torch.zeros_like(output["instance_offset"])
-        flow = output["instance_flow"].detach()
-        tracked = torch.cat([make_instance_id_temporally_consistent(per_frame[b:b + 1], flow[b:b + 1]) for b in range(B)])
-    else:
-        tracked = per_frame
-    if not compute_matched_centers:
-        return tracked
-    assert B == 1
-    counts, centres, _ = instance_moments(tracked[0])
-    tracks = {}
-    for ident in (np.flatnonzero(counts[0][1:]) + 1).tolist():      # the instances of the first frame, wherever they reappear
-        seen = counts[:, ident] > 0
-        tracks[ident] = centres[seen, ident][:, ::-1]               # (row, col) -> (x, y)
-    return tracked, tracks
+    return _predict(output, compute_matched_centers, make_consistent, vehicles_id, short_interval=False)
+
+
+def predict_instance_segmentation_and_trajectories_short_interval(output, compute_matched_centers=False, make_consistent=True,
+                                                                  vehicles_id=1):
+    """``predict_instance_segmentation_and_trajectories`` with the short-interval matcher (the streaming evaluator's
+    post-processing): the flow is not used; a missing ``instance_flow`` is still replaced by zeros in the dict."""
+    return _predict(output, compute_matched_centers, make_consistent, vehicles_id, short_interval=True)
