@@ -524,7 +524,26 @@ int sf_sparse_to_dense_fwd(const float* feats, const int32_t* coords, int n, int
  *   pixel starts at 0, as the reference's does) -> instance [F][H][W] int64, every id <= cap.  Enqueues only: no allocation,
  *   no synchronisation, nothing read back.  SF_ERR_INVALID: a NULL pointer, F / H / W / cap < 1, F*H*W or F*(cap+1) >= 2^31,
  *   or F * ceil(H*W / 256) * 256 >= 2^32 (the grouping launch pads each frame to whole workgroups of 256 pixels);
- *   SF_ERR_WORKSPACE: ws_bytes < sf_instance_seq_ws_bytes(F, H, W, cap) (exactly that size is enough; 0 for invalid sizes). */
+ *   SF_ERR_WORKSPACE: ws_bytes < sf_instance_seq_ws_bytes(F, H, W, cap) (exactly that size is enough; 0 for invalid sizes).
+ * sf_instance_labels_fwd — convert_instance_mask_to_center_and_offset_label (instance.py:12-77) for B sequences of T frames,
+ *   all F = B*T frames at once: instance [F][H][W] int64 ids, theta [F][6] the row-major 2x3 sampling matrix each frame is
+ *   resampled with (nearest neighbour, as sf_warp_affine_fwd does it; frame t of a sequence takes the inverse of ego-motion t-1,
+ *   frame 0 is never looked at warped and may take the identity), K = num_instances: ids outside 1..K are background.
+ *   Launch 1, moments: per (frame, id) the pixel count and the integer (row, col) sums of the frame as it is and of the frame as
+ *   resampled — looked up destination pixel by destination pixel, with the coordinate arithmetic of sf_warp_affine_fwd bit for
+ *   bit; no warped map is stored.  Integer atomics only.  A centre is round_half_even(fp32(sum) / fp32(count)) per axis: what
+ *   x[mask].mean().round() gives while the sums stay below 2^24, i.e. on every grid up to 256 x 256 (beyond that fp32(sum) is a
+ *   rounded value here and the order of torch's summation matters there).
+ *   Launch 2, labels: center [F][1][H][W] = exp(-min_k d_k^2 / sigma^2) over the instances present in the frame (d^2 the exact
+ *   integer squared distance to centre k, one fp32 division and one expf; 0 in a frame without instances), offset [F][2][H][W]
+ *   = centre - pixel of the pixel's own instance, flow [F][2][H][W] = warped centre in frame t+1 - centre in frame t on the
+ *   pixels of an instance that is present in t and t+1 and whose warped mask in t+1 is not empty; ignore_index elsewhere.
+ *   Workspace, n = F*(K+1) slots, slot = frame*(K+1) + id, every part on a multiple of 256 bytes, zero-filled here:
+ *     plain counts int32 [n] | plain sums int64 [n][2] | warped counts int32 [n] | warped sums int64 [n][2].
+ *   Enqueues one memset and two launches, whatever B, T and K: no allocation, no synchronisation, nothing read back.
+ *   SF_ERR_INVALID: a NULL pointer, B / T / H / W < 1, K < 0 or >= 2^24, H or W > 32768, sigma not > 0, F*H*W or F*(K+1) >= 2^31,
+ *   or F * ceil(H*W / 256) * 256 >= 2^32; SF_ERR_WORKSPACE: ws_bytes < sf_instance_labels_ws_bytes(B, T, H, W, K) (0 for
+ *   invalid sizes). */
 /* sf_warp_affine_fwd — warp_features (utils/geometry.py:196-236): F.affine_grid(theta [B][2][3], align_corners=False)
  *   + F.grid_sample(mode nearest | bilinear, padding zeros, align_corners=False) on NCHW maps x [B][C][H][W]. */
 int sf_warp_affine_fwd(const float* x, const float* theta, int B, int C, int H, int W, int bilinear, float* out,
@@ -543,6 +562,9 @@ size_t sf_instance_seq_ws_bytes(int F, int H, int W, int cap);
 int sf_instance_seq_fwd(const float* center, const float* offsets, const uint8_t* foreground, int F, int H, int W,
                         float conf_threshold, int cap, int32_t* centers, int32_t* n_centers, int64_t* instance, void* ws,
                         size_t ws_bytes, void* stream);
+size_t sf_instance_labels_ws_bytes(int B, int T, int H, int W, int num_instances);
+int sf_instance_labels_fwd(const int64_t* instance, const float* theta, int B, int T, int H, int W, int num_instances, double sigma,
+                           float ignore_index, float* center, float* offset, float* flow, void* ws, size_t ws_bytes, void* stream);
 
 /* hipGraph capture of whatever the caller enqueues between begin and end on `stream` (must not be
  * the legacy default stream). */

@@ -12,8 +12,12 @@
 //   sf_confusion_frames_fwd   the joint histogram per frame of a whole label sequence in one launch
 //   sf_instance_seq_fwd       centres, grouping and consecutive ids (get_instance_segmentation_and_centers, instance.py:119-144)
 //                             of a whole sequence of frames: a fixed number of launches, nothing read back by the host
+//   sf_instance_labels_fwd    convert_instance_mask_to_center_and_offset_label (instance.py:12-77): centerness, centre offsets and
+//                             future displacements of B sequences of T instance maps: one moments launch (plain + ego-warped), one
+//                             label launch, nothing read back by the host
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <cstdint>
 #include <cstring>
 
@@ -248,6 +252,19 @@ __global__ void seq_relabel_kernel(const int* __restrict__ lut, int cap, long pl
 //   base grid   x_j = (2j + 1)/W - 1,  y_i = (2i + 1)/H - 1
 //   source      gx = t0*x + t1*y + t2, gy = t3*x + t4*y + t5;  ix = ((gx + 1)*W - 1)/2, iy likewise
 //   nearest     index = nearbyint(ix) (ties to even), zero when outside; bilinear: 4 taps, zeros outside
+// The source position (in pixels) of destination pixel (i, j) under the 2x3 matrix t: the ONE statement of this arithmetic, shared by
+// warp_affine_kernel and the warped half of instance_label_moments_kernel, which must pick the same source pixel bit for bit.
+// Which multiply-adds are fused is therefore written out and the compiler's own contraction is off in here (left to it, the same
+// expression came out fused in one kernel and unfused in the other); the fused ones are those warp_affine_kernel has always run.
+__device__ __forceinline__ void warp_source(const float* __restrict__ t, int i, int j, int H, int W, float& ix, float& iy) {
+#pragma clang fp contract(off)
+  const float xs = (2.f * j + 1.f) / (float)W - 1.f, ys = (2.f * i + 1.f) / (float)H - 1.f;      // 2j + 1 is exact either way
+  const float gx = fmaf(t[0], xs, t[1] * ys) + t[2];
+  const float gy = fmaf(t[3], xs, t[4] * ys) + t[5];
+  ix = fmaf(gx + 1.f, (float)W, -1.f) * 0.5f;
+  iy = fmaf(gy + 1.f, (float)H, -1.f) * 0.5f;
+}
+
 __global__ void warp_affine_kernel(const float* __restrict__ x, const float* __restrict__ theta, int B, int C, int H, int W, int bilinear,
                                    float* __restrict__ out) {
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -255,11 +272,8 @@ __global__ void warp_affine_kernel(const float* __restrict__ x, const float* __r
   const int j = (int)(idx % W);
   const long r = idx / W;
   const int i = (int)(r % H), b = (int)(r / H);
-  const float* t = theta + 6 * b;
-  const float xs = (2.f * j + 1.f) / (float)W - 1.f, ys = (2.f * i + 1.f) / (float)H - 1.f;
-  const float gx = __fadd_rn(__fadd_rn(__fmul_rn(t[0], xs), __fmul_rn(t[1], ys)), t[2]);
-  const float gy = __fadd_rn(__fadd_rn(__fmul_rn(t[3], xs), __fmul_rn(t[4], ys)), t[5]);
-  const float ix = ((gx + 1.f) * (float)W - 1.f) * 0.5f, iy = ((gy + 1.f) * (float)H - 1.f) * 0.5f;
+  float ix, iy;
+  warp_source(theta + 6 * b, i, j, H, W, ix, iy);
   const size_t plane = (size_t)H * W;
   const float* xb = x + (size_t)b * C * plane;
   float* ob = out + (size_t)b * C * plane + (size_t)i * W + j;
@@ -283,6 +297,119 @@ __global__ void warp_affine_kernel(const float* __restrict__ x, const float* __r
     if (in(y1, x1)) v += pc[(size_t)y1 * W + x1] * (wx1 * wy1);
     ob[c * plane] = v;
   }
+}
+
+// ---- ground-truth labels from instance maps (sf_instance_labels_fwd): convert_instance_mask_to_center_and_offset_label ---------
+// Pass 1.  Per (frame, id in 1..K): pixel count and integer sums of (row, col), of the frame as it is ("plain") and of the frame
+// resampled by theta[f] with nearest-neighbour sampling ("warped").  The warped half never writes a warped map: a thread owns
+// DESTINATION pixel (i, j), looks its source pixel up exactly as warp_affine_kernel's nearest branch does (warp_source, then
+// nearbyint and the range test) and adds (i, j) to the moments of the id it finds there.  Integer atomics only (the sums do not
+// depend on the arrival order); ids outside 1..K are background and issue none.
+__global__ void instance_label_moments_kernel(const long long* __restrict__ inst, const float* __restrict__ theta, int F, int H, int W, int K,
+                                              int* __restrict__ cnt, unsigned long long* __restrict__ pos, int* __restrict__ wcnt,
+                                              unsigned long long* __restrict__ wpos) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long plane = (long)H * W;
+  if (idx >= F * plane) return;
+  const int f = (int)(idx / plane);
+  const int pix = (int)(idx - f * plane);
+  const int i = pix / W, j = pix - i * W;
+  const long long* frame = inst + (size_t)f * plane;
+  const size_t row = (size_t)f * ((size_t)K + 1);
+  const long long id = frame[pix];
+  if (id >= 1 && id <= K) {
+    atomicAdd(pos + 2 * (row + id), (unsigned long long)i);
+    atomicAdd(pos + 2 * (row + id) + 1, (unsigned long long)j);
+    atomicAdd(cnt + row + id, 1);
+  }
+  float ix, iy;
+  warp_source(theta + 6 * (size_t)f, i, j, H, W, ix, iy);
+  const float fx = nearbyintf(ix), fy = nearbyintf(iy);
+  const bool ok = fx >= 0.f && fx < (float)W && fy >= 0.f && fy < (float)H;
+  if (!ok) return;                                                    // zeros padding: background
+  const long long wid = frame[(size_t)((int)fy) * W + (int)fx];
+  if (wid >= 1 && wid <= K) {
+    atomicAdd(wpos + 2 * (row + wid), (unsigned long long)i);
+    atomicAdd(wpos + 2 * (row + wid) + 1, (unsigned long long)j);
+    atomicAdd(wcnt + row + wid, 1);
+  }
+}
+
+// x[mask].mean().round() of the reference: the fp32 sum of integer coordinates is exact while it stays below 2^24 (every grid
+// up to 256 x 256), one fp32 division, round half to even.
+__device__ __forceinline__ float moment_centre(unsigned long long sum, int count) { return rintf(__fdiv_rn((float)sum, (float)count)); }
+
+// Pass 2.  A workgroup serves 256 pixels of ONE frame.  It builds the frame's instance table in LDS from the moments, LABEL_CHUNK
+// ids at a time (K is not bounded by LDS): presence, centre, and — when the instance is also in the next frame of its sequence and
+// its warped mask there is not empty — the displacement warped centre(t + 1) - centre(t).  Every thread then walks the chunk with
+// the same index (LDS broadcasts) for the smallest squared distance to a centre, exact in integers; a pixel whose own id falls
+// into the chunk picks its offset and flow from its entry.  max_k exp(-d_k^2 / sigma^2) = exp(-min_k d_k^2 / sigma^2): one fp32
+// division and one exp per pixel, unfused, on the operands the reference has.
+constexpr int LABEL_CHUNK = 128;
+struct LabelEntry {
+  int present, xc, yc, moves;
+  float dx, dy;
+};
+__global__ void instance_label_kernel(const long long* __restrict__ inst, const int* __restrict__ cnt, const unsigned long long* __restrict__ pos,
+                                      const int* __restrict__ wcnt, const unsigned long long* __restrict__ wpos, int T, int H, int W, int K,
+                                      int blocks_per_frame, float sigma_sq, float ignore, float* __restrict__ center, float* __restrict__ offset,
+                                      float* __restrict__ flow) {
+  __shared__ LabelEntry tab[LABEL_CHUNK];
+  const int f = blockIdx.x / blocks_per_frame;
+  const int plane = H * W;
+  const int pix = (blockIdx.x - f * blocks_per_frame) * blockDim.x + threadIdx.x;
+  const bool live = pix < plane;
+  const int i = pix / W, j = pix - i * W;
+  const bool has_next = (f % T) < T - 1;                              // frame f + 1 belongs to the same sequence
+  const size_t row = (size_t)f * ((size_t)K + 1), next = row + (size_t)K + 1;
+  const long long own = live ? inst[(size_t)f * plane + pix] : 0LL;
+  int best = INT_MAX;
+  bool any = false;
+  float ox = ignore, oy = ignore, fx = ignore, fy = ignore;
+  for (int k0 = 0; k0 < K; k0 += LABEL_CHUNK) {                       // K is uniform over the workgroup: every thread reaches the barriers
+    const int m = min(LABEL_CHUNK, K - k0);
+    __syncthreads();
+    if ((int)threadIdx.x < m) {
+      const size_t id = (size_t)k0 + 1 + threadIdx.x;
+      LabelEntry e = {0, 0, 0, 0, 0.f, 0.f};
+      const int n = cnt[row + id];
+      if (n > 0) {
+        e.present = 1;
+        e.xc = (int)moment_centre(pos[2 * (row + id)], n);
+        e.yc = (int)moment_centre(pos[2 * (row + id) + 1], n);
+        if (has_next && cnt[next + id] > 0) {
+          const int wn = wcnt[next + id];
+          if (wn > 0) {
+            e.moves = 1;
+            e.dx = __fsub_rn(moment_centre(wpos[2 * (next + id)], wn), (float)e.xc);
+            e.dy = __fsub_rn(moment_centre(wpos[2 * (next + id) + 1], wn), (float)e.yc);
+          }
+        }
+      }
+      tab[threadIdx.x] = e;
+    }
+    __syncthreads();
+    for (int k = 0; k < m; ++k) {
+      if (!tab[k].present) continue;                                  // uniform: no lane diverges here
+      const int dx = tab[k].xc - i, dy = tab[k].yc - j;
+      best = min(best, dx * dx + dy * dy);
+      any = true;
+    }
+    const long long mine = own - 1 - k0;
+    if (mine >= 0 && mine < m) {                                      // the pixel itself makes its instance present
+      const LabelEntry e = tab[(int)mine];
+      ox = (float)(e.xc - i);
+      oy = (float)(e.yc - j);
+      if (e.moves) { fx = e.dx; fy = e.dy; }
+    }
+  }
+  if (!live) return;
+  const size_t o1 = (size_t)f * plane + pix, o2 = (size_t)f * 2 * plane + pix;
+  center[o1] = any ? expf(-__fdiv_rn((float)best, sigma_sq)) : 0.f;
+  offset[o2] = ox;
+  offset[o2 + plane] = oy;
+  flow[o2] = fx;
+  flow[o2 + plane] = fy;
 }
 
 inline size_t a256e(size_t n) { return (n + 255) & ~size_t(255); }
@@ -396,6 +523,55 @@ int sf_instance_seq_fwd(const float* center, const float* offsets, const uint8_t
                      H, W, bpf, reinterpret_cast<long long*>(instance), present);
   hipLaunchKernelGGL(seq_lut_kernel, dim3((unsigned)F), block, 0, st, present, cap, lut);
   hipLaunchKernelGGL(seq_relabel_kernel, grid, block, 0, st, lut, cap, (long)H * W, (long)n, reinterpret_cast<long long*>(instance));
+  return hipGetLastError() == hipSuccess ? SF_OK : SF_ERR_LAUNCH;
+}
+
+// workspace of sf_instance_labels_fwd, F = B*T frames, n = F * (K + 1) slots (slot = frame * (K + 1) + id; the slots of id 0 stay zero),
+// every part starting on a multiple of 256 bytes:
+//   plain counts  int32 [n] | plain (row, col) sums  int64 [n][2] | warped counts  int32 [n] | warped (row, col) sums  int64 [n][2]
+struct LabelLayout {
+  size_t n, ac, as, total;      // slots, bytes of a count part, bytes of a sum part
+  int F, bpf;                   // frames, workgroups of 256 pixels per frame
+};
+static bool label_layout(int B, int T, int H, int W, int K, LabelLayout* L) {
+  if (B < 1 || T < 1 || H < 1 || W < 1 || K < 0 || K >= (1 << 24) || H > 32768 || W > 32768) return false;
+  const size_t frames = (size_t)B * T;
+  L->n = frames * ((size_t)K + 1);
+  if (frames * H * W >= (size_t(1) << 31) || L->n >= (size_t(1) << 31)) return false;
+  L->F = (int)frames;
+  L->bpf = (int)(((size_t)H * W + 255) / 256);
+  if (frames * L->bpf * 256 >= (size_t(1) << 32)) return false;      // the label launch pads every frame to whole workgroups
+  L->ac = a256e(L->n * sizeof(int32_t));
+  L->as = a256e(L->n * 2 * sizeof(int64_t));
+  L->total = 2 * (L->ac + L->as);
+  return true;
+}
+
+size_t sf_instance_labels_ws_bytes(int B, int T, int H, int W, int num_instances) {
+  LabelLayout L;
+  return label_layout(B, T, H, W, num_instances, &L) ? L.total : 0;
+}
+
+int sf_instance_labels_fwd(const int64_t* instance, const float* theta, int B, int T, int H, int W, int num_instances, double sigma,
+                           float ignore_index, float* center, float* offset, float* flow, void* ws, size_t ws_bytes, void* stream) {
+  LabelLayout L;
+  if (!instance || !theta || !center || !offset || !flow || !ws || !(sigma > 0.0) || !label_layout(B, T, H, W, num_instances, &L))
+    return SF_ERR_INVALID;
+  if (ws_bytes < L.total) return SF_ERR_WORKSPACE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  char* p = static_cast<char*>(ws);
+  int* cnt = reinterpret_cast<int*>(p);
+  unsigned long long* pos = reinterpret_cast<unsigned long long*>(p + L.ac);
+  int* wcnt = reinterpret_cast<int*>(p + L.ac + L.as);
+  unsigned long long* wpos = reinterpret_cast<unsigned long long*>(p + 2 * L.ac + L.as);
+  if (hipMemsetAsync(ws, 0, L.total, st) != hipSuccess) return SF_ERR_LAUNCH;
+  const long long* ids = reinterpret_cast<const long long*>(instance);
+  const size_t pixels = (size_t)L.F * H * W;
+  hipLaunchKernelGGL(instance_label_moments_kernel, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, st, ids, theta, L.F, H, W,
+                     num_instances, cnt, pos, wcnt, wpos);
+  // sigma ** 2 of the reference is a Python number (double) that torch divides by in fp32
+  hipLaunchKernelGGL(instance_label_kernel, dim3((unsigned)((size_t)L.F * L.bpf)), dim3(256), 0, st, ids, cnt, pos, wcnt, wpos, T, H, W,
+                     num_instances, L.bpf, (float)(sigma * sigma), ignore_index, center, offset, flow);
   return hipGetLastError() == hipSuccess ? SF_OK : SF_ERR_LAUNCH;
 }
 

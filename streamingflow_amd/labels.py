@@ -10,6 +10,13 @@ shift.  For a sequence the ego-motions are chained as 4x4 matrices first (all sa
 products), each chained matrix is reduced to its (yaw, shift) and turned into one 2x3 sampling matrix, and then ALL
 frames of the sequence are resampled by a single launch of ``sf_warp_affine_fwd`` (affine grid + nearest / bilinear
 sampling, zeros outside, ``align_corners=False``).  CUDA tensors only.
+
+The labels themselves — ``convert_instance_mask_to_center_and_offset_label`` (``streamingflow/utils/instance.py:12-77``,
+called by both data loaders) and its batched form ``instance_labels``: the centerness heat map, the centre offsets and the
+future displacements of B sequences of T instance maps come from ``sf_instance_labels_fwd``, two launches for all B*T
+frames (moments of every instance in the plain and the ego-motion-warped maps, then the per-pixel labels) instead of the
+reference's Python loop over instances x frames.  ``prepare_future_labels`` derives them from ``batch["instance"]`` when
+a batch does not carry them.
 """
 import torch
 
@@ -105,11 +112,78 @@ def cumulative_warp_features_reverse(x, flow, mode="nearest", spatial_extent=Non
     return _warp_sequence(x, chained, {0}, mode, spatial_extent)
 
 
+def _label_moments(ws, frames, num_instances):
+    """The moments ``sf_instance_labels_fwd`` left in its workspace (layout: include/sfnative.h), as copies: counts [F, K + 1]
+    int32 and (row, col) sums [F, K + 1, 2] int64 of the plain maps, then the same of the warped maps."""
+    n = frames * (num_instances + 1)
+    raw = ws.view(torch.uint8)
+    ac, asum = (n * 4 + 255) // 256 * 256, (n * 16 + 255) // 256 * 256
+    out, at = [], 0
+    for _ in range(2):
+        out.append(raw[at:at + n * 4].view(torch.int32).view(frames, num_instances + 1).clone())
+        out.append(raw[at + ac:at + ac + n * 16].view(torch.int64).view(frames, num_instances + 1, 2).clone())
+        at += ac + asum
+    return tuple(out)
+
+
+def instance_labels(instance, future_egomotion, num_instances, ignore_index=255, subtract_egomotion=True, sigma=3, spatial_extent=None,
+                    return_moments=False):
+    """instance [B, T, H, W] integer ids (1..num_instances; anything else is background), future_egomotion [B, T, 6] ->
+    (centerness [B, T, 1, H, W], offset [B, T, 2, H, W], flow [B, T, 2, H, W]) fp32 on the device: per sequence what the
+    reference's ``convert_instance_mask_to_center_and_offset_label`` returns.  Two launches for all B*T frames; nothing is
+    read back.  ``return_moments`` adds the per (frame, id) counts and sums of the plain and the warped maps (``_label_moments``)."""
+    if not subtract_egomotion:
+        raise NotImplementedError("subtract_egomotion=False is a NameError in the reference (instance.py:28): there is nothing to match")
+    if spatial_extent is None:
+        raise ValueError("spatial_extent (half extents of the grid in metres) is needed to warp the instance maps")
+    if instance.dim() != 4 or tuple(future_egomotion.shape) != tuple(instance.shape[:2]) + (6,):
+        raise AssertionError("instance must be [B, T, H, W] and future_egomotion [B, T, 6]")
+    runtime.require_cuda(instance, future_egomotion)
+    B, T, H, W = instance.shape
+    K = int(num_instances)
+    ids = instance.detach().to(torch.int64).contiguous()
+    dev = ids.device
+    # frame t is resampled by the inverse of ego-motion t - 1; frame 0 is never looked at warped: identity
+    poses = torch.zeros((B, T, 6), dtype=torch.float32, device=dev)
+    if T > 1:
+        step = pose_vec2mat(future_egomotion[:, :-1].float()).reshape(B * (T - 1), 4, 4)
+        poses[:, 1:] = mat2pose_vec(invert_pose_matrix(step)).view(B, T - 1, 6)
+    theta = _sampling_matrices(poses.view(B * T, 6), spatial_extent)
+    center = torch.empty((B, T, 1, H, W), dtype=torch.float32, device=dev)
+    offset = torch.empty((B, T, 2, H, W), dtype=torch.float32, device=dev)
+    flow = torch.empty((B, T, 2, H, W), dtype=torch.float32, device=dev)
+    L = _lib.lib()
+    ws = runtime.workspace(L.sf_instance_labels_ws_bytes(B, T, H, W, K), dev)
+    _lib.check(L.sf_instance_labels_fwd(ptr(ids), ptr(theta), B, T, H, W, K, float(sigma), float(ignore_index), ptr(center), ptr(offset),
+                                        ptr(flow), ptr(ws), ws.numel() * 4, runtime.stream_ptr(dev)), "instance_labels")
+    if return_moments:
+        return center, offset, flow, _label_moments(ws, B * T, K)
+    return center, offset, flow
+
+
+def convert_instance_mask_to_center_and_offset_label(instance_img, future_egomotion, num_instances, ignore_index=255,
+                                                     subtract_egomotion=True, sigma=3, spatial_extent=None):
+    """instance_img [T, H, W], future_egomotion [T, 6] -> (centerness [T, 1, H, W], offset [T, 2, H, W], future displacement
+    [T, 2, H, W]): the reference's function of the same name, on the device (``instance_labels`` with B = 1)."""
+    if instance_img.dim() != 3:
+        raise AssertionError("instance_img must be [T, H, W]")
+    c, o, f = instance_labels(instance_img.unsqueeze(0), future_egomotion.unsqueeze(0), num_instances, ignore_index=ignore_index,
+                              subtract_egomotion=subtract_egomotion, sigma=sigma, spatial_extent=spatial_extent)
+    return c[0], o[0], f[0]
+
+
 def prepare_future_labels(batch, cfg, receptive_field, spatial_extent, encoder_downsample=8, is_lyft=False):
     """Every label sequence of a batch in the PRESENT frame (index receptive_field - 1): the past is warped forward, the
-    future backward, and the two halves are joined without repeating the present."""
+    future backward, and the two halves are joined without repeating the present.  A batch without ``centerness``,
+    ``offset`` or ``flow`` gets the missing ones from its ``instance`` maps (``instance_labels``, with the data loaders'
+    arguments: every positive id an instance, cfg.DATASET.IGNORE_INDEX or 255, sigma 3)."""
     rf = receptive_field
     ego = batch["future_egomotion"]
+    needed = (("centerness", "offset") if cfg.INSTANCE_SEG.ENABLED else ()) + (("flow",) if cfg.INSTANCE_FLOW.ENABLED else ())
+    if any(k not in batch for k in needed):
+        ignore = getattr(getattr(cfg, "DATASET", None), "IGNORE_INDEX", 255)
+        made = instance_labels(batch["instance"], ego, max(int(batch["instance"].max().item()), 0), ignore_index=ignore, spatial_extent=spatial_extent)
+        batch = {**dict(zip(("centerness", "offset", "flow"), made)), **batch}
     labels = {}
     if not is_lyft and "gt_trajectory" in batch:
         labels["gt_trajectory"] = batch["gt_trajectory"]
