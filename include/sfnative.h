@@ -606,6 +606,20 @@ int sf_debug_stamps(void* buf);
 /* diagnostic: workgroups per CU the runtime grants the large LDS-DMA tiles with their dynamic LDS
  * (0: 128x128 fp32, 1: 128x128 bf16x3, 2: 64x128 fp32, 3: 64x128 bf16x3); -1 on error */
 int sf_debug_occupancy(int which);
+/* diagnostic, host only (no HIP call, nothing dereferenced beyond *w: w->w / w->w_wino need only be non-NULL): what the conv dispatch will
+ * decide for a launch of `nprob` (1..4) identical problems of packed layer `w` under epilogue family `epi` (0 affine, 1 blend, 2 LayerNorm +
+ * GELU, 4 sampling) on n_img images of Hin x Win (in_up = 1: nearest x2 upsampling on read) — the Winograd plan of dispatch.hip (wino_plan)
+ * under the switches in force.  flags: 1 = SE input scale present, 2 = residual present, 4 = second output present (the reset gate's).
+ * out[0 .. SF_WINO_PLAN_INTS):
+ *   [0] 1: the layer runs on the Winograd kernel (0: it does not, everything else is 0)
+ *   [1] form: 2 plain, 3 dilated, 4 images concatenated along x
+ *   [2] launches (segments): 1, or 2 = main launch + remainder band; 0: nothing is launched for these nprob problems together — a group
+ *       (nprob > 1) cannot share a launch and runs one problem at a time; a single problem (nprob = 1) is beyond what the kernel's block
+ *       decode computes exactly, and the call that asks for it returns SF_ERR_LAUNCH
+ *   [3 + 4 s ..] per segment s: tile rows per block (4: 32-tile blocks, 2: 16-tile blocks), first tile row, tile rows, workgroups
+ *   [11] workgroups of the whole launch on 32-tile blocks (what SF_WINO_SMALL_WGS is compared with) */
+#define SF_WINO_PLAN_INTS 12
+int sf_debug_wino_plan(const sf_conv_w* w, int epi, int n_img, int Hin, int Win, int in_up, int nprob, int flags, int32_t* out, int n_out);
 
 #ifdef __cplusplus
 }

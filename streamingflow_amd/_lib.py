@@ -15,6 +15,7 @@ i32p = C.POINTER(C.c_int32)
 SF_COEF_STRIDE = 12
 SF_ABI_VERSION = 7       # include/sfnative.h: changes whenever a public struct changes layout
 SF_PROF_KEYS = 168
+SF_WINO_PLAN_INTS = 12     # include/sfnative.h: int32 entries sf_debug_wino_plan writes
 PACK_TRANSPOSED, PACK_FOLD_DUP, PACK_INTERLEAVE, PACK_BF16X3, PACK_WINOGRAD = 1, 2, 4, 8, 16      # SF_PACK_* of sfnative.h
 ACT = {"none": 0, "lrelu": 1, "relu": 2, "tanh": 3, "sigmoid": 4, "gelu": 5}
 SOLVER = {"euler": 0, "midpoint": 1, "rk4": 2}
@@ -184,6 +185,7 @@ SIGNATURES = {
     "sf_debug_stamps": (_i, [_vp]),
     "sf_pack_conv_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "sf_debug_occupancy": (_i, [_i]),
+    "sf_debug_wino_plan": (_i, [C.POINTER(ConvW), _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int32), _i]),
     "sf_bn_fold": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_float, _i, _vp, _vp, _vp]),
     "sf_pack_conv": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_float, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, C.POINTER(ConvW), _vp]),
 }

@@ -1200,6 +1200,11 @@ int sf_debug_stamps(void* buf) { return debug_stamps(buf); }
 
 /* diagnostic: workgroups per CU of the large LDS-DMA tiles (0: 128x128 fp32, 1: 128x128 bf16x3, 2: 64x128 fp32, 3: 64x128 bf16x3) */
 int sf_debug_occupancy(int which) { return glds_occupancy(which); }
+/* diagnostic, host only: the Winograd plan of a launch (dispatch.hip: debug_wino_plan) */
+int sf_debug_wino_plan(const sf_conv_w* w, int epi, int n_img, int Hin, int Win, int in_up, int nprob, int flags, int32_t* out, int n_out) {
+  if (!w || !valid_w(*w)) return SF_ERR_INVALID;
+  return debug_wino_plan(*w, epi, n_img, Hin, Win, in_up, nprob, flags, out, n_out);
+}
 
 int sf_prof_enable(int on) {
   prof_enable(on != 0);

@@ -18,7 +18,6 @@
 #include "sf_math.h"
 #include "sf_launch.h"
 
-#include <cstdlib>
 #include <type_traits>
 
 namespace sf {
@@ -31,7 +30,6 @@ hipError_t set_stamp_buffer_wino(unsigned long long*) { return hipErrorNotSuppor
 #endif
 
 constexpr int WN_THREADS = 512;
-constexpr long SF_WINO_SPLIT_WGS_DEFAULT = 512;      // launch_conv_wino: remainder launches from this many workgroups
 typedef __attribute__((address_space(3))) void wn_lds_void;
 
 __device__ __forceinline__ f32x4 wn_lds_read128(const float* p) {
@@ -171,12 +169,12 @@ __device__ __forceinline__ float wn_gelu(float v) { return 0.5f * v * (1.f + spm
 
 // TH_: tile rows of the workgroup's block — 4 (8 x 16 output pixels, 32 tiles: the kernel as measured in DESIGN 4.3) or 2 (4 x 16 pixels, 16
 // tiles, three workgroups per CU: round 6, for launches of fewer than two rounds of the chip's 512 workgroup slots — a single 200x200 frame
-// with 64 / 128 output channels is 313 / 626 workgroups of 32 tiles; launch_conv_wino holds the measured rule)
+// with 64 / 128 output channels is nominally 313 / 626 workgroups of 32 tiles, 328 / 656 as launched; dispatch.hip: wino_plan holds the measured rule)
 template <bool DIL, bool CAT, int TH_ = 4>
 struct Wino5Geo {
   static_assert(!(DIL && CAT), "one run structure at a time");
-  static_assert(TH_ == 4 || (TH_ == 2 && !DIL), "tile rows per block");
-  static constexpr int COUT_T = 64, TH = TH_, TW = 8, WT = TH * TW, NB = WT / 16;
+  static_assert(TH_ == WN_TH || (TH_ == WN_TH_SMALL && !DIL), "tile rows per block");
+  static constexpr int COUT_T = WN_COUT_T, TH = TH_, TW = WN_TW, WT = TH * TW, NB = WT / 16;      // (sf_launch.h: the planner counts blocks by them)
   static constexpr int RY = 2, RX = 4;
   static constexpr int PH = 2 * TH + (DIL ? 2 * RY : 2), PW = 2 * TW + (DIL ? 2 * RX : (CAT ? 4 : 2));
   static constexpr int NPX = PH * PW;
@@ -522,9 +520,10 @@ __global__ __launch_bounds__(WN_THREADS, TH_ == 2 ? 6 : 4) void conv_wino5_kerne
   };
   // ---- prologue -----------------------------------------------------------------------------------------------------------------------------
   float scv = 1.f;
-  if constexpr (SCALED)
+  if constexpr (SCALED) {
     if (scaled && tid < c0) scv = PX.in_scale[(size_t)img * c0 + tid];
     if (CAT_SC && scaled && tid >= c0 && tid < 2 * c0 && img + 1 < P.n_img) scv = PX.in_scale[(size_t)(img + 1) * c0 + (tid - c0)];
+  }
   issue_patch(0);
   f32x4 A[2][2];                                                // [ring slot = step & 1][mb]
   A[0][0] = load_A(0, 0); A[0][1] = load_A(0, 1);
@@ -908,21 +907,17 @@ hipError_t launch_wino_weights(const float* w, float* U, int cout_pad, int cin_p
   return hipGetLastError();
 }
 
-// what the kernel takes: 3x3, stride 1, pad 1, no dilation / upsampling / gather / gate / SE scale / split-K / channel sums; inputs
-// in whole 16-channel chunks; transformed weights present; images of at least one workgroup tile
+// what the kernel can address: 3x3, stride 1, pad 1, no dilation / upsampling / gather / gate / SE scale / split-K / channel sums; inputs
+// in whole 16-channel chunks; transformed weights present; images of at least one workgroup tile.  (Shapes, operand combinations and 32-bit
+// offsets only: which of these layers the dispatcher WANTS here — its on / off switches and size thresholds — is dispatch.hip: wino_runs.)
 // EPI_LNG (round 6): the 7x7 / pad-3 + LayerNorm + GELU layer of the batched cells as nine 3x3 tap groups (GRP = 9): 64 output channels = one
 // cout block (the LayerNorm needs a pixel's channels in one workgroup), LayerNorm on, plain inputs, [+ residual]
 static bool wino_takes_ln7(const ConvProblem& q) {
-  static const int on = [] { const char* v = std::getenv("SF_WINO_LN7"); return v ? std::atoi(v) : 1; }();
-  if (!on || !q.w_wino || q.KH != 7 || q.KW != 7 || q.stride != 1 || q.dil != 1 || q.pad != 3 || q.in_up || q.gather || q.gate || q.se_sum || q.in_scale ||
+  if (!q.w_wino || q.KH != 7 || q.KW != 7 || q.stride != 1 || q.dil != 1 || q.pad != 3 || q.in_up || q.gather || q.gate || q.se_sum || q.in_scale ||
       q.nsplit > 1 || q.chansum || q.acc_in || q.fuse_w || q.out_planar || q.pool2 || q.add_up || q.add_scale || q.bias_per_img || q.out2)
     return false;
   if (q.cout != 64 || q.cout_pad != 64 || (q.c0 % 16) || (q.c1 % 16) || q.c0 + q.c1 != q.cin_pad || (q.cin_pad % 32)) return false;
   if (q.Hout != q.Hin || q.Wout != q.Win || q.Hout < 16 || q.Wout < 32) return false;
-  // one cout block and 9 x cin/16 chunks per workgroup: the launch needs a full round of workgroups (2 x 256 blocks of 32 tiles = 65536 pixels) to
-  // pay — 8 latents of 50x50 are 175 workgroups of ~200 us each and LOSE to the direct form (batch-8 step 549 -> 563 us, profiles/r06_ln7_ab.txt)
-  static const double min_p = [] { const char* v = std::getenv("SF_WINO_LN7_MIN_P"); return v ? std::atof(v) : 65536.0; }();
-  if ((double)q.n_img * q.Hout * q.Wout < min_p) return false;
   const double img_bytes = 4.0 * q.Hin * q.Win;
   if (img_bytes * q.out_cs >= 2147483648.0 || img_bytes * q.add_cs >= 2147483648.0 || img_bytes * q.in0_cs >= 2147483648.0 ||
       img_bytes * q.in1_cs >= 2147483648.0 || 4.0 * 9 * 16 * q.cout_pad * q.cin_pad >= 2147483648.0)
@@ -932,9 +927,8 @@ static bool wino_takes_ln7(const ConvProblem& q) {
 bool wino_takes(const ConvProblem& q, int epi) {
   if (epi == EPI_LNG) return wino_takes_ln7(q);
   if (epi == EPI_SAMPLE) {      // the sampling layer of the batched infer_state (round 6): the plain AFFINE rules + what its epilogue addresses
-    static const int on = [] { const char* v = std::getenv("SF_WINO_SAMPLE"); return v ? std::atoi(v) : 1; }();
     const double img_px = (double)q.Hin * q.Win;
-    if (!on || q.dil != 1 || q.in_up || q.add || q.add_scale || q.pool2 || q.add_up || q.bias_per_img || q.scale || (q.cout % 8) || (q.c1 != 0) ||
+    if (q.dil != 1 || q.in_up || q.add || q.add_scale || q.pool2 || q.add_up || q.bias_per_img || q.scale || (q.cout % 8) || (q.c1 != 0) ||
         2.0 * 4.0 * img_px * q.cout >= 2147483648.0 || (!q.e0 && !q.philox))
       return false;
     return wino_takes(q, EPI_AFFINE);      // (out2 here is the q tensor: no gate_from semantics — the kernel's SAMPLE branch never reads it as a gate)
@@ -958,88 +952,19 @@ bool wino_takes(const ConvProblem& q, int epi) {
   if (img_bytes * q.in0_cs >= 2147483648.0 || img_bytes * q.in1_cs >= 2147483648.0 || 4.0 * 16 * q.cout_pad * q.cin_pad >= 2147483648.0) return false;
   return true;
 }
-
-// CAT pays where blocks of 8 tile columns fit the image badly and no epilogue operand is per image (SF_WINO_CAT=0: never)
-static bool wino_cat(const ConvProblem& q) {
-  static const int on = [] { const char* v = std::getenv("SF_WINO_CAT"); return v ? std::atoi(v) : 1; }();
-  const int tpi = (q.Wout + 1) / 2;
-  static const int cat_scaled = [] { const char* v = std::getenv("SF_WINO_CAT_SCALED"); return v ? std::atoi(v) : 1; }();      // round 6: SE scales of both images of a block
-  if (!on || q.dil != 1 || q.in_up || q.n_img < 2 || tpi < 8 || q.bias_per_img || ((q.in_scale || q.add_scale) && !cat_scaled)) return false;
-  const int plain = (tpi + 7) / 8 * 8;
-  // less than 10 % empty columns: the plain form, whose patch is two columns narrower — except at 128 or more output channels and at
-  // least 4 % empty columns (100 tile columns run 104: the 200x200 gates and 128 -> 128 layers), where CAT measured 1.7 - 2.8 % faster and
-  // the 64-channel layers within +-1 % (SF_WINO_CAT_WIDE=0: the 10 % rule alone.  Read at every such launch: tests compare both)
-  if (plain * 100 < tpi * 110) {
-    if (q.cout_pad < 128 || plain * 100 < tpi * 104) return false;
-    const char* const v = std::getenv("SF_WINO_CAT_WIDE");
-    if (v && std::atoi(v) == 0) return false;
-  }
-  const double img_bytes = 4.0 * q.Hin * q.Win;
-  const int cs = q.in0_cs > q.in1_cs ? q.in0_cs : q.in1_cs;
-  const int co = q.out_cs > q.add_cs ? q.out_cs : q.add_cs;
-  const int ce = q.e0_cs > q.e1_cs ? q.e0_cs : q.e1_cs;
-  const int cm = co > ce ? (co > q.out2_cs ? co : q.out2_cs) : (ce > q.out2_cs ? ce : q.out2_cs);
-  return 2.0 * img_bytes * cs < 2147483648.0 && 2.0 * img_bytes * cm < 2147483648.0;      // two images behind one base
-}
-// which form of the kernel a problem runs on: 2 = plain, 3 = dilated, 4 = images concatenated along x; -1: none
-int wino_variant(const ConvProblem& q) {
-  if (q.cout_pad % 64) return -1;
-  if (q.dil > 1) return 3;
-  if (wino_cat(q)) return 4;
-  return 2;
+// tile columns / rows of one image as the kernel lists them (dilated: over the d phases of the axis)
+void wino_tile_grid(const ConvProblem& q, int& tiles_x, int& tiles_y) {
+  tiles_x = q.dil > 1 ? WnAxis(q.Wout, q.dil).nt : (q.Wout + 1) / 2;
+  tiles_y = q.dil > 1 ? WnAxis(q.Hout, q.dil).nt : (q.Hout + 1) / 2;
 }
 // Winograd tiles a launch executes (the profiler prices 16 products per tile and (cin, cout) pair)
 double wino_tiles(const ConvProblem& q) {
-  if (q.dil > 1) return (double)q.n_img * WnAxis(q.Hout, q.dil).nt * WnAxis(q.Wout, q.dil).nt;
-  return (double)q.n_img * ((q.Hout + 1) / 2) * ((q.Wout + 1) / 2);
+  int tiles_x, tiles_y;
+  wino_tile_grid(q, tiles_x, tiles_y);
+  return (double)q.n_img * tiles_y * tiles_x;
 }
-// workgroups a launch of the group has over `rows` tile rows of every image with blocks of `th` tile rows (the choice between the two block
-// sizes and the split rule count the window a launch covers, not the layer)
-static long wino5_wgs(const ConvLaunch& L, bool cat, int rows, int th) {
-  const ConvProblem& P = L.p[0];
-  const int tiles_x = (P.Wout + 1) / 2;
-  const long nby = (rows + th - 1) / th;
-  const long blocks = cat ? nby * (((long)P.n_img * tiles_x + 7) / 8) : (long)P.n_img * nby * ((tiles_x + 7) / 8);
-  return ((blocks + 7) / 8) * 8 * (P.cout_pad / 64) * L.nprob;
-}
-template <int EPI, bool DIL = false, bool CAT = false, int TH_ = 4, int GRP = 1>
-static hipError_t launch_wino5_t(const ConvLaunch& L, hipStream_t stream, const int row0 = 0, const int rows = -1) {
-  typedef Wino5Geo<DIL, CAT, TH_> G;
-  auto kern = conv_wino5_kernel<EPI, DIL, CAT, TH_, GRP>;
-  constexpr int lds = G::LDS_FLOATS * 4;
-  static bool attr_done[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-  if (!attr_done[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return e;
-    attr_done[dev] = true;
-  }
-  const ConvProblem& P = L.p[0];
-  const int tiles_x = DIL ? WnAxis(P.Wout, P.dil).nt : (P.Wout + 1) / 2, tiles_all = DIL ? WnAxis(P.Hout, P.dil).nt : (P.Hout + 1) / 2;
-  // the window of tile rows [row0, row0 + rows) (rows < 0: the whole image); a window that does not end with the image is whole blocks
-  const int tiles_y = rows < 0 ? tiles_all : rows;
-  if (row0 < 0 || tiles_y < 1 || row0 + tiles_y > tiles_all || (DIL && tiles_y != tiles_all) || (row0 + tiles_y < tiles_all && tiles_y % G::TH)) return hipErrorInvalidValue;
-  const long blocks = CAT ? (long)((tiles_y + G::TH - 1) / G::TH) * (((long)P.n_img * tiles_x + G::TW - 1) / G::TW)
-                          : (long)P.n_img * ((tiles_y + G::TH - 1) / G::TH) * ((tiles_x + G::TW - 1) / G::TW);
-  const long grid1 = ((blocks + 7) / 8) * 8 * (P.cout_pad / G::COUT_T), grid = grid1 * L.nprob;
-  if (grid > 0x7fffffffL) return hipErrorInvalidValue;
-  ConvLaunch L2 = L;
-  L2.wg_base[0] = 0;
-  L2.wg_base[1] = (int)grid1;
-  L2.wn_ty0 = row0; L2.wn_nty = tiles_y;
-  // reciprocals of the block decode's divisors (conv_wino5_kernel): ceil(2^32 / d), 0 for d = 1; exact while dividend x d < 2^32
-  const long nbx = ((CAT ? (long)P.n_img * tiles_x : tiles_x) + G::TW - 1) / G::TW, nby = (tiles_y + G::TH - 1) / G::TH, ncb = P.cout_pad / G::COUT_T;
-  if ((grid1 / 8 + 1) * ncb >= 0x100000000L || (blocks + 8) * nbx >= 0x100000000L || (blocks + 8) * nby >= 0x100000000L ||
-      (nbx * G::TW + G::TW) * tiles_x >= 0x100000000L)
-    return hipErrorInvalidValue;
-  if (L.nprob > 1 && grid * grid1 >= 0x100000000L) return hipErrorInvalidValue;      // (callers launch such groups one by one)
-  L2.wn_m[0] = L.nprob > 1 ? magic(grid1) : 1u;
-  L2.wn_m[1] = magic(ncb); L2.wn_m[2] = magic(nbx); L2.wn_m[3] = magic(nby); L2.wn_m[4] = magic(tiles_x);
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid, 1, 1), dim3(WN_THREADS), lds, stream, L2);
-  return hipGetLastError();
-}
-// same tiling, same kernel instantiation, same workgroup count: the layers may share a launch
+// same tiling, same workgroup count: the layers may share a launch where the plan also gives them the same form (every field the form is
+// decided by is compared here; dispatch.hip: wino_plan compares the forms it computed)
 bool wino_same_geometry(const ConvProblem& a, const ConvProblem& b) {
   return a.n_img == b.n_img && a.Hin == b.Hin && a.Win == b.Win && a.Hout == b.Hout && a.Wout == b.Wout && a.in_up == b.in_up && a.dil == b.dil &&
          a.c0 == b.c0 && a.c1 == b.c1 && a.cin_pad == b.cin_pad && a.cout == b.cout && a.cout_pad == b.cout_pad &&
@@ -1048,59 +973,43 @@ bool wino_same_geometry(const ConvProblem& a, const ConvProblem& b) {
          (a.bias != nullptr) == (b.bias != nullptr) && a.in0_cs == b.in0_cs && a.in1_cs == b.in1_cs && a.add_cs == b.add_cs && a.out_cs == b.out_cs &&
          a.out_co == b.out_co && a.out2_cs == b.out2_cs && a.e0_cs == b.e0_cs && a.e1_cs == b.e1_cs && a.act == b.act && a.mode == b.mode &&
          a.gate_from == b.gate_from && a.clamp_from == b.clamp_from && a.clamp_lo == b.clamp_lo && a.clamp_hi == b.clamp_hi &&
-         a.bias_per_img == b.bias_per_img && a.pool2 == b.pool2 && a.add_up == b.add_up && wino_variant(a) == wino_variant(b);
+         a.bias_per_img == b.bias_per_img && a.pool2 == b.pool2 && a.add_up == b.add_up;
+}
+
+// ---- the instantiation table.  L arrives planned (dispatch.hip: wino_plan): window of tile rows, workgroups per problem in wg_base[1],
+// reciprocals of the block decode
+template <int EPI, bool DIL = false, bool CAT = false, int TH_ = WN_TH, int GRP = 1>
+static hipError_t launch_wino5_t(const ConvLaunch& L, hipStream_t stream) {
+  auto kern = conv_wino5_kernel<EPI, DIL, CAT, TH_, GRP>;
+  constexpr int lds = Wino5Geo<DIL, CAT, TH_>::LDS_FLOATS * 4;
+  static bool attr_done[64] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
+  if (!attr_done[dev]) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e != hipSuccess) return e;
+    attr_done[dev] = true;
+  }
+  hipLaunchKernelGGL(kern, dim3((unsigned)((long)L.wg_base[1] * L.nprob), 1, 1), dim3(WN_THREADS), lds, stream, L);
+  return hipGetLastError();
 }
 // one problem per launch, or up to SF_MAX_GROUP of identical geometry
-hipError_t launch_conv_wino(const ConvLaunch& L, int epi, hipStream_t stream) {
-  if (L.nprob < 1 || L.nprob > SF_MAX_GROUP) return hipErrorInvalidValue;
-  for (int i = 0; i < L.nprob; ++i)
-    if (!wino_takes(L.p[i], epi) || !wino_same_geometry(L.p[0], L.p[i])) return hipErrorInvalidValue;
-  const bool affine = epi == EPI_AFFINE;
-  const int var = wino_variant(L.p[0]);
-  if (epi == EPI_SAMPLE) {
-    if (var == 2) return launch_wino5_t<EPI_SAMPLE>(L, stream);
-    if (var == 4) return launch_wino5_t<EPI_SAMPLE, false, true>(L, stream);
-    return hipErrorInvalidValue;
+hipError_t launch_conv_wino(const ConvLaunch& L, int epi, WinoForm form, int th, hipStream_t stream) {
+  if (L.nprob < 1 || L.nprob > SF_MAX_GROUP || (th != WN_TH && th != WN_TH_SMALL)) return hipErrorInvalidValue;
+  const bool cat = form == WINO_CAT, small = th == WN_TH_SMALL;
+  if (form != WINO_PLAIN && !cat) return (form == WINO_DIL && epi == EPI_AFFINE && !small) ? launch_wino5_t<EPI_AFFINE, true>(L, stream) : hipErrorInvalidValue;
+  if (small && (epi == EPI_SAMPLE || epi == EPI_LNG || (cat && L.p[0].in_scale))) return hipErrorInvalidValue;      // no 16-tile form
+  switch (epi) {
+    case EPI_SAMPLE: return cat ? launch_wino5_t<EPI_SAMPLE, false, true>(L, stream) : launch_wino5_t<EPI_SAMPLE>(L, stream);
+    case EPI_LNG: return cat ? launch_wino5_t<EPI_LNG, false, true, WN_TH, 9>(L, stream) : launch_wino5_t<EPI_LNG, false, false, WN_TH, 9>(L, stream);
+    case EPI_AFFINE:
+      if (cat) return small ? launch_wino5_t<EPI_AFFINE, false, true, WN_TH_SMALL>(L, stream) : launch_wino5_t<EPI_AFFINE, false, true>(L, stream);
+      return small ? launch_wino5_t<EPI_AFFINE, false, false, WN_TH_SMALL>(L, stream) : launch_wino5_t<EPI_AFFINE>(L, stream);
+    case EPI_BLEND:
+      if (cat) return small ? launch_wino5_t<EPI_BLEND, false, true, WN_TH_SMALL>(L, stream) : launch_wino5_t<EPI_BLEND, false, true>(L, stream);
+      return small ? launch_wino5_t<EPI_BLEND, false, false, WN_TH_SMALL>(L, stream) : launch_wino5_t<EPI_BLEND>(L, stream);
+    default: return hipErrorInvalidValue;
   }
-  if (epi == EPI_LNG) {
-    if (var == 2) return launch_wino5_t<EPI_LNG, false, false, 4, 9>(L, stream);
-    if (var == 4) return launch_wino5_t<EPI_LNG, false, true, 4, 9>(L, stream);
-    return hipErrorInvalidValue;
-  }
-  // 16-tile blocks where 32-tile blocks would leave the launch below SF_WINO_SMALL_WGS workgroups (two rounds of the chip's 512 slots; 0: never).
-  // The 16-tile form runs THREE workgroups per CU (80 registers, 46 KB of LDS), so a launch of 313 / 626 32-tile workgroups becomes 626 / 1252
-  // of 768 slots.  Measured per threshold (profiles/r06_wino16_ab.txt, single-sample forward): BLEND launches 0.608 -> 0.514 ms, AFFINE 2.880 ->
-  // 2.841, forward 7.44 -> 7.27 ms; at two samples per forward 13.18 -> 13.14; above ~1 400 workgroups the 32-tile form wins (every workgroup
-  // loads the whole U of its 64 output channels whatever its tile count: 16 tiles double the load instructions per MFMA)
-  static const long small_wgs = [] { const char* v = std::getenv("SF_WINO_SMALL_WGS"); return v ? std::atol(v) : 1000L; }();
-  if (var == 3) return affine ? launch_wino5_t<EPI_AFFINE, true>(L, stream) : hipErrorInvalidValue;
-  if (var != 2 && var != 4) return hipErrorInvalidValue;
-  const bool cat = var == 4;
-  const bool only32 = cat && L.p[0].in_scale;      // (SE-scaled CAT: 32-tile form only)
-  auto launch = [&](const bool small, const int row0, const int rows) -> hipError_t {
-    if (cat) {
-      if (small) return affine ? launch_wino5_t<EPI_AFFINE, false, true, 2>(L, stream, row0, rows) : launch_wino5_t<EPI_BLEND, false, true, 2>(L, stream, row0, rows);
-      return affine ? launch_wino5_t<EPI_AFFINE, false, true>(L, stream, row0, rows) : launch_wino5_t<EPI_BLEND, false, true>(L, stream, row0, rows);
-    }
-    if (small) return affine ? launch_wino5_t<EPI_AFFINE, false, false, 2>(L, stream, row0, rows) : launch_wino5_t<EPI_BLEND, false, false, 2>(L, stream, row0, rows);
-    return affine ? launch_wino5_t<EPI_AFFINE>(L, stream, row0, rows) : launch_wino5_t<EPI_BLEND>(L, stream, row0, rows);
-  };
-  const int tiles_y = (L.p[0].Hout + 1) / 2;
-  const bool small = !only32 && wino5_wgs(L, cat, tiles_y, 4) < small_wgs;
-  // Vertical remainder band: 25 / 50 tile rows end in a band of four with one / two real rows.  Such a layer runs as two launches: rows
-  // [0, 4 floor(tiles_y / 4)) on 32-tile blocks, the rest on 16-tile blocks (28 -> 26 / 52 -> 50 tile rows executed) — where the remainder
-  // launch has at least SF_WINO_SPLIT_WGS workgroups (default 512; 0: never, the layer stays whole).  Measured: the encoder / decoder
-  // layers of 224 - 256 images (704 - 3 200 remainder workgroups) gain 3 - 6 %, the rollout's 32-image layers (208) nothing: every workgroup loads
-  // the whole U and the launch has one more tail.  The sampling layer, the tap groups and SE-scaled concatenated images
-  // have no 16-tile form and stay whole.  (Read at every launch: tests compare both forms in one process.)
-  const char* const sv = std::getenv("SF_WINO_SPLIT_WGS");
-  const long split_wgs = sv ? std::atol(sv) : SF_WINO_SPLIT_WGS_DEFAULT;
-  const int main_rows = tiles_y & ~3, rem_rows = tiles_y - main_rows;
-  if (!small && !only32 && split_wgs > 0 && rem_rows > 0 && main_rows > 0 && wino5_wgs(L, cat, rem_rows, 2) >= split_wgs) {
-    const hipError_t e = launch(wino5_wgs(L, cat, main_rows, 4) < small_wgs, 0, main_rows);
-    return e != hipSuccess ? e : launch(true, main_rows, rem_rows);
-  }
-  return launch(small, 0, -1);
 }
 
 }  // namespace sf

@@ -28,9 +28,13 @@ struct Arena {
 };
 inline size_t al(size_t n) { return (n + 63) & ~size_t(63); }
 
-// Switches, read once per process from the environment (experiments and A/B aids only; defaults are the shipped choice).  geti is the only
-// reader; isset: a debugging aid that is on when its variable is set at all.
+// Switches, read once per process from the environment (experiments and A/B aids only; defaults are the shipped choice).  geti (atoi) and
+// getl (atol) in dispatch.hip are the only readers of the conv dispatch; isset: a debugging aid that is on when its variable is set at all.
+// Two switches are LIVE — re-read at every Winograd plan (dispatch.hip: wino_live), because tests/test_gpu_wino_split.py flips them inside one
+// process to compare both forms on the same tensors: SF_WINO_SPLIT_WGS (default 512) and SF_WINO_CAT_WIDE (default 1); see wino_plan.
+// Two readers remain in kernel files: SF_XCD_CHUNK (conv_igemm.hip) and SF_DWCONV_PK (aux_kernels.hip).
 int geti(const char* name, int dflt);
+long getl(const char* name, long dflt);
 inline bool isset(const char* name) { return geti(name, INT32_MIN) != INT32_MIN; }
 struct Tune {
   // 1: one latent: the launches of a rollout run as phases of ONE persistent flow kernel per cell boundary (conv_sp.hip: sp_flow_kernel;
@@ -78,6 +82,20 @@ struct Tune {
   int sp_fuse_1x1 = geti("SF_SP_FUSE_1X1", 1);     // small-P kernel: the trusting gate's 1x1 layer runs inside the 7x7 layer's launch
   int split_cfg = geti("SF_SPLIT_CFG", 4);         // tile config of the mid-P split-K launches without a LayerNorm epilogue (4 | 1)
   int split_from = geti("SF_SPLIT_FROM", 100);     // only layers with at least this many K chunks (the 7x7)
+  // ---- what wino_plan / wino_runs decide by (conv_wino.hip's wino_takes says what the kernel CAN address)
+  int wino_ln7 = geti("SF_WINO_LN7", 1);           // the 7x7 + LayerNorm layer of the batched cells as nine 3x3 tap groups on the Winograd kernel (0: direct form) ...
+  int wino_ln7_min_p = geti("SF_WINO_LN7_MIN_P", 65536);   // ... from this many pixels: one cout block and 9 x cin/16 chunks per workgroup, so the launch needs a full round of
+                                                   // workgroups (2 x 256 blocks of 32 tiles = 65536 pixels) to pay — 8 latents of 50x50 are 175 workgroups of ~200 us each and
+                                                   // LOSE to the direct form (batch-8 step 549 -> 563 us, profiles/r06_ln7_ab.txt)
+  int wino_sample = geti("SF_WINO_SAMPLE", 1);     // the sampling layer of the batched infer_state on the Winograd kernel (0: direct form)
+  int wino_cat = geti("SF_WINO_CAT", 1);           // images concatenated along x where blocks of 8 tile columns fit one image badly (0: never) ...
+  int wino_cat_scaled = geti("SF_WINO_CAT_SCALED", 1);   // ... also layers with an SE input / residual scale (round 6: the SE scales of both images of a block; 0: plain form)
+  // 16-tile blocks where 32-tile blocks would leave the launch below this many workgroups (two rounds of the chip's 512 slots; 0: never).  The
+  // 16-tile form runs THREE workgroups per CU (80 registers, 46 KB of LDS), so a launch of nominally 313 / 626 32-tile workgroups (10 000 tiles / 32; as launched 328 / 656: 25 x 13
+  // blocks rounded up to 8) becomes about twice as many of 768 slots.  Measured per threshold (profiles/r06_wino16_ab.txt, single-sample forward): BLEND launches 0.608 -> 0.514 ms, AFFINE 2.880 ->
+  // 2.841, forward 7.44 -> 7.27 ms; at two samples per forward 13.18 -> 13.14; above ~1 400 workgroups the 32-tile form wins (every workgroup
+  // loads the whole U of its 64 output channels whatever its tile count: 16 tiles double the load instructions per MFMA)
+  long wino_small_wgs = getl("SF_WINO_SMALL_WGS", 1000);
   int wino_group = geti("SF_WINO_GROUP", 1);       // Winograd layers of identical geometry (the two branches of a dual cell) share ONE launch: their tails merge
   bool wino_list = isset("SF_WINO_LIST");          // debugging aid (tools/r05/wino_layers.py): every Winograd launch timed by itself on stderr — SYNCHRONISES the stream
   bool wino_why = isset("SF_WINO_WHY");            // debugging aid: which large 3x3 launches keep the direct form
@@ -113,6 +131,7 @@ hipError_t timed(Launch&& launch, CostFn&& cost, hipStream_t st) { return prof_o
 void prof_enable(bool on);
 int prof_collect(int32_t* calls, double* ms, double* flops, double* bytes);      // sf_prof_collect
 int debug_stamps(void* buf);                                                     // sf_debug_stamps
+int debug_wino_plan(const sf_conv_w& w, int epi, int n_img, int Hin, int Win, int in_up, int nprob, int flags, int32_t* out, int n_out);   // sf_debug_wino_plan
 
 // Scratch for the cross-workgroup split-K path, carved from the caller's workspace by the top-level entry points for the duration of one
 // call (RAII; the pointer to it is thread-local inside dispatch.hip, no global allocation)

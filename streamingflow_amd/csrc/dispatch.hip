@@ -55,6 +55,10 @@ hipError_t zero_fill(void* p, size_t bytes, hipStream_t st) {     // p 16-byte a
 }
 
 int geti(const char* k, int d) { const char* v = std::getenv(k); return v ? std::atoi(v) : d; }
+long getl(const char* k, long d) { const char* v = std::getenv(k); return v ? std::atol(v) : d; }
+// the two LIVE switches of the Winograd plan (dispatch.h), read once per plan
+struct WinoLive { long split_wgs; bool cat_wide; };
+static WinoLive wino_live() { return {getl("SF_WINO_SPLIT_WGS", 512), geti("SF_WINO_CAT_WIDE", 1) != 0}; }
 const Tune& tune() { static const Tune t; return t; }
 
 static int pick_cfg(int P, int epi) {
@@ -162,9 +166,16 @@ static bool offsets_fit32(const ConvProblem& q, double tile_px) {
   const double span = q.gather ? 4.0 * q.Win : (tile_px / ((double)q.Hout * q.Wout) + 2.0) * q.Hin * q.Win * 4.0;   // bytes per channel stride unit
   return span * q.in0_cs < 2147483648.0 && span * q.in1_cs < 2147483648.0 && 4.0 * q.cout_pad * q.ktot < 2147483648.0;
 }
+// the Winograd kernel can address this problem (conv_wino.hip: wino_takes) and its family is switched on at this size: the 7x7 tap-group
+// layer (SF_WINO_LN7, SF_WINO_LN7_MIN_P) and the sampling layer (SF_WINO_SAMPLE)
+static bool wino_wanted(const ConvProblem& q, int epi) {
+  if (epi == EPI_LNG && (!tune().wino_ln7 || pixels(q) < tune().wino_ln7_min_p)) return false;
+  if (epi == EPI_SAMPLE && !tune().wino_sample) return false;
+  return wino_takes(q, epi);
+}
 // this problem runs on the Winograd kernel of the large launches (conv_wino.hip)
 bool wino_runs(const ConvProblem& q, int epi) {
-  return tune().wino && (double)pixels(q) >= tune().wino_min_p && wino_takes(q, epi) && !(tune().b3 && q.w3);
+  return tune().wino && (double)pixels(q) >= tune().wino_min_p && wino_wanted(q, epi) && !(tune().b3 && q.w3);
 }
 
 // the split-K scratch of the running top-level call (SplitScope)
@@ -423,11 +434,10 @@ static Cost direct_cost(int key, const ConvProblem* ps, int n) {
   return c;
 }
 // Winograd form, priced at its EXECUTED flops: 16 products per 2x2 outputs, (cin, cout) pair and tap group (nine for the 7x7); the
-// variant of the first problem names the launch (_lib.KERNEL_NAMES: wino128x32t / wino64x64t / wino64x32t2, also its form with
-// concatenated images / wino64x32t2dil)
-static Cost wino_cost(const ConvProblem* ps, int n, int epi) {
-  const int wv = wino_variant(ps[0]);
-  Cost c{(16 + (wv == 4 ? 2 : wv)) * 8 + epi, 0, 0};
+// plan's form names the launch (_lib.KERNEL_NAMES: wino128x32t / wino64x64t / wino64x32t2, also its form with concatenated images /
+// wino64x32t2dil)
+static Cost wino_cost(const ConvProblem* ps, int n, int epi, WinoForm form) {
+  Cost c{(16 + (form == WINO_CAT ? 2 : (int)form)) * 8 + epi, 0, 0};
   for (int i = 0; i < n; ++i) {
     const ConvProblem& q = ps[i];
     const double grp = q.KH == 7 ? 9.0 : 1.0;
@@ -462,13 +472,143 @@ static int run_wide_ln(ConvLaunch& L, int epi, hipStream_t st) {
   return SF_OK;
 }
 
+// ---- Winograd launches, deciding: wino_plan is a pure function of the problems and the switches — form, one or two launches (segments),
+// per segment the window of tile rows, the block height, the grid and the reciprocals of the kernel's block decode, and whether the kernel's
+// arithmetic covers all of it.  Nothing is launched before the whole plan stands.
+struct WinoSeg {
+  int th, row0, rows;      // blocks of th tile rows over the tile rows [row0, row0 + rows) of every image
+  long grid1;              // workgroups per problem (the launch has grid1 * nprob)
+  unsigned m[5];           // ConvLaunch::wn_m
+};
+struct WinoPlan {
+  bool ok = false;         // false: not one launch of this kernel (a group then runs one by one)
+  WinoForm form = WINO_PLAIN;
+  int nprob = 0, nseg = 0;
+  long wgs32 = 0;          // workgroups of the whole layer / group on 32-tile blocks: what SF_WINO_SMALL_WGS is compared with
+  WinoSeg seg[2];
+};
+// Concatenated images pay where blocks of 8 tile columns fit the image badly and no epilogue operand is per image (SF_WINO_CAT=0: never)
+static WinoForm wino_form(const ConvProblem& q, const WinoLive& live) {
+  if (q.dil > 1) return WINO_DIL;
+  const int tpi = (q.Wout + 1) / 2;
+  if (!tune().wino_cat || q.in_up || q.n_img < 2 || tpi < WN_TW || q.bias_per_img || ((q.in_scale || q.add_scale) && !tune().wino_cat_scaled)) return WINO_PLAIN;
+  const int plain = (tpi + WN_TW - 1) / WN_TW * WN_TW;
+  // less than 10 % empty columns: the plain form, whose patch is two columns narrower — except at 128 or more output channels and at
+  // least 4 % empty columns (100 tile columns run 104: the 200x200 gates and 128 -> 128 layers), where CAT measured 1.7 - 2.8 % faster and
+  // the 64-channel layers within +-1 % (SF_WINO_CAT_WIDE=0: the 10 % rule alone)
+  if (plain * 100 < tpi * 110 && (q.cout_pad < 128 || plain * 100 < tpi * 104 || !live.cat_wide)) return WINO_PLAIN;
+  const double img_bytes = 4.0 * q.Hin * q.Win;
+  const int cs = std::max(q.in0_cs, q.in1_cs), cm = std::max({q.out_cs, q.add_cs, q.e0_cs, q.e1_cs, q.out2_cs});
+  return 2.0 * img_bytes * cs < 2147483648.0 && 2.0 * img_bytes * cm < 2147483648.0 ? WINO_CAT : WINO_PLAIN;      // two images behind one base
+}
+// tile blocks of one problem over `rows` tile rows of every image (tiles_x tile columns each) on blocks of th tile rows; nbx: block columns
+static long wino_blocks(const ConvProblem& P, WinoForm form, int tiles_x, int rows, int th, long* nbx_out = nullptr) {
+  const long nbx = ((form == WINO_CAT ? (long)P.n_img * tiles_x : tiles_x) + WN_TW - 1) / WN_TW, nby = (rows + th - 1) / th;
+  if (nbx_out) *nbx_out = nbx;
+  return form == WINO_CAT ? nby * nbx : (long)P.n_img * nby * nbx;
+}
+// ... and the workgroups of a launch of nprob such problems (the choice between the two block sizes and the split rule count the window a
+// launch covers, not the layer)
+static long wino_wgs(const ConvProblem& P, int nprob, WinoForm form, int tiles_x, int rows, int th) {
+  return ((wino_blocks(P, form, tiles_x, rows, th) + 7) / 8) * 8 * (P.cout_pad / WN_COUT_T) * nprob;
+}
+// One launch.  false: the window is not one the kernel walks (it must end with the image or be whole blocks; the dilated form takes the
+// whole image only), or the launch is beyond what the block decode computes exactly: it divides by multiplication with ceil(2^32 / d),
+// exact while dividend x d < 2^32
+static bool wino_segment(const ConvProblem& P, int nprob, WinoForm form, int th, int row0, int rows, WinoSeg& s) {
+  int tiles_x, tiles_all;
+  wino_tile_grid(P, tiles_x, tiles_all);
+  if (row0 < 0 || rows < 1 || row0 + rows > tiles_all || (form == WINO_DIL && rows != tiles_all) || (row0 + rows < tiles_all && rows % th)) return false;
+  long nbx;
+  const long blocks = wino_blocks(P, form, tiles_x, rows, th, &nbx), nby = (rows + th - 1) / th, ncb = P.cout_pad / WN_COUT_T;
+  const long grid1 = ((blocks + 7) / 8) * 8 * ncb, grid = grid1 * nprob;
+  if (grid > 0x7fffffffL) return false;
+  if ((grid1 / 8 + 1) * ncb >= 0x100000000L || (blocks + 8) * nbx >= 0x100000000L || (blocks + 8) * nby >= 0x100000000L ||
+      (nbx * WN_TW + WN_TW) * tiles_x >= 0x100000000L)
+    return false;
+  if (nprob > 1 && grid * grid1 >= 0x100000000L) return false;
+  s = WinoSeg{th, row0, rows, grid1, {nprob > 1 ? magic(grid1) : 1u, magic(ncb), magic(nbx), magic(nby), magic(tiles_x)}};
+  return true;
+}
+static WinoPlan wino_plan(const ConvProblem* ps, int n, int epi) {
+  WinoPlan W;
+  if (n < 1 || n > SF_MAX_GROUP) return W;
+  const WinoLive live = wino_live();
+  const ConvProblem& P = ps[0];
+  W.form = wino_form(P, live);
+  W.nprob = n;
+  // a group: one geometry, one form, and — the rule of the groups — few enough tile blocks for the group decode by multiplication (< 2^32 /
+  // workgroups; the exact tests of wino_segment cannot fail below this bound)
+  for (int i = 1; i < n; ++i)
+    if (!wino_same_geometry(P, ps[i]) || wino_form(ps[i], live) != W.form) return W;
+  if (n > 1 && !(wino_tiles(P) * (P.cout_pad / 64.0) * n < 1.0e6)) return W;
+  if (P.cout_pad % WN_COUT_T || (W.form == WINO_DIL && epi != EPI_AFFINE)) return W;
+  int tiles_x, tiles_y;
+  wino_tile_grid(P, tiles_x, tiles_y);
+  W.wgs32 = wino_wgs(P, n, W.form, tiles_x, tiles_y, WN_TH);
+  // the dilated form, the sampling layer, the tap groups and SE-scaled concatenated images have no 16-tile form and stay whole
+  const bool only32 = W.form == WINO_DIL || epi == EPI_SAMPLE || epi == EPI_LNG || (W.form == WINO_CAT && P.in_scale);
+  // 16-tile blocks where 32-tile blocks would leave the launch below SF_WINO_SMALL_WGS workgroups (Tune::wino_small_wgs)
+  const bool small = !only32 && W.wgs32 < tune().wino_small_wgs;
+  // Vertical remainder band: 25 / 50 tile rows end in a band of four with one / two real rows.  Such a layer runs as two launches: rows
+  // [0, 4 floor(tiles_y / 4)) on 32-tile blocks, the rest on 16-tile blocks (28 -> 26 / 52 -> 50 tile rows executed) — where the remainder
+  // launch has at least SF_WINO_SPLIT_WGS workgroups (default 512; 0: never, the layer stays whole).  Measured: the encoder / decoder
+  // layers of 224 - 256 images (704 - 3 200 remainder workgroups) gain 3 - 6 %, the rollout's 32-image layers (208) nothing: every workgroup loads
+  // the whole U and the launch has one more tail
+  const int main_rows = tiles_y & ~(WN_TH - 1), rem_rows = tiles_y - main_rows;
+  if (!small && !only32 && live.split_wgs > 0 && rem_rows > 0 && main_rows > 0 && wino_wgs(P, n, W.form, tiles_x, rem_rows, WN_TH_SMALL) >= live.split_wgs) {
+    const bool main_small = wino_wgs(P, n, W.form, tiles_x, main_rows, WN_TH) < tune().wino_small_wgs;
+    W.nseg = 2;
+    W.ok = wino_segment(P, n, W.form, main_small ? WN_TH_SMALL : WN_TH, 0, main_rows, W.seg[0]) &&
+           wino_segment(P, n, W.form, WN_TH_SMALL, main_rows, rem_rows, W.seg[1]);
+  } else {
+    W.nseg = 1;
+    W.ok = wino_segment(P, n, W.form, small ? WN_TH_SMALL : WN_TH, 0, tiles_y, W.seg[0]);
+  }
+  return W;
+}
+// the plan's launches, in order
+static hipError_t wino_issue(ConvLaunch& L, const WinoPlan& W, int epi, hipStream_t st) {
+  for (int s = 0; s < W.nseg; ++s) {
+    const WinoSeg& g = W.seg[s];
+    L.wg_base[0] = 0; L.wg_base[1] = (int)g.grid1;
+    L.wn_ty0 = g.row0; L.wn_nty = g.rows;
+    for (int k = 0; k < 5; ++k) L.wn_m[k] = g.m[k];
+    const hipError_t e = launch_conv_wino(L, epi, W.form, g.th, st);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+// sf_debug_wino_plan (include/sfnative.h): what run() will decide for nprob identical problems of this layer.  Host only: the pointers that
+// decide are non-null placeholders, nothing is dereferenced, no HIP call
+int debug_wino_plan(const sf_conv_w& w, int epi, int n_img, int Hin, int Win, int in_up, int nprob, int flags, int32_t* out, int n_out) {
+  if (!out || n_out < SF_WINO_PLAN_INTS || nprob < 1 || nprob > SF_MAX_GROUP || n_img < 1 || Hin < 1 || Win < 1 || in_up < 0 || in_up > 1) return SF_ERR_INVALID;
+  float* const ph = reinterpret_cast<float*>(uintptr_t(64));
+  ConvProblem g[SF_MAX_GROUP];
+  g[0] = problem(w, ph, w.c1 > 0 ? ph : nullptr, ph, n_img, Hin, Win, in_up);
+  if (flags & 1) g[0].in_scale = ph;
+  if (flags & 2) g[0].add = ph;
+  if (flags & 4) { g[0].out2 = ph; g[0].out2_cs = w.cout / 2; g[0].e1 = ph; g[0].e1_cs = w.cout / 2; g[0].gate_from = w.cout / 2; }      // (the reset gate's second output)
+  if (epi == EPI_SAMPLE) g[0].e0 = ph;
+  for (int i = 1; i < nprob; ++i) g[i] = g[0];
+  for (int i = 0; i < SF_WINO_PLAN_INTS; ++i) out[i] = 0;
+  if (!wino_runs(g[0], epi)) return SF_OK;
+  const WinoPlan W = wino_plan(g, nprob, epi);
+  out[0] = 1; out[1] = (int)W.form; out[2] = W.ok ? W.nseg : 0;
+  for (int s = 0; s < out[2]; ++s) {
+    out[3 + 4 * s] = W.seg[s].th; out[4 + 4 * s] = W.seg[s].row0; out[5 + 4 * s] = W.seg[s].rows; out[6 + 4 * s] = (int)(W.seg[s].grid1 * nprob);
+  }
+  out[11] = (int)std::min(W.wgs32, 0x7fffffffL);
+  return SF_OK;
+}
+
 // SF_WINO_LIST (tools/r05/wino_layers.py): the launch timed by itself, one line on stderr.  SYNCHRONISES the stream — a debugging aid only
-static int wino_list_launch(const ConvLaunch& W1, int epi, hipStream_t st) {
+static int wino_list_launch(ConvLaunch& W1, const WinoPlan& W, int epi, hipStream_t st) {
   const ConvProblem& q = W1.p[0];
   hipEvent_t a, b;
   SF_HIP(hipEventCreate(&a)); SF_HIP(hipEventCreate(&b));
   SF_HIP(hipEventRecord(a, st));
-  SF_HIP(launch_conv_wino(W1, epi, st));
+  SF_HIP(wino_issue(W1, W, epi, st));
   SF_HIP(hipEventRecord(b, st));
   SF_HIP(hipEventSynchronize(b));
   float ms = 0.f;
@@ -476,14 +616,14 @@ static int wino_list_launch(const ConvLaunch& W1, int epi, hipStream_t st) {
   (void)hipEventDestroy(a); (void)hipEventDestroy(b);
   std::fprintf(stderr, "[sf-wino] n=%d %dx%d c=%d+%d->%d epi=%d act=%d mode=%d add=%d add_scale=%d out2=%d in_scale=%d bias_img=%d clamp=%d dil=%d up=%d var=%d us=%.1f gflop=%.3f\n",
                q.n_img, q.Hout, q.Wout, q.c0, q.c1, q.cout, epi, q.act, q.mode, q.add != nullptr, q.add_scale != nullptr, q.out2 != nullptr,
-               q.in_scale != nullptr, q.bias_per_img, q.clamp_from >= 0, q.dil, q.in_up, wino_variant(q), ms * 1e3,
+               q.in_scale != nullptr, q.bias_per_img, q.clamp_from >= 0, q.dil, q.in_up, (int)W.form, ms * 1e3,
                2.0 * 16.0 * wino_tiles(q) * q.cout * (q.c0 + q.c1) * 1e-9);
   return SF_OK;
 }
 // SF_WINO_WHY: which large 3x3 launches keep the direct form, one line each on stderr
 static void wino_why(const ConvProblem* ps, int n, int epi) {
   for (int i = 0; i < n; ++i)
-    if (ps[i].KH == 3 && !wino_takes(ps[i], epi))
+    if (ps[i].KH == 3 && !wino_wanted(ps[i], epi))
       std::fprintf(stderr, "[sf] direct 3x3: n=%d/%d %dx%d c=%d+%d->%d stride=%d dil=%d up=%d gather=%d gate=%d in_scale=%d se_sum=%d nsplit=%d chansum=%d acc_in=%d fuse=%d mode=%d wino=%d\n",
                    i, n, ps[i].Hout, ps[i].Wout, ps[i].c0, ps[i].c1, ps[i].cout, ps[i].stride, ps[i].dil, ps[i].in_up, ps[i].gather != nullptr,
                    ps[i].gate != nullptr, ps[i].in_scale != nullptr, ps[i].se_sum != nullptr, ps[i].nsplit, ps[i].chansum != nullptr,
@@ -510,27 +650,21 @@ static int run_wino(const ConvProblem* ps, int n, int P, int epi, hipStream_t st
       if (!takes[i]) rest[nr++] = ps[i];
     SF_TRY(run(rest, nr, epi, st));
   }
+  // one profiler record per planned layer / group, whatever its number of launches
+  auto issue = [&](ConvLaunch& L, const WinoPlan& W) {
+    L.stamp_slot = next_stamp_slot();
+    return timed([&] { return wino_issue(L, W, epi, st); }, [&] { return wino_cost(L.p, L.nprob, epi, W.form); }, st);
+  };
   // layers of identical geometry (the two branches of a dual cell) share ONE launch: their tails merge
   if (tune().wino_group && !tune().wino_list && n_wino >= 2) {
     ConvLaunch WG;
     std::memset(&WG, 0, sizeof(WG));
-    bool same = true;
-    int first = -1;
-    for (int i = 0; i < n; ++i) {
-      if (!takes[i]) continue;
-      if (first < 0) first = i;
-      same = same && wino_same_geometry(ps[first], ps[i]);
-      WG.p[WG.nprob++] = ps[i];
-    }
-    if (same && wino_tiles(ps[first]) * (ps[first].cout_pad / 64.0) * WG.nprob < 1.0e6) {      // (group decode by multiplication: < 2^32 / workgroups)
-      WG.stamp_slot = next_stamp_slot();
-      // (the kernel's block decode multiplies by host-made reciprocals and refuses — hipErrorInvalidValue, nothing launched — a size whose
-      // exactness check fails: the heuristic above is not that check, so a refused group runs as one launch per problem below, ADVICE r5;
-      // profiled or not)
-      const hipError_t ge = timed([&] { return launch_conv_wino(WG, epi, st); }, [&] { return wino_cost(WG.p, WG.nprob, epi); }, st);
-      if (ge == hipSuccess) return SF_OK;
-      if (ge != hipErrorInvalidValue) return SF_ERR_LAUNCH;
-      (void)hipGetLastError();
+    for (int i = 0; i < n; ++i)
+      if (takes[i]) WG.p[WG.nprob++] = ps[i];
+    const WinoPlan W = wino_plan(WG.p, WG.nprob, epi);
+    if (W.ok) {      // (not ok — geometries differ, or too large for the group decode: one launch per problem below)
+      SF_HIP(issue(WG, W));
+      return SF_OK;
     }
   }
   for (int i = 0; i < n; ++i) {      // the kernel takes one problem, or a group of one geometry: launched one by one
@@ -539,9 +673,14 @@ static int run_wino(const ConvProblem* ps, int n, int P, int epi, hipStream_t st
     std::memset(&W1, 0, sizeof(W1));
     W1.p[0] = ps[i];
     W1.nprob = 1;
-    W1.stamp_slot = next_stamp_slot();
-    if (tune().wino_list && !prof_on()) SF_TRY(wino_list_launch(W1, epi, st));
-    else SF_HIP(timed([&] { return launch_conv_wino(W1, epi, st); }, [&] { return wino_cost(W1.p, 1, epi); }, st));
+    const WinoPlan W = wino_plan(W1.p, 1, epi);
+    if (!W.ok) return SF_ERR_LAUNCH;
+    if (tune().wino_list && !prof_on()) {
+      W1.stamp_slot = next_stamp_slot();
+      SF_TRY(wino_list_launch(W1, W, epi, st));
+    } else {
+      SF_HIP(issue(W1, W));
+    }
   }
   return SF_OK;
 }

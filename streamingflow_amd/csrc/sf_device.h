@@ -139,8 +139,8 @@ struct ConvLaunch {
   // Winograd kernel: ceil(2^32 / d) of the block decode's divisors (0: d = 1) — workgroups per problem of a group (1: one problem),
   // cout blocks, tile-block columns, tile-block rows, tile columns per image
   unsigned wn_m[6];
-  // Winograd kernel: the launch's window of tile rows, [wn_ty0, wn_ty0 + wn_nty) of every image (launch_wino5_t fills it: the whole image,
-  // or one part of a layer that launch_conv_wino split at its last full band of four tile rows)
+  // Winograd kernel: the launch's window of tile rows, [wn_ty0, wn_ty0 + wn_nty) of every image (dispatch.hip: wino_plan decides it: the whole image,
+  // or one part of a layer that it split at its last full band of four tile rows)
   int wn_ty0, wn_nty;
 };
 

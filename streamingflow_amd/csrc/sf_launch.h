@@ -12,10 +12,17 @@ int glds_occupancy(int which);
 hipError_t set_stamp_buffer_sp(unsigned long long* p);
 hipError_t set_stamp_buffer_wino(unsigned long long* p);
 hipError_t launch_conv_sp(const ConvLaunch& L, int epi, bool scaled, int bn, hipStream_t stream);
-hipError_t launch_conv_wino(const ConvLaunch& L, int epi, hipStream_t stream);
+// Winograd kernel (conv_wino.hip).  A workgroup's block: WN_COUT_T output channels x (4 or 2 tile rows) x WN_TW tile columns — 32 or 16
+// Winograd tiles.  The form names the run structure of a launch (also the profiler's variant of the kernel key).  dispatch.hip: wino_plan
+// decides form, block height, window of tile rows, grid and reciprocals and writes them into the ConvLaunch; the launcher only maps
+// (epi, form, block height) to the instantiation (hipErrorInvalidValue where there is none: dilated + blend, sample / LNG on 16-tile
+// blocks, SE-scaled concatenated images on 16-tile blocks)
+constexpr int WN_COUT_T = 64, WN_TW = 8, WN_TH = 4, WN_TH_SMALL = 2;
+enum WinoForm { WINO_PLAIN = 2, WINO_DIL = 3, WINO_CAT = 4 };
+hipError_t launch_conv_wino(const ConvLaunch& L, int epi, WinoForm form, int th, hipStream_t stream);
 bool wino_takes(const ConvProblem& q, int epi);
 bool wino_same_geometry(const ConvProblem& a, const ConvProblem& b);
-int wino_variant(const ConvProblem& q);
+void wino_tile_grid(const ConvProblem& q, int& tiles_x, int& tiles_y);
 double wino_tiles(const ConvProblem& q);
 hipError_t launch_sp_flow(const SpFlow& F, int grid, bool b3, hipStream_t stream);
 hipError_t launch_flow_write(const void* host_src, void* dev_dst, size_t bytes, hipStream_t stream);

@@ -344,7 +344,7 @@ def test_winograd_epilogues_of_the_batched_latents_against_the_direct_form():
 
 @pytest.mark.parametrize("thr", [0, 1000000000])
 def test_winograd_cases_under_both_block_sizes(thr):
-    """conv_wino5_kernel has two block sizes (32 and 16 Winograd tiles per workgroup; launch_conv_wino picks by the launch's workgroup
+    """conv_wino5_kernel has two block sizes (32 and 16 Winograd tiles per workgroup; dispatch.hip: wino_plan picks by the launch's workgroup
     count).  Every Winograd case of this file and of test_gpu_ops.py again in a child process with the choice forced: never / always the
     16-tile form — the same oracle, the same tolerances."""
     import subprocess

@@ -1,7 +1,7 @@
 """conv_wino5_kernel without workgroups on tiles outside the image.  (1) A layer whose tile rows are not a multiple of four runs as a
-main launch on 32-tile blocks and a remainder launch on 16-tile blocks over a window of tile rows (launch_conv_wino, SF_WINO_SPLIT_WGS;
-0 keeps the layer whole).  (2) 200x200 layers of 128 or more output channels run on images concatenated along x instead of 104 tile
-columns for 100 (wino_cat, SF_WINO_CAT_WIDE; 0 keeps the plain form).  Every real tile is computed by the same arithmetic in both
+main launch on 32-tile blocks and a remainder launch on 16-tile blocks over a window of tile rows (dispatch.hip: wino_plan,
+SF_WINO_SPLIT_WGS; 0 keeps the layer whole).  (2) 200x200 layers of 128 or more output channels run on images concatenated along x instead
+of 104 tile columns for 100 (wino_plan, SF_WINO_CAT_WIDE; 0 keeps the plain form).  Every real tile is computed by the same arithmetic in both
 forms, so the two must agree — and both with the oracle the existing Winograd cases use (test_gpu_conv_random.py: torch's conv2d,
 2e-4; the direct form of the same layer, 5e-5)."""
 import os
@@ -9,7 +9,7 @@ import os
 import pytest
 import torch
 
-from util import hashfill, maxabs
+from util import hashfill, maxabs, wino_plan
 
 pytestmark = pytest.mark.gpu
 
@@ -17,7 +17,7 @@ SPLIT, WIDE = "SF_WINO_SPLIT_WGS", "SF_WINO_CAT_WIDE"
 
 
 class _env:
-    """both switches are read at every launch: set one for the calls inside the block"""
+    """both switches are read at every plan of a launch: set one for the calls inside the block"""
 
     def __init__(self, name, value):
         self.name, self.value = name, value
@@ -31,16 +31,6 @@ class _env:
             os.environ.pop(self.name, None)
         else:
             os.environ[self.name] = self.was
-
-
-def _wgs32(n, H, W, cout, rows=None):
-    """32-tile workgroups of a launch as launch_conv_wino counts them (concatenated images where the plain form leaves >= 10 % of the
-    block columns empty)"""
-    tx, ty = (W + 1) // 2, (H + 1) // 2
-    rows = ty if rows is None else rows
-    cat = n >= 2 and tx >= 8 and (tx + 7) // 8 * 8 * 100 >= tx * 110
-    blocks = (rows + 3) // 4 * ((n * tx + 7) // 8) if cat else n * ((rows + 3) // 4) * ((tx + 7) // 8)
-    return (blocks + 7) // 8 * 8 * ((cout + 63) // 64)
 
 
 # 64 -> 64 and 128 -> 128 layers: 50x50 (25 tile rows: one left over), 100x100 (50: two left over), 200x200 (100: none — the switch must
@@ -67,12 +57,13 @@ def test_split_layer_equals_the_whole_layer(i):
     c = dict(k=3, stride=1, dil=1, pad=1, act=["relu", "none", "lrelu", "tanh"][i % 4], add=i % 3 != 1, after=i % 2 == 0, in_slack=8 * (i % 2),
              out_slack=[0, 4, 16][i % 3])
     c.update(_CASES[i])
-    ty = (c["H"] + 1) // 2
-    splits = ty % 4 != 0 and _wgs32(c["n"], c["H"], c["W"], c["cout"]) >= 1000
-    assert splits == _SPLITS[i], "the case no longer exercises what it was chosen for"
+    layer = {k: c[k] for k in ("c0", "c1", "cout", "n", "H", "W")}
     with _env(SPLIT, 0):
+        assert len(wino_plan(**layer)["segs"]) == 1
         whole = _run(c, 700 + i, wino=True)        # (asserts <= 2e-4 against torch)
     with _env(SPLIT, 1):
+        # what the library plans (sf_debug_wino_plan): the split case as two launches, the other as one
+        assert len(wino_plan(**layer)["segs"]) == (2 if _SPLITS[i] else 1), "the case no longer exercises what it was chosen for"
         split = _run(c, 700 + i, wino=True)
     direct = _run(c, 700 + i, wino=False)
     d = maxabs(split, whole)
@@ -122,7 +113,7 @@ def test_gates_with_second_output_and_blend(B, h, w, switch):
     from streamingflow_amd import packing
     C = 64
     cts, lts, tts, dt = cases.timeset("shipped")
-    assert _wgs32(B, h, w, 2 * C) >= 1000
+    assert wino_plan(C, C, 2 * C, B, h, w, flags=4)["wgs32"] >= 1000      # the gates launch, counted on 32-tile blocks
 
     def build(wino, on):
         was = packing.winograd()

@@ -32,6 +32,21 @@ def build_pair(C, solver="euler", impute=True, variable=True, delta_t=0.05, devi
     return net, sd
 
 
+def wino_plan(c0, c1, cout, n, H, W, dil=1, in_up=0, k=3, epi=0, nprob=1, flags=0):
+    """What the conv dispatch decides for a launch of `nprob` identical k x k / stride-1 / pad = dil (k - 1) / 2 layers on n images of H x W
+    (sf_debug_wino_plan: host arithmetic under the switches in force, no GPU; the weight pointers are placeholders nobody reads).  flags:
+    1 SE input scale, 2 residual, 4 second output.  dict(takes, form 2 plain / 3 dilated / 4 concatenated, segs = [(tile rows per block,
+    first tile row, tile rows, workgroups)] — empty where a group runs one by one —, wgs32 = workgroups of the whole launch on 32-tile blocks)"""
+    import ctypes
+    from streamingflow_amd import _lib
+    cin = c0 + c1
+    w = _lib.ConvW(w=64, cout=cout, cout_pad=(cout + 15) // 16 * 16, c0=c0, c1=c1, cin_pad=(cin + 31) // 32 * 32, kh=k, kw=k, dil=dil, stride=1,
+                   pad=dil * (k - 1) // 2, act=0, w_wino=64)
+    out = (ctypes.c_int32 * _lib.SF_WINO_PLAN_INTS)()
+    _lib.check(_lib.lib().sf_debug_wino_plan(ctypes.byref(w), epi, n, H, W, in_up, nprob, flags, out, len(out)), "sf_debug_wino_plan")
+    return dict(takes=bool(out[0]), form=out[1], segs=[tuple(out[3 + 4 * s:7 + 4 * s]) for s in range(out[2])], wgs32=out[11])
+
+
 def gold(name):
     return np.load(os.path.join(GOLD, name))
 
