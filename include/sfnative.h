@@ -566,6 +566,36 @@ size_t sf_instance_labels_ws_bytes(int B, int T, int H, int W, int num_instances
 int sf_instance_labels_fwd(const int64_t* instance, const float* theta, int B, int T, int H, int W, int num_instances, double sigma,
                            float ignore_index, float* center, float* offset, float* flow, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the planner (streamingflow/cost.py, models/planning_model.py, metrics.py:263-396).  Every pointer below is a device pointer
+ * except `factors`; every call enqueues only: no allocation, no synchronisation, nothing read back.  Grids are square (H == W = G).
+ * Trajectories are rows of traj_stride floats per waypoint (x, y first), so a [.., T, 3] tensor is passed as it is.
+ * sf_plan_cost_fwd — Cost_Function.forward for trajs [B][N][T] waypoints: cost_volume [B][T][G][G] fp32, occupancy [B][T][G][G] uint8,
+ *   lane_divider and drivable [B][G][G] fp32 already reduced to one channel, target_points [B][2], the footprint tables rc0 [n0][2] and
+ *   rc_lambda [n_lambda][2] (int32 row, column offsets of the ego rectangle and of the rectangle grown by lambda), dx [2], bx [2],
+ *   safety_w [2] (device), factors[7] (HOST: safety, headway, lane divider, comfort, progress, rule, cost volume), the headway and the
+ *   divider distance in metres -> cost_fo [B][N][T], cost_fc [B][N], cs [B][N] = cost_fc + sum_t cost_fo.  Two launches: a one-thread
+ *   launch forms target_points.sum() < 0.5 (over the whole batch) in the workspace, the second scores one trajectory per wavefront.
+ *   SF_ERR_INVALID: a NULL pointer, B / N / T / H < 1, H != W, traj_stride < 2; SF_ERR_WORKSPACE: ws_bytes < sf_plan_cost_ws_bytes().
+ * sf_plan_select_refine_fwd — one workgroup per sample: arg-min of cs [B][N] over N (lowest index on a tie), selected [B][T][3] = that
+ *   trajectory, and, for S > 0, the refinement loop of Planning.forward on it: h = h0 [B][S], x = 0, per waypoint
+ *   h = GRUCell([x, waypoint xy, target]), x = Linear(ReLU(Linear(h))) -> refined [B][T][3] with a zero third column.  Weights in
+ *   torch's layout: w_ih [3S][6], w_hh [3S][S], b_ih, b_hh [3S] (gates r, z, n), w1 [S][S], b1 [S], w2 [2][S], b2 [2].  S == 0 selects
+ *   only (the GRU arguments and refined may be NULL).  SF_ERR_INVALID: a NULL pointer, B / N / T < 1, S < 0 or > 256, traj_stride < 3.
+ * sf_plan_metric_fwd — PlanningMetric.update: ADDS into obj_col [T], obj_box_col [T], l2 [T] (fp32) and total (int64) for trajs and
+ *   gt_trajs [B][T] waypoints and segmentation [B][T][G][G] uint8.  One launch, one writer per counter (no atomics).
+ *   SF_ERR_INVALID: a NULL pointer, B / T / H < 1, H != W, traj_stride < 2. */
+size_t sf_plan_cost_ws_bytes(void);
+int sf_plan_cost_fwd(const float* trajs, long traj_stride, const float* cost_volume, const uint8_t* occupancy, const float* lane_divider,
+                     const float* drivable, const float* target_points, const int32_t* rc0, int n0, const int32_t* rc_lambda, int n_lambda,
+                     const float* dx, const float* bx, const float* safety_w, const float* factors, float headway_L, float divider_L, int B,
+                     int N, int T, int H, int W, float* cost_fo, float* cost_fc, float* cs, void* ws, size_t ws_bytes, void* stream);
+int sf_plan_select_refine_fwd(const float* cs, const float* trajs, long traj_stride, const float* target_points, const float* h0,
+                              const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, const float* w1, const float* b1,
+                              const float* w2, const float* b2, int B, int N, int T, int S, float* selected, float* refined, void* stream);
+int sf_plan_metric_fwd(const float* trajs, const float* gt_trajs, long traj_stride, const uint8_t* segmentation, const int32_t* rc0, int n0,
+                       const float* dx, const float* bx, int B, int T, int H, int W, float* obj_col, float* obj_box_col, float* l2,
+                       int64_t* total, void* stream);
+
 /* hipGraph capture of whatever the caller enqueues between begin and end on `stream` (must not be
  * the legacy default stream). */
 int sf_graph_begin(void* stream);

@@ -184,3 +184,83 @@ class PanopticMetric(_Accumulator):
         denominator = torch.maximum(self.true_positive + 0.5 * self.false_positive + 0.5 * self.false_negative, one)
         return {"pq": self.iou / denominator, "sq": self.iou / torch.maximum(self.true_positive, one),
                 "rq": self.true_positive / denominator}
+
+
+class PlanningMetric(_Accumulator):
+    """``PlanningMetric`` (streamingflow/metrics.py:263-396): per future frame the L2 distance to the ground-truth trajectory, the
+    collisions of the planned point (``obj_col``) and of the ego rectangle (``obj_box_col``) with the ground-truth occupancy,
+    counted only where the ground-truth trajectory's own rectangle is free.  ``update`` on device tensors is one launch of
+    ``sf_plan_metric_fwd`` that adds into the counters; nothing is read back.  CPU tensors (or ``SF_PLAN_TORCH=1``) take the
+    plain-torch statement of the same arithmetic."""
+
+    def __init__(self, cfg, n_future=4, compute_on_step: bool = False):
+        super().__init__(("obj_col", "obj_box_col", "L2"), n_future)
+        from .cost import footprint
+        from .models.lift_splat import calculate_birds_eye_view_parameters
+        dx, bx, dim = calculate_birds_eye_view_parameters(cfg.LIFT.X_BOUND, cfg.LIFT.Y_BOUND, cfg.LIFT.Z_BOUND)
+        self.dx = nn.Parameter(dx[:2].float(), requires_grad=False)
+        self.bx = nn.Parameter(bx[:2].float(), requires_grad=False)
+        self.bev_dimension = dim.numpy()
+        self.W, self.H, self.n_future = cfg.EGO.WIDTH, cfg.EGO.HEIGHT, n_future
+        self.register_buffer("total", torch.tensor(0), persistent=False)
+        self.register_buffer("_rc", footprint(self.W, self.H, dx[:2].numpy(), bx[:2].numpy()).to(torch.int32), persistent=False)
+
+    def reset(self):
+        super().reset()
+        self.total.zero_()
+
+    def sync(self):
+        """The reference declares ``total`` with ``dist_reduce_fx='sum'`` like the three sums: it is reduced with them."""
+        super().sync()
+        from . import dist
+        dist.reduce_counters(self.total)
+
+    def _box_hit(self, traj, segmentation):
+        """traj [B, T, 2] (mirrored), segmentation [B, T, G, G] -> [B, T] bool: the ego rectangle touches an occupied cell.  The
+        reference swaps, divides by dx in fp32 and adds the integer table in float64 (numpy) before it truncates."""
+        G = segmentation.shape[-1]
+        q = (traj[..., [1, 0]] / self.dx).double().unsqueeze(2) + self._rc.double()
+        r, c = q[..., 0].long().clamp(0, G - 1), q[..., 1].long().clamp(0, G - 1)
+        B, T = traj.shape[:2]
+        ii = torch.arange(B, device=traj.device)[:, None, None]
+        tt = torch.arange(T, device=traj.device)[None, :, None]
+        return (segmentation[ii, tt, r, c] != 0).any(dim=-1)
+
+    def _update_torch(self, trajs, gt_trajs, segmentation):
+        G = segmentation.shape[-1]
+        flip = torch.tensor([-1, 1], device=trajs.device)
+        p, g = trajs[..., :2] * flip, gt_trajs[..., :2] * flip
+        gt_hit = self._box_hit(g, segmentation)
+        yi = ((p[..., 1] - self.bx[0]) / self.dx[0]).long()
+        xi = ((p[..., 0] - self.bx[1]) / self.dx[1]).long()
+        inside = (yi >= 0) & (yi < G) & (xi >= 0) & (xi < G) & ~gt_hit
+        B, T = p.shape[:2]
+        ii = torch.arange(B, device=p.device)[:, None]
+        tt = torch.arange(T, device=p.device)[None, :]
+        at = segmentation[ii, tt, yi.clamp(0, G - 1), xi.clamp(0, G - 1)].float()
+        self.obj_col += torch.where(inside, at, torch.zeros_like(at)).sum(dim=0)
+        self.obj_box_col += (self._box_hit(p, segmentation) & ~gt_hit).float().sum(dim=0)
+        self.L2 += torch.sqrt(((trajs[..., :2] - gt_trajs[..., :2]) ** 2).sum(dim=-1)).sum(dim=0)
+        self.total += len(trajs)
+
+    def update(self, trajs, gt_trajs, segmentation):
+        """trajs, gt_trajs [B, T, 3]; segmentation [B, T, G, G] (0 = free)."""
+        assert trajs.shape == gt_trajs.shape
+        from .cost import occupancy_u8, use_torch_path
+        if segmentation.shape[-1] != segmentation.shape[-2]:
+            raise NotImplementedError("non-square BEV grids")
+        if self.L2.device != trajs.device:                  # first update on another device: the state moves, not the data
+            self.to(trajs.device)
+        seg = occupancy_u8(segmentation)
+        trajs, gt_trajs = runtime.f32c(trajs), runtime.f32c(gt_trajs)
+        if use_torch_path(trajs, gt_trajs, seg):
+            return self._update_torch(trajs, gt_trajs, seg)
+        B, T, s = trajs.shape
+        if T != self.n_future or s < 2:
+            raise ValueError("expected [B, %d, >= 2] trajectories" % self.n_future)
+        _lib.check(_lib.lib().sf_plan_metric_fwd(ptr(trajs), ptr(gt_trajs), s, ptr(seg), ptr(self._rc), self._rc.shape[0], ptr(self.dx), ptr(self.bx),
+                                                 B, T, seg.shape[-2], seg.shape[-1], ptr(self.obj_col), ptr(self.obj_box_col), ptr(self.L2),
+                                                 ptr(self.total), runtime.stream_ptr(trajs.device)), "plan_metric")
+
+    def compute(self):
+        return {"obj_col": self.obj_col / self.total, "obj_box_col": self.obj_box_col / self.total, "L2": self.L2 / self.total}

@@ -21,6 +21,7 @@ import torch.nn as nn
 from .decoder import Decoder
 from .future_prediction_ode import FuturePredictionODE
 from .lift_splat import LiftSplat
+from .planning import Planning
 from .sparse_encoder import SparseEncoder
 from .temporal_model import TemporalModel
 from ..voxelize import Voxelization, voxelize
@@ -48,7 +49,11 @@ def default_cfg(**over):
                       FUTURE_PRED=NS(N_GRU_BLOCKS=2, N_RES_LAYERS=1, MIXTURE=True, DELTA_T=0.05, USE_VARIABLE_ODE_STEP=True),
                       IMPUTE=True, SOLVER="euler", SMALL_ENCODER=NS(FILTER_SIZE=64, SKIPCO=False)),
              SEMANTIC_SEG=NS(VEHICLE=NS(WEIGHTS=[1.0, 2.0]), PEDESTRIAN=NS(ENABLED=False), HDMAP=NS(ENABLED=False, ELEMENTS=["lane_divider", "drivable_area"])),
-             INSTANCE_SEG=NS(ENABLED=True), INSTANCE_FLOW=NS(ENABLED=True), PLANNING=NS(ENABLED=False),
+             INSTANCE_SEG=NS(ENABLED=True), INSTANCE_FLOW=NS(ENABLED=True),
+             # the planner is off unless asked for; GRU_STATE_SIZE 256 is what reduce_channel makes of a [64, 28, 60] front-camera map
+             PLANNING=NS(ENABLED=False, GRU_STATE_SIZE=256, SAMPLE_NUM=600, COMMAND=["LEFT", "FORWARD", "RIGHT"]),
+             EGO=NS(WIDTH=1.85, HEIGHT=4.084),
+             COST_FUNCTION=NS(SAFETY=0.1, LAMBDA=1.0, HEADWAY=1.0, LRDIVIDER=10.0, COMFORT=0.1, PROGRESS=0.5, VOLUME=100.0),
              LIDAR_ENCODER=LIDAR_ENCODER)
     for k, v in over.items():
         setattr(cfg, k, v)
@@ -67,6 +72,7 @@ class streamingflow(nn.Module):
         self.use_lidar, self.use_camera = cfg.MODEL.MODALITY.USE_LIDAR, cfg.MODEL.MODALITY.USE_CAMERA
         self.receptive_field, self.n_future = cfg.TIME_RECEPTIVE_FIELD, cfg.N_FUTURE_FRAMES
         self.latent_dim = cfg.MODEL.DISTRIBUTION.LATENT_DIM
+        self.planning_enabled = bool(getattr(getattr(cfg, "PLANNING", None), "ENABLED", False))
         self.bev_size = (int(self.bev_dimension[0]), int(self.bev_dimension[1]))
         self.encoder = None                       # image backbone: not part of this build (see module docstring)
         tm = cfg.MODEL.TEMPORAL_MODEL
@@ -87,7 +93,9 @@ class streamingflow(nn.Module):
                                predict_gate={"perceive_hdmap": cfg.SEMANTIC_SEG.HDMAP.ENABLED,
                                              "predict_pedestrian": cfg.SEMANTIC_SEG.PEDESTRIAN.ENABLED,
                                              "predict_instance": cfg.INSTANCE_SEG.ENABLED,
-                                             "predict_future_flow": cfg.INSTANCE_FLOW.ENABLED, "planning": cfg.PLANNING.ENABLED})
+                                             "predict_future_flow": cfg.INSTANCE_FLOW.ENABLED, "planning": self.planning_enabled})
+        if self.planning_enabled:
+            self.planning = Planning(cfg, self.encoder_out_channels, 6, gru_state_size=cfg.PLANNING.GRU_STATE_SIZE)
         if self.use_lidar:
             enc = getattr(cfg, "LIDAR_ENCODER", LIDAR_ENCODER)
             self.encoders = nn.ModuleDict({"lidar": nn.ModuleDict({
@@ -117,7 +125,8 @@ class streamingflow(nn.Module):
 
     def calculate_birds_eye_view_features(self, image, intrinsics, extrinsics, future_egomotion):
         """streamingflow.py:430-448 minus the image backbone: ``image`` is (features [b,s,n,C,fH,fW],
-        depth logits [b,s,n,D,fH,fW]) or, with ``self.encoder`` set, the images [b,s,n,3,H,W]."""
+        depth logits [b,s,n,D,fH,fW]) or, with ``self.encoder`` set, the images [b,s,n,3,H,W].  The third result is the planner's
+        ``cam_front``: the features of camera 1 in the last (present) frame (``encoder_forward``, :294-303), None with planning off."""
         if isinstance(image, (tuple, list)):
             feat, depth = image
         else:
@@ -127,7 +136,8 @@ class streamingflow(nn.Module):
             feat, depth = self.encoder(image.reshape(b * s * n, *image.shape[3:]))
             feat, depth = feat.view(b, s, n, *feat.shape[1:]), depth.view(b, s, n, *depth.shape[1:])
         x = self.lift.lift_splat(feat, depth, intrinsics, extrinsics, future_egomotion)
-        return x, depth, None
+        cam_front = feat[:, -1, 1].contiguous() if self.planning_enabled else None
+        return x, depth, cam_front
 
     def forward(self, image, intrinsics, extrinsics, future_egomotion, padded_voxel_points=None, camera_timestamp=None, points=None,
                 lidar_timestamp=None, target_timestamp=None):
