@@ -20,19 +20,28 @@ bool valid_w(const sf_conv_w& w) {
 
 // ---- modules ---------------------------------------------------------------------------------
 
-// conv-GRU cell (temporal.py:44-57): gates -> blend.  gates buffer g: [P][2C] = [u | r]
-// rs: optional [P][C] scratch.  Large pixel counts: the gates epilogue also writes (1 - r) * s there and the candidate
-// convolution reads cat[x, rs] as a plain layer (LDS-DMA staging); otherwise the gate is applied while staging.
+// The two convolutions of one conv-GRU branch (temporal.py:44-57); gates buffer g: [P][2C] = [u | r].  rs: optional [P][C] scratch.  Large
+// pixel counts: the gates epilogue also writes (1 - r) * s there and the candidate convolution reads cat[x, rs] as a plain layer (LDS-DMA
+// staging); otherwise (rs == nullptr) the gate is applied while staging.
+ConvProblem gates_problem(const sf_conv_w& gw, const float* in0, const float* in1, float* g, const float* s, float* rs, int C, int n, int H, int W) {
+  ConvProblem p = problem(gw, in0, in1, g, n, H, W);
+  if (rs) { p.out2 = rs; p.out2_cs = C; p.e1 = s; p.e1_cs = C; p.gate_from = C; }      // the pre-gated second output
+  return p;
+}
+ConvProblem cand_problem(const sf_conv_w& cw, const float* x, const float* s, const float* rs, float* h, const float* g, int C, int n, int H, int W) {
+  ConvProblem p = problem(cw, x, rs ? rs : s, h, n, H, W);
+  p.e0 = g; p.e0_cs = 2 * C; p.e1 = s; p.e1_cs = C;                                      // the blend operands
+  if (!rs) { p.gate = g; p.gate_cs = 2 * C; p.gate_co = C; }
+  return p;
+}
+
+// conv-GRU cell: gates -> blend
 int gru_cell(const sf_gru_w& w, const float* x, const float* s, float* out, float* g, float* rs, int n, int H, int W,
              hipStream_t st, int ode_derivative = 0) {
   const int C = w.cand.cout;
-  const bool pre = rs && pregate((long)n * H * W, w.cand);
-  ConvProblem a = problem(w.gates, x, s, g, n, H, W);
-  if (pre) { a.out2 = rs; a.out2_cs = C; a.e1 = s; a.e1_cs = C; a.gate_from = C; }
-  SF_TRY(run1(a, EPI_AFFINE, st));
-  ConvProblem b = problem(w.cand, x, pre ? rs : s, out, n, H, W);
-  if (!pre) { b.gate = g; b.gate_cs = 2 * C; b.gate_co = C; }
-  b.e0 = g; b.e0_cs = 2 * C; b.e1 = s; b.e1_cs = C;
+  if (!(rs && pregate((long)n * H * W, w.cand))) rs = nullptr;
+  SF_TRY(run1(gates_problem(w.gates, x, s, g, s, rs, C, n, H, W), EPI_AFFINE, st));
+  ConvProblem b = cand_problem(w.cand, x, s, rs, out, g, C, n, H, W);
   b.mode = ode_derivative ? 1 : 0;
   return run1(b, EPI_BLEND, st);
 }
@@ -50,28 +59,6 @@ struct CellBufs {
     return A.ok();
   }
 };
-void cell_gate_problems(const sf_dual_w& w, const float* x, const float* s, const CellBufs& b, bool pre, int B, int H, int W,
-                        ConvProblem& g1, ConvProblem& g2) {
-  const int C = w.C;
-  g1 = problem(w.gates1, x, s, b.g1, B, H, W);
-  g2 = problem(w.gates2, s, nullptr, b.g2, B, H, W);   // cell 2 sees cat[s,s]: duplicate input folded into the packed weights
-  if (pre) {
-    g1.out2 = b.rs1; g1.out2_cs = C; g1.e1 = s; g1.e1_cs = C; g1.gate_from = C;
-    g2.out2 = b.rs2; g2.out2_cs = C; g2.e1 = s; g2.e1_cs = C; g2.gate_from = C;
-  }
-}
-void cell_cand_problems(const sf_dual_w& w, const float* x, const float* s, const CellBufs& b, bool pre, int B, int H, int W,
-                        ConvProblem& c1, ConvProblem& c2) {
-  const int C = w.C;
-  c1 = problem(w.cand1, x, pre ? b.rs1 : s, b.h1, B, H, W);
-  c1.e0 = b.g1; c1.e0_cs = 2 * C; c1.e1 = s; c1.e1_cs = C;
-  c2 = problem(w.cand2, s, pre ? b.rs2 : s, b.h2, B, H, W);
-  c2.e0 = b.g2; c2.e0_cs = 2 * C; c2.e1 = s; c2.e1_cs = C;
-  if (!pre) {
-    c1.gate = b.g1; c1.gate_cs = 2 * C; c1.gate_co = C;
-    c2.gate = b.g2; c2.gate_cs = 2 * C; c2.gate_co = C;
-  }
-}
 // Small-P kernel: a 1x1 + LayerNorm + GELU layer `q` (weights w1) that follows the LayerNorm layer ps[0] is applied to ps[0]'s
 // tile before it leaves the workgroup (conv_sp.hip, ConvProblem::fuse_*); ps[0]'s own output is then not stored.  Returns
 // whether the launch of ps carries q.
@@ -128,6 +115,47 @@ struct Side {                // extra problems for infer_state's launches (AFFIN
   ConvProblem p[3];
   int n;                     // 2 or 3
 };
+bool carries_gates1_s(const sf_dual_w& w) { return w.gates1_x.w && w.gates1_s.w && tune().pipe >= 2; }
+
+// ---- The four launch groups of the carried form, each built in ONE place: infer_state and dual_cell issue what these builders return, and
+// carry_ok asks sp_takes about the same groups (with placeholder pointers).
+// the two side problems of cell `w` on state `s` (= the output of the cell before it)
+void side_problems(const sf_dual_w& w, const float* s, const Carry& c, int B, int H, int W, Side& sd) {
+  sd.p[0] = gates_problem(w.gates2, s, nullptr, c.g2, s, c.rs2, w.C, B, H, W);
+  sd.p[1] = cand_problem(w.cand2, s, s, c.rs2, c.h2, c.g2, w.C, B, H, W);
+  sd.p[1].mode = 4;          // blend inside an AFFINE launch
+  sd.n = 2;
+  if (c.g1s && carries_gates1_s(w)) {      // gates1 = sigmoid(W_x x + [W_s s] + b): the bracket now, raw
+    sd.p[2] = problem(w.gates1_s, s, nullptr, c.g1s, B, H, W);
+    sd.n = 3;
+  }
+}
+// infer_state launch 1: rb0.conv1 + rb0.proj [+ gates2 of the next cell].  Launch 2: rb0.conv2 (+ residual, channel sums) [+ cand2 of the next
+// cell, + the state half of its gates1] — without its scratch pointers, which no launch decision reads: infer_state sizes its scratch by the
+// tile width of this launch and fills them in afterwards.  Return the number of problems.
+int infer_group1(const sf_pmodel_w& w, const float* s, float* a, float* pr, const Side* side, int B, int H, int W, ConvProblem* ps) {
+  ps[0] = problem(w.rb0.conv1, s, nullptr, a, B, H, W);
+  ps[1] = problem(w.rb0.proj, s, nullptr, pr, B, H, W);
+  if (side) ps[2] = side->p[0];
+  return side ? 3 : 2;
+}
+int infer_group2(const sf_pmodel_w& w, const Side* side, int B, int H, int W, ConvProblem* ps) {
+  ps[0] = problem(w.rb0.conv2, nullptr, nullptr, nullptr, B, H, W);
+  if (side) { ps[1] = side->p[1]; ps[2] = side->p[2]; }
+  return side ? side->n : 1;
+}
+// the carried cell's gates launch: gates1, or its x half on top of the carried state half (acc_in) ...
+ConvProblem carried_gates(const sf_dual_w& w, const float* x, const float* s, float* g1, float* rs1, const float* g1s, int B, int H, int W) {
+  ConvProblem g = gates_problem(g1s ? w.gates1_x : w.gates1, x, g1s ? nullptr : s, g1, s, rs1, w.C, B, H, W);
+  if (g1s) { g.acc_in = g1s; g.acc_cs = 2 * w.C; }
+  return g;
+}
+// ... and its candidate launch: candidate of cell 1 + blend beside rnn_state2 = conv_decoder_2(h2) of the carried branch
+void carried_cand(const sf_dual_w& w, const float* x, const float* s, const CellBufs& b, const float* h2, int B, int H, int W, ConvProblem* ps) {
+  ps[0] = cand_problem(w.cand1, x, s, b.rs1, b.h1, b.g1, w.C, B, H, W);
+  ps[0].mode = 4;
+  ps[1] = problem(w.dec2, h2, nullptr, b.r2, B, H, W);
+}
 
 bool carry_ok(const sf_dual_w& w, const sf_pmodel_w& pm, int B, int H, int W) {
   const long P = (long)B * H * W;
@@ -137,43 +165,20 @@ bool carry_ok(const sf_dual_w& w, const sf_pmodel_w& pm, int B, int H, int W) {
   if (!(tune().pipe && B == 1 && P < tune().sp_max_p && tune().sp && pregate(P, w.cand1) && pregate(P, w.cand2))) return false;
   if (!pm.rb0.proj.w) return false;
   // The launch GROUPS the carried form issues must all be ones the small-P kernel takes (its AFFINE epilogue alone has the blend
-  // mode and acc_in; run() refuses them elsewhere and the rollout would fail instead of falling back — ADVICE r3).  Built here with
-  // the pointers that decide sp_takes set to a non-null placeholder: sp_takes never dereferences them.
+  // mode and acc_in; run() refuses them elsewhere and the rollout would fail instead of falling back — ADVICE r3).  The groups above with
+  // every buffer a non-null placeholder: sp_takes never dereferences them.
   float* const ph = reinterpret_cast<float*>(uintptr_t(64));
-  auto prob = [&](const sf_conv_w& c, bool two_inputs) { return problem(c, ph, two_inputs ? ph : nullptr, ph, B, H, W); };
+  const Carry c = {ph, ph, ph, carries_gates1_s(w) ? ph : nullptr};
+  const CellBufs b = {ph, ph, ph, ph, ph, ph, ph, ph, ph, ph};
+  Side sd = {};
+  side_problems(w, ph, c, B, H, W, sd);
   ConvProblem g[3];
-  // infer_state launch 1: rb0.conv1 + rb0.proj + gates2 (with the pre-gated state as second output)
-  g[0] = prob(pm.rb0.conv1, false); g[1] = prob(pm.rb0.proj, false); g[2] = prob(w.gates2, false); g[2].out2 = ph; g[2].e1 = ph;
-  if (!sp_takes(g, 3, EPI_AFFINE)) return false;
-  // launch 2: rb0.conv2 (+ residual, channel sums) + cand2 (blend mode) [+ the state half of gates1]
-  g[0] = prob(pm.rb0.conv2, false); g[0].add = ph; g[0].chansum = ph;
-  g[1] = prob(w.cand2, true); g[1].e0 = ph; g[1].e1 = ph; g[1].mode = 4;
-  int n2 = 2;
-  if (w.gates1_x.w && w.gates1_s.w && tune().pipe >= 2) { g[2] = prob(w.gates1_s, false); n2 = 3; }
-  if (!sp_takes(g, n2, EPI_AFFINE)) return false;
-  // the next cell: gates1 (x half with acc_in when the state half is carried), then cand1 (blend mode) + conv_decoder_2
-  g[0] = n2 == 3 ? prob(w.gates1_x, false) : prob(w.gates1, true);
-  g[0].out2 = ph; g[0].e1 = ph; if (n2 == 3) g[0].acc_in = ph;
+  if (!sp_takes(g, infer_group1(pm, ph, ph, ph, &sd, B, H, W, g), EPI_AFFINE)) return false;
+  if (!sp_takes(g, infer_group2(pm, &sd, B, H, W, g), EPI_AFFINE)) return false;
+  g[0] = carried_gates(w, ph, ph, ph, ph, c.g1s, B, H, W);      // the next cell
   if (!sp_takes(g, 1, EPI_AFFINE)) return false;
-  g[0] = prob(w.cand1, true); g[0].e0 = ph; g[0].e1 = ph; g[0].mode = 4;
-  g[1] = prob(w.dec2, false);
+  carried_cand(w, ph, ph, b, ph, B, H, W, g);
   return sp_takes(g, 2, EPI_AFFINE);
-}
-// the two side problems of cell `w` on state `s` (= the output of the cell before it)
-void side_problems(const sf_dual_w& w, const float* s, const Carry& c, int B, int H, int W, Side& sd) {
-  const int C = w.C;
-  ConvProblem& g2 = sd.p[0];
-  g2 = problem(w.gates2, s, nullptr, c.g2, B, H, W);
-  g2.out2 = c.rs2; g2.out2_cs = C; g2.e1 = s; g2.e1_cs = C; g2.gate_from = C;
-  ConvProblem& c2 = sd.p[1];
-  c2 = problem(w.cand2, s, c.rs2, c.h2, B, H, W);
-  c2.e0 = c.g2; c2.e0_cs = 2 * C; c2.e1 = s; c2.e1_cs = C;
-  c2.mode = 4;               // blend inside an AFFINE launch
-  sd.n = 2;
-  if (c.g1s && w.gates1_x.w && w.gates1_s.w && tune().pipe >= 2) {      // gates1 = sigmoid(W_x x + [W_s s] + b): the bracket now, raw
-    sd.p[2] = problem(w.gates1_s, s, nullptr, c.g1s, B, H, W);
-    sd.n = 3;
-  }
 }
 
 // B images (samples) are processed as one pixel space; coef_stride = floats between the
@@ -189,24 +194,17 @@ int dual_cell(const sf_dual_w& w, const float* x, const float* s, float* out, in
   ConvProblem ps[2];
   if (carry) {
     if (!pre) return SF_ERR_INVALID;
-    ConvProblem unused;
-    cell_gate_problems(w, x, s, b, pre, B, H, W, ps[0], unused);
-    if (carry->g1s) {                                               // x half only; the state half is carried
-      ConvProblem gx = problem(w.gates1_x, x, nullptr, b.g1, B, H, W);
-      gx.out2 = ps[0].out2; gx.out2_cs = ps[0].out2_cs; gx.e1 = ps[0].e1; gx.e1_cs = ps[0].e1_cs; gx.gate_from = ps[0].gate_from;
-      gx.acc_in = carry->g1s; gx.acc_cs = 2 * C;
-      ps[0] = gx;
-    }
-    SF_TRY(run(ps, 1, EPI_AFFINE, st));                             // gates of cell 1
-    cell_cand_problems(w, x, s, b, pre, B, H, W, ps[0], unused);
-    ps[0].mode = 4;                                                 // candidate of cell 1 + blend ...
-    ps[1] = problem(w.dec2, carry->h2, nullptr, b.r2, B, H, W);     // ... beside rnn_state2 = conv_decoder_2(h2)
+    SF_TRY(run1(carried_gates(w, x, s, b.g1, b.rs1, carry->g1s, B, H, W), EPI_AFFINE, st));      // gates of cell 1
+    carried_cand(w, x, s, b, carry->h2, B, H, W, ps);
     SF_TRY(run(ps, 2, EPI_AFFINE, st));
     return cell_tail(w, s, out, derivative, base, coef, coef_stride, out2, acc2, b, B, H, W, st);
   }
-  cell_gate_problems(w, x, s, b, pre, B, H, W, ps[0], ps[1]);     // gates of both cells in one launch
+  float *rs1 = pre ? b.rs1 : nullptr, *rs2 = pre ? b.rs2 : nullptr;
+  ps[0] = gates_problem(w.gates1, x, s, b.g1, s, rs1, C, B, H, W);             // gates of both cells in one launch
+  ps[1] = gates_problem(w.gates2, s, nullptr, b.g2, s, rs2, C, B, H, W);       // cell 2 sees cat[s,s]: duplicate input folded into the packed weights
   SF_TRY(run(ps, 2, EPI_AFFINE, st));
-  cell_cand_problems(w, x, s, b, pre, B, H, W, ps[0], ps[1]);     // candidates + blend
+  ps[0] = cand_problem(w.cand1, x, s, rs1, b.h1, b.g1, C, B, H, W);            // candidates + blend
+  ps[1] = cand_problem(w.cand2, s, s, rs2, b.h2, b.g2, C, B, H, W);
   SF_TRY(run(ps, 2, EPI_BLEND, st));
   SF_TRY(run1(problem(w.dec2, b.h2, nullptr, b.r2, B, H, W), EPI_AFFINE, st));   // rnn_state2 = conv_decoder_2(h2)
   return cell_tail(w, s, out, derivative, base, coef, coef_stride, out2, acc2, b, B, H, W, st);
@@ -233,10 +231,11 @@ int infer_state(const sf_pmodel_w& w, const float* s, const float* eps, float* p
   // gate at 200x200).  Several samples (tiles straddle images): per-image slab sums of the tensor.  All fixed-order.
   const bool tiles = (B == 1);
   const bool two_level = tiles && P >= 8192;
-  // rows of per-tile channel sums each SE producer writes (its kernel's pixel tile)
-  ConvProblem probe1[3] = {problem(w.rb0.conv2, s, nullptr, nullptr, B, H, W), ConvProblem(), ConvProblem()}, probe2 = problem(w.rb1.conv2, s, nullptr, nullptr, B, H, W);
-  if (side) { probe1[1] = side->p[1]; probe1[2] = side->p[2]; }      // they ride in rb0.conv2's launch
-  const int tpx1 = chansum_tile_px(probe1, side ? side->n : 1, EPI_AFFINE), tpx2 = chansum_tile_px(&probe2, 1, EPI_AFFINE);
+  // The launches that write per-tile channel sums, built before the scratch: their kernel's pixel tile (the whole group decides it: the side
+  // problems ride in rb0.conv2's launch) says how many rows of sums each SE producer writes
+  ConvProblem ps[3], l2[3], c4 = problem(w.rb1.conv2, nullptr, nullptr, nullptr, B, H, W);
+  const int n2 = infer_group2(w, side, B, H, W, l2);
+  const int tpx1 = chansum_tile_px(l2, n2, EPI_AFFINE), tpx2 = chansum_tile_px(&c4, 1, EPI_AFFINE);
   const int nt1 = tiles ? (P + tpx1 - 1) / tpx1 : SE_SLABS, nt2 = tiles ? (P + tpx2 - 1) / tpx2 : SE_SLABS;
   float* a = A.take((size_t)P * C);
   float* pr = A.take((size_t)P * C2);
@@ -263,16 +262,9 @@ int infer_state(const sf_pmodel_w& w, const float* s, const float* eps, float* p
     }
     return SF_OK;
   };
-  ConvProblem ps[3];
-  ps[0] = problem(w.rb0.conv1, s, nullptr, a, B, H, W);
-  ps[1] = problem(w.rb0.proj, s, nullptr, pr, B, H, W);
-  if (side) ps[2] = side->p[0];
-  SF_TRY(run(ps, side ? 3 : 2, EPI_AFFINE, st));
-  ConvProblem c2 = problem(w.rb0.conv2, a, nullptr, y1, B, H, W);
-  c2.add = pr; c2.chansum = tiles ? cs1 : nullptr;
-  ps[0] = c2;
-  if (side) { ps[1] = side->p[1]; ps[2] = side->p[2]; }
-  SF_TRY(run(ps, side ? side->n : 1, EPI_AFFINE, st));
+  SF_TRY(run(ps, infer_group1(w, s, a, pr, side, B, H, W, ps), EPI_AFFINE, st));
+  l2[0].in0 = a; l2[0].out = y1; l2[0].add = pr; l2[0].chansum = tiles ? cs1 : nullptr;
+  SF_TRY(run(l2, n2, EPI_AFFINE, st));
   // SE gates.  One sample on the small-P kernel: the consuming layer computes the gate in its prologue from the
   // producer's per-tile channel sums (two launches fewer per infer_state); otherwise the gate kernel
   ConvProblem c3 = problem(w.rb1.conv1, y1, nullptr, b, B, H, W);
@@ -285,8 +277,7 @@ int infer_state(const sf_pmodel_w& w, const float* s, const float* eps, float* p
     c3.in_scale = sc1;
   }
   SF_TRY(run1(c3, EPI_AFFINE, st));
-  ConvProblem c4 = problem(w.rb1.conv2, b, nullptr, y2, B, H, W);
-  c4.add = y1; c4.add_scale = sc1; c4.chansum = tiles ? cs2 : nullptr;
+  c4.in0 = b; c4.out = y2; c4.add = y1; c4.add_scale = sc1; c4.chansum = tiles ? cs2 : nullptr;
   SF_TRY(run1(c4, EPI_AFFINE, st));
   ConvProblem c5 = problem(w.last, y2, nullptr, p_out, B, H, W);
   c5.e0 = eps; c5.out2 = q_out; c5.philox = philox; c5.draw = draw;
@@ -302,58 +293,63 @@ int infer_state(const sf_pmodel_w& w, const float* s, const float* eps, float* p
   return run1(c5, EPI_SAMPLE, st);
 }
 
-// temporal_ode_bayes.py:436-461 (+ build-defined RK4).  `zeros`: [P][C] zero tensor (IMPUTE=False).
-// Scratch: k (P*C), pk (P*C), acc (P*C) + cell/infer workspaces.
-int ode_step(const sf_dual_w& gc, const sf_pmodel_w& pm, int solver, int impute, const float* s_in,
-             const float* p_in, const float* coef, int coef_stride, const float* eps, float* s_out, float* p_out,
-             const float* zeros, int skip_dead_infer, int B, int H, int W, Arena& A0, hipStream_t st) {
-  const int C = gc.C;
-  const size_t PC = (size_t)B * H * W * C;
-  const float* x = impute ? p_in : zeros;
-  auto cell = [&](const float* xx, const float* ss, float* out, const float* base, const float* cf, float* out2,
-                  int acc2) {
-    Arena A = A0;
-    return dual_cell(gc, xx, ss, out, 1, base, cf, coef_stride, out2, acc2, B, H, W, A, st);
-  };
-  auto infer = [&](const float* ss, int draw, float* po) {
-    Arena A = A0;
-    return infer_state(pm, ss, eps + (size_t)draw * PC, po, nullptr, B, H, W, A, st);
-  };
+// ---- solver stages ----------------------------------------------------------------------------------------------------------
+// A stage = one dual cell (ODE derivative + integrator update, or a Bayesian jump) followed by an optional infer_state.
+struct Stage {              // (the defaults: an inner stage of an ODE step)
+  const sf_dual_w* w = nullptr;
+  const float* x = nullptr; const float* s = nullptr; float* out = nullptr;
+  int derivative = 1; const float* base = nullptr; const float* coef = nullptr; float* out2 = nullptr; int acc2 = 0;
+  bool infer_after = true; int draw = 0; float* p_out = nullptr;
+  int op_end = -1;      // index of the op this stage completes (-1: an inner solver stage)
+};
+struct StageBufs { float *k, *pk, *acc, *s3; };      // [P][C] each; Euler uses none
+
+// One ODE step (temporal_ode_bayes.py:436-461, + build-defined RK4) of cell `w` as 1, 2 or 4 stages appended to `out`: input x (the
+// imputed input, or zeros with IMPUTE off), state s -> s2, and infer_state(s2) -> p2 where need_p.  cf: the step's coefficient record
+// (SF_COEF_STRIDE in sfnative.h); draws are numbered from `draw`.  Returns the number of draws (a skipped infer_state keeps its number).
+int step_stages(int solver, const sf_dual_w* w, const float* x, const float* s, float* s2, float* p2, bool need_p, const float* cf, int draw,
+                int op, const StageBufs& b, std::vector<Stage>& out) {
   if (solver == SF_SOLVER_EULER) {
-    SF_TRY(cell(x, s_in, s_out, s_in, coef + 0, nullptr, 0));
-    if (!(skip_dead_infer && !impute)) SF_TRY(infer(s_out, 0, p_out));
-    return SF_OK;
+    out.push_back({.w = w, .x = x, .s = s, .out = s2, .base = s, .coef = cf + 0, .infer_after = need_p, .draw = draw, .p_out = p2, .op_end = op});
+    return 1;
   }
-  float* k = A0.take(PC);
-  float* pk = A0.take(PC);
-  float* acc = A0.take(PC);
-  if (!A0.ok()) return SF_ERR_WORKSPACE;
   if (solver == SF_SOLVER_MIDPOINT) {
-    SF_TRY(cell(x, s_in, k, s_in, coef + 1, nullptr, 0));              // k = s + dt/2 f(p, s)
-    SF_TRY(infer(k, 0, pk));            // :452 — evaluated even when IMPUTE is off (only :443's input is zeroed)
-    SF_TRY(cell(pk, k, s_out, s_in, coef + 0, nullptr, 0));            // s' = s + dt f(pk, k)
-    if (!(skip_dead_infer && !impute)) SF_TRY(infer(s_out, 1, p_out));
-    return SF_OK;
+    // k = s + dt/2 f(p, s); pk = infer(k) (:452 — evaluated even when IMPUTE is off: only :443's input is zeroed); s' = s + dt f(pk, k)
+    out.push_back({.w = w, .x = x, .s = s, .out = b.k, .base = s, .coef = cf + 1, .draw = draw, .p_out = b.pk});
+    out.push_back({.w = w, .x = b.pk, .s = b.k, .out = s2, .base = s, .coef = cf + 0, .infer_after = need_p, .draw = draw + 1, .p_out = p2, .op_end = op});
+    return 2;
   }
-  if (solver == SF_SOLVER_RK4) {
-    // coef = {dt, dt/2, dt/6, dt/3}.  acc = s + dt/6 k1 + dt/3 k2 + dt/3 k3 ; s' = acc + dt/6 k4
-    float* s2 = k;
-    float* s3 = A0.take(PC);
+  // RK4: cf = {dt, dt/2, dt/6, dt/3, ...}.  acc = s + dt/6 k1 + dt/3 k2 + dt/3 k3 ; s' = acc + dt/6 k4.  Stage coefficient pairs {out coef,
+  // out2 coef} follow the four scalars in the record: {dt/2, dt/6}, {dt/2, dt/3}, {dt, dt/3}, {dt/6, 0}; stage inputs always come from
+  // infer_state, as in midpoint; the fourth stage state reuses k
+  const float* rk = cf + 4;
+  out.push_back({.w = w, .x = x, .s = s, .out = b.k, .base = s, .coef = rk + 0, .out2 = b.acc, .draw = draw, .p_out = b.pk});
+  out.push_back({.w = w, .x = b.pk, .s = b.k, .out = b.s3, .base = s, .coef = rk + 2, .out2 = b.acc, .acc2 = 1, .draw = draw + 1, .p_out = b.pk});
+  out.push_back({.w = w, .x = b.pk, .s = b.s3, .out = b.k, .base = s, .coef = rk + 4, .out2 = b.acc, .acc2 = 1, .draw = draw + 2, .p_out = b.pk});
+  out.push_back({.w = w, .x = b.pk, .s = b.k, .out = s2, .base = b.acc, .coef = rk + 6, .infer_after = need_p, .draw = draw + 3, .p_out = p2, .op_end = op});
+  return 4;
+}
+
+// One stand-alone step: its stages one after the other, every cell and every infer_state on its own (no carried branch, no persistent flow).
+// `zeros`: [P][C] zero tensor (IMPUTE=False).  Scratch: k, pk, acc, s3 (P*C each; Euler: none) + cell/infer workspaces.
+int ode_step(const sf_dual_w& gc, const sf_pmodel_w& pm, int solver, int impute, const float* s_in, const float* p_in, const float* coef,
+             int coef_stride, const float* eps, float* s_out, float* p_out, const float* zeros, int B, int H, int W, Arena& A0, hipStream_t st) {
+  if (solver != SF_SOLVER_EULER && solver != SF_SOLVER_MIDPOINT && solver != SF_SOLVER_RK4) return SF_ERR_INVALID;
+  const size_t PC = (size_t)B * H * W * gc.C;
+  StageBufs sb = {};
+  if (solver != SF_SOLVER_EULER) {
+    sb.k = A0.take(PC); sb.pk = A0.take(PC); sb.acc = A0.take(PC);
+    if (solver == SF_SOLVER_RK4) sb.s3 = A0.take(PC);
     if (!A0.ok()) return SF_ERR_WORKSPACE;
-    // stage coefficient pairs {out coef, out2 coef} follow the four scalars in the coef record:
-    // {dt/2, dt/6}, {dt/2, dt/3}, {dt, dt/3}, {dt/6, 0}   (see SF_COEF_STRIDE in sfnative.h)
-    const float* rk = coef + 4;
-    SF_TRY(cell(x, s_in, s2, s_in, rk + 0, acc, 0));
-    SF_TRY(infer(s2, 0, pk));           // stage inputs always come from infer_state, as in midpoint
-    SF_TRY(cell(pk, s2, s3, s_in, rk + 2, acc, 1));
-    SF_TRY(infer(s3, 1, pk));
-    SF_TRY(cell(pk, s3, s2, s_in, rk + 4, acc, 1));   // s4 reuses s2
-    SF_TRY(infer(s2, 2, pk));
-    SF_TRY(cell(pk, s2, s_out, acc, rk + 6, nullptr, 0));
-    if (!(skip_dead_infer && !impute)) SF_TRY(infer(s_out, 3, p_out));
-    return SF_OK;
   }
-  return SF_ERR_INVALID;
+  std::vector<Stage> stages;
+  step_stages(solver, &gc, impute ? p_in : zeros, s_in, s_out, p_out, true, coef, 0, 0, sb, stages);
+  for (const Stage& g : stages) {
+    Arena Ac = A0, Ai = A0;
+    SF_TRY(dual_cell(*g.w, g.x, g.s, g.out, g.derivative, g.base, g.coef, coef_stride, g.out2, g.acc2, B, H, W, Ac, st));
+    if (g.infer_after) SF_TRY(infer_state(pm, g.out, eps + (size_t)g.draw * PC, g.p_out, nullptr, B, H, W, Ai, st));
+  }
+  return SF_OK;
 }
 
 size_t ode_step_ws_floats(int C, int P) {
@@ -496,9 +492,10 @@ int sf_upsample_bilinear2_add_fwd(const float* in, const float* skip, float* out
   return SF_OK;
 }
 
-/* sparse (gather) convolution: out[j] = act(scale * sum_t W_t . feats[nbr[j][t]] + bias) (+ add), see sfnative.h */
-int sf_sparse_conv_fwd(const sf_conv_w* w, const float* feats, int feats_cs, int n_in, const int32_t* nbr, int n_out,
-                       const float* add, int act_after_add, float* out, float* ws, size_t ws_bytes, void* stream) {
+/* sparse (gather) convolution: out[j] = act(scale * sum_t W_t . feats[nbr[j][t]] + bias) (+ add), see sfnative.h; with an optional tap
+ * mask: tile_mask64[i] bit t = some row of 64 i .. 64 i + 63 has an input row under tap t */
+int sf_sparse_conv_masked_fwd(const sf_conv_w* w, const float* feats, int feats_cs, int n_in, const int32_t* nbr, const uint32_t* tile_mask64, int n_out,
+                              const float* add, int act_after_add, float* out, float* ws, size_t ws_bytes, void* stream) {
   if (!w || !valid_w(*w) || !feats || !nbr || !out || n_out < 0 || n_in < 1 || w->kw != 1 || w->c1 != 0 || feats_cs < w->c0 ||
       (feats_cs % 4))
     return SF_ERR_INVALID;
@@ -509,28 +506,14 @@ int sf_sparse_conv_fwd(const sf_conv_w* w, const float* feats, int feats_cs, int
   p.in0_cs = feats_cs;
   p.Hout = 1; p.Wout = n_out;
   p.gather = nbr;
-  p.add = add;
-  if (act_after_add) p.mode |= 2;
-  return run1(p, EPI_AFFINE, (hipStream_t)stream);
-}
-
-/* the same with a tap mask: tile_mask64[i] bit t = some row of 64 i .. 64 i + 63 has an input row under tap t (see sfnative.h) */
-int sf_sparse_conv_masked_fwd(const sf_conv_w* w, const float* feats, int feats_cs, int n_in, const int32_t* nbr, const uint32_t* tile_mask64, int n_out,
-                              const float* add, int act_after_add, float* out, float* ws, size_t ws_bytes, void* stream) {
-  if (!w || !valid_w(*w) || !feats || !nbr || !out || n_out < 0 || n_in < 1 || w->kw != 1 || w->c1 != 0 || feats_cs < w->c0 ||
-      (feats_cs % 4))
-    return SF_ERR_INVALID;
-  if (n_out == 0) return SF_OK;
-  Arena A(ws, ws_bytes);
-  SplitScope sp(A, (hipStream_t)stream);
-  ConvProblem p = problem(*w, feats, nullptr, out, 1, 1, n_in, 0);
-  p.in0_cs = feats_cs;
-  p.Hout = 1; p.Wout = n_out;
-  p.gather = nbr;
   p.tap_mask = tile_mask64; p.tap_mask_n = tile_mask64 ? (n_out + 63) / 64 : 0;
   p.add = add;
   if (act_after_add) p.mode |= 2;
   return run1(p, EPI_AFFINE, (hipStream_t)stream);
+}
+int sf_sparse_conv_fwd(const sf_conv_w* w, const float* feats, int feats_cs, int n_in, const int32_t* nbr, int n_out,
+                       const float* add, int act_after_add, float* out, float* ws, size_t ws_bytes, void* stream) {
+  return sf_sparse_conv_masked_fwd(w, feats, feats_cs, n_in, nbr, nullptr, n_out, add, act_after_add, out, ws, ws_bytes, stream);
 }
 
 /* per-image channel means of an NHWC tensor (fixed-order two-level sum: reproducible) */
@@ -574,24 +557,23 @@ int sf_conv2d_repeat(const sf_conv_w* w, const float* in0, const float* in1, con
 size_t sf_gru_cell_ws_bytes(int C, int n_img, int H, int W) {
   return (al((size_t)n_img * H * W * 2 * C) + al((size_t)n_img * H * W * C)) * sizeof(float);
 }
-int sf_gru_cell_fwd(const sf_gru_w* w, const float* x, const float* s, float* out, int n_img, int H, int W, float* ws,
-                    size_t ws_bytes, void* stream) {
+static int gru_cell_entry(const sf_gru_w* w, const float* x, const float* s, float* out, int n_img, int H, int W, float* ws, size_t ws_bytes,
+                          void* stream, int ode_derivative) {
   if (!w || !x || !s || !out || !valid_w(w->gates) || !valid_w(w->cand)) return SF_ERR_INVALID;
   Arena A(ws, ws_bytes);
   float* g = A.take((size_t)n_img * H * W * 2 * w->cand.cout);
   float* rs = A.take((size_t)n_img * H * W * w->cand.cout);
   if (!A.ok()) return SF_ERR_WORKSPACE;
-  return gru_cell(*w, x, s, out, g, rs, n_img, H, W, (hipStream_t)stream, 0);
+  return gru_cell(*w, x, s, out, g, rs, n_img, H, W, (hipStream_t)stream, ode_derivative);
+}
+int sf_gru_cell_fwd(const sf_gru_w* w, const float* x, const float* s, float* out, int n_img, int H, int W, float* ws,
+                    size_t ws_bytes, void* stream) {
+  return gru_cell_entry(w, x, s, out, n_img, H, W, ws, ws_bytes, stream, 0);
 }
 // SpatialGRUODECell.forward — temporal_ode_bayes.py:35-61: dh = u * (h~ - s)
 int sf_gru_ode_cell_fwd(const sf_gru_w* w, const float* x, const float* s, float* out, int n_img, int H, int W, float* ws,
                         size_t ws_bytes, void* stream) {
-  if (!w || !x || !s || !out || !valid_w(w->gates) || !valid_w(w->cand)) return SF_ERR_INVALID;
-  Arena A(ws, ws_bytes);
-  float* g = A.take((size_t)n_img * H * W * 2 * w->cand.cout);
-  float* rs = A.take((size_t)n_img * H * W * w->cand.cout);
-  if (!A.ok()) return SF_ERR_WORKSPACE;
-  return gru_cell(*w, x, s, out, g, rs, n_img, H, W, (hipStream_t)stream, 1);
+  return gru_cell_entry(w, x, s, out, n_img, H, W, ws, ws_bytes, stream, 1);
 }
 
 size_t sf_spatial_gru_ws_bytes(int C, int n_img, int H, int W) {
@@ -710,22 +692,14 @@ int sf_ode_step_fwd(const sf_dual_w* gru_c, const sf_pmodel_w* pm, int solver, i
   float* zeros = A.take(PC);
   if (!A.ok()) return SF_ERR_WORKSPACE;
   if (!impute) SF_HIP(zero_fill(zeros, al(PC) * sizeof(float), st));
-  return ode_step(*gru_c, *pm, solver, impute, state_in, p_in, coef, 0, eps, state_out, p_out, zeros, 0, n_img, H, W, A, st);
+  return ode_step(*gru_c, *pm, solver, impute, state_in, p_in, coef, 0, eps, state_out, p_out, zeros, n_img, H, W, A, st);
 }
 
 // ---- rollout as a list of stages -----------------------------------------------------------------------------------------
-// A stage = one dual cell (ODE derivative + integrator update, or a Bayesian jump) followed by an optional infer_state.
 // (Measured and rejected, profiles/README.md "two-stream rollout": running gru_cell_2 / conv_decoder_2 of stage j+1 on a
 // second stream beside stage j's infer_state — they only need the state — made the 18-op rollout 11 % slower: every
 // small-P workgroup owns a whole CU, so the two chains take turns instead of overlapping, and the split launches lose
 // the grouping of the two gate / candidate convolutions.)
-struct Stage {
-  const sf_dual_w* w;
-  const float* x; const float* s; float* out;
-  int derivative; const float* base; const float* coef; float* out2; int acc2;
-  bool infer_after; int draw; float* p_out;
-  int op_end;      // index of the op this stage completes (-1: an inner solver stage)
-};
 
 // What a resumed segment takes over from / hands on to its neighbours besides the state and the imputed input: the carried branch 2
 // of the ODE cell that follows the boundary (struct Carry), [g2 2PC | g1s 2PC | rs2 PC | h2 PC] in caller memory.
@@ -742,7 +716,6 @@ Carry carry_view(float* base, size_t PC) {
   c.g2 = base; c.g1s = base + al(2 * PC); c.rs2 = base + 2 * al(2 * PC); c.h2 = c.rs2 + al(PC);
   return c;
 }
-bool carries_gates1_s(const sf_dual_w& w) { return w.gates1_x.w && w.gates1_s.w && tune().pipe >= 2; }
 
 size_t rollout_ws_floats(int C, int P) {
   const size_t cellw = dual_ws_floats(C, P), inf = infer_ws_floats(C, P);
@@ -801,13 +774,17 @@ int run_stages(const std::vector<Stage>& stages, const sf_pmodel_w& pm, const fl
 
 size_t sf_nnfo_rollout_ws_bytes(int C, int n_img, int H, int W) { return rollout_ws_floats(C, n_img * H * W) * sizeof(float); }
 size_t sf_nnfo_rollout_carry_bytes(int C, int n_img, int H, int W) { return carry_floats((size_t)n_img * H * W * C) * sizeof(float); }
+struct SegmentIO {      // what only a resumed segment is given (sfnative.h: sf_nnfo_rollout_resume_fwd)
+  const float* state_in = nullptr; const float* p_in = nullptr; const float* carry_in = nullptr; int draw_base = 0;
+  float* p_out = nullptr; float* carry_out = nullptr;
+};
 // One segment of the rollout.  state_in / p_in (NULL: zeros) are read, never written; draws are numbered from draw_base; p_out != NULL
-// keeps the infer_state of the last op.  The one-shot entry points are this with (NULL, NULL, NULL, 0, NULL, NULL).
+// keeps the infer_state of the last op.  The one-shot entry points are this with an empty SegmentIO.
 static int rollout_core(const sf_dual_w* gru_c, const sf_dual_w* gru_obs, const sf_pmodel_w* pm, int solver, int impute,
                         const int32_t* ops, int n_ops, const float* hx_obs, const float* eps, const unsigned long long* philox,
                         const float* coef, int coef_per_image, const int32_t* sel_nops, int n_targets, float* out_states,
-                        float* final_state, const float* state_in, const float* p_in, const float* carry_in, int draw_base,
-                        float* p_out, float* carry_out, int n_img, int H, int W, float* ws, size_t ws_bytes, void* stream) {
+                        float* final_state, int n_img, int H, int W, float* ws, size_t ws_bytes, void* stream, const SegmentIO& io = SegmentIO()) {
+  const auto [state_in, p_in, carry_in, draw_base, p_out, carry_out] = io;
   if (!gru_c || !gru_obs || !pm || (!ops && n_ops > 0) || (!eps && !philox) || n_img < 1 || n_ops < 0 || n_targets < 0 || draw_base < 0) return SF_ERR_INVALID;
   if (n_targets > 0 && (!sel_nops || !out_states)) return SF_ERR_INVALID;
   if ((carry_in && (!state_in || !p_in)) || (carry_out && (!p_out || n_ops == 0))) return SF_ERR_INVALID;      // (no op: no infer_state to compute the carry beside)
@@ -821,10 +798,7 @@ static int rollout_core(const sf_dual_w* gru_c, const sf_dual_w* gru_obs, const 
   float* zeros = A.take(PC);
   float* sbuf[2] = {A.take(PC), A.take(PC)};
   float* pbuf[2] = {A.take(PC), A.take(PC)};
-  float* k = A.take(PC);       // solver stages (midpoint / RK4)
-  float* pk = A.take(PC);
-  float* acc = A.take(PC);
-  float* s3 = A.take(PC);
+  const StageBufs sb = {A.take(PC), A.take(PC), A.take(PC), A.take(PC)};       // solver stages (midpoint / RK4)
   if (!A.ok()) return SF_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   SF_HIP(zero_fill(zeros, al(PC) * sizeof(float), st));
@@ -851,34 +825,14 @@ static int rollout_core(const sf_dual_w* gru_c, const sf_dual_w* gru_obs, const 
       // (the jump's imputed input replaces the current one in place; p_in itself is never written)
       float* pj = (last && p_out) ? p_out : pbuf[pi];
       if (!hx_obs) return SF_ERR_INVALID;      // (NULL is fine for a segment without jumps)
-      stages.push_back(Stage{gru_obs, hx_obs + (size_t)arg * PC, s, s2, 0, nullptr, nullptr, nullptr, 0, need_p, draw, pj, i});
+      stages.push_back({.w = gru_obs, .x = hx_obs + (size_t)arg * PC, .s = s, .out = s2, .derivative = 0, .infer_after = need_p, .draw = draw, .p_out = pj, .op_end = i});
       draw += 1;
       si ^= 1;
       s_cur = s2;
       if (need_p) p_cur = pj;
     } else if (kind == SF_OP_STEP) {
       if (!coef) return SF_ERR_INVALID;
-      const float* cf = coef + (size_t)arg * step_stride;
-      const float* x = impute ? p : zeros;
-      if (solver == SF_SOLVER_EULER) {
-        stages.push_back(Stage{gru_c, x, s, s2, 1, s, cf + 0, nullptr, 0, need_p, draw, p2, i});
-        draw += 1;
-      } else if (solver == SF_SOLVER_MIDPOINT) {
-        // k = s + dt/2 f(p, s); pk = infer(k) (:452 — evaluated even when IMPUTE is off); s' = s + dt f(pk, k)
-        stages.push_back(Stage{gru_c, x, s, k, 1, s, cf + 1, nullptr, 0, true, draw, pk, -1});
-        stages.push_back(Stage{gru_c, pk, k, s2, 1, s, cf + 0, nullptr, 0, need_p, draw + 1, p2, i});
-        draw += 2;
-      } else {
-        // RK4 (build-defined): acc = s + dt/6 k1 + dt/3 k2 + dt/3 k3 ; s' = acc + dt/6 k4.  Stage coefficient pairs
-        // {out coef, out2 coef} follow the four scalars in the coef record (SF_COEF_STRIDE in sfnative.h); stage inputs
-        // always come from infer_state, as in midpoint
-        const float* rk = cf + 4;
-        stages.push_back(Stage{gru_c, x, s, k, 1, s, rk + 0, acc, 0, true, draw, pk, -1});
-        stages.push_back(Stage{gru_c, pk, k, s3, 1, s, rk + 2, acc, 1, true, draw + 1, pk, -1});
-        stages.push_back(Stage{gru_c, pk, s3, k, 1, s, rk + 4, acc, 1, true, draw + 2, pk, -1});
-        stages.push_back(Stage{gru_c, pk, k, s2, 1, acc, rk + 6, nullptr, 0, need_p, draw + 3, p2, i});
-        draw += 4;
-      }
+      draw += step_stages(solver, gru_c, impute ? p : zeros, s, s2, p2, need_p, coef + (size_t)arg * step_stride, draw, i, sb, stages);
       si ^= 1;
       pi ^= 1;
       s_cur = s2;
@@ -909,7 +863,7 @@ int sf_nnfo_rollout_fwd(const sf_dual_w* gru_c, const sf_dual_w* gru_obs, const 
                         float* final_state, int n_img, int H, int W, float* ws, size_t ws_bytes, void* stream) {
   if (!eps || !ops || !hx_obs || !sel_nops || !out_states) return SF_ERR_INVALID;
   return rollout_core(gru_c, gru_obs, pm, solver, impute, ops, n_ops, hx_obs, eps, nullptr, coef, coef_per_image, sel_nops, n_targets,
-                      out_states, final_state, nullptr, nullptr, nullptr, 0, nullptr, nullptr, n_img, H, W, ws, ws_bytes, stream);
+                      out_states, final_state, n_img, H, W, ws, ws_bytes, stream);
 }
 // resumable form: see sfnative.h.  eps holds the segment's own draws (draw k of the segment reads eps[k]); draw_base keys the Philox form
 int sf_nnfo_rollout_resume_fwd(const sf_dual_w* gru_c, const sf_dual_w* gru_obs, const sf_pmodel_w* pm, int solver, int impute,
@@ -919,7 +873,7 @@ int sf_nnfo_rollout_resume_fwd(const sf_dual_w* gru_c, const sf_dual_w* gru_obs,
                                float* carry_out, int n_img, int H, int W, float* ws, size_t ws_bytes, void* stream) {
   if (!eps) return SF_ERR_INVALID;
   return rollout_core(gru_c, gru_obs, pm, solver, impute, ops, n_ops, hx_obs, eps, nullptr, coef, coef_per_image, sel_nops, n_targets,
-                      out_states, final_state, state_in, p_in, carry_in, draw_base, p_out, carry_out, n_img, H, W, ws, ws_bytes, stream);
+                      out_states, final_state, n_img, H, W, ws, ws_bytes, stream, {state_in, p_in, carry_in, draw_base, p_out, carry_out});
 }
 int sf_nnfo_rollout_resume_philox_fwd(const sf_dual_w* gru_c, const sf_dual_w* gru_obs, const sf_pmodel_w* pm, int solver, int impute,
                                       const int32_t* ops, int n_ops, const float* hx_obs, const uint64_t* philox_state, const float* coef,
@@ -928,8 +882,8 @@ int sf_nnfo_rollout_resume_philox_fwd(const sf_dual_w* gru_c, const sf_dual_w* g
                                       float* carry_out, int n_img, int H, int W, float* ws, size_t ws_bytes, void* stream) {
   if (!philox_state) return SF_ERR_INVALID;
   return rollout_core(gru_c, gru_obs, pm, solver, impute, ops, n_ops, hx_obs, nullptr, reinterpret_cast<const unsigned long long*>(philox_state),
-                      coef, coef_per_image, sel_nops, n_targets, out_states, final_state, state_in, p_in, carry_in, draw_base, p_out, carry_out,
-                      n_img, H, W, ws, ws_bytes, stream);
+                      coef, coef_per_image, sel_nops, n_targets, out_states, final_state, n_img, H, W, ws, ws_bytes, stream,
+                      {state_in, p_in, carry_in, draw_base, p_out, carry_out});
 }
 // the same with the Gaussian noise of infer_state generated in the sampling epilogue (Philox4x32-10, csrc/sf_math.h)
 int sf_nnfo_rollout_philox_fwd(const sf_dual_w* gru_c, const sf_dual_w* gru_obs, const sf_pmodel_w* pm, int solver, int impute,
@@ -938,8 +892,7 @@ int sf_nnfo_rollout_philox_fwd(const sf_dual_w* gru_c, const sf_dual_w* gru_obs,
                                int n_img, int H, int W, float* ws, size_t ws_bytes, void* stream) {
   if (!philox_state || !ops || !hx_obs || !sel_nops || !out_states) return SF_ERR_INVALID;
   return rollout_core(gru_c, gru_obs, pm, solver, impute, ops, n_ops, hx_obs, nullptr, reinterpret_cast<const unsigned long long*>(philox_state),
-                      coef, coef_per_image, sel_nops, n_targets, out_states, final_state, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
-                      n_img, H, W, ws, ws_bytes, stream);
+                      coef, coef_per_image, sel_nops, n_targets, out_states, final_state, n_img, H, W, ws, ws_bytes, stream);
 }
 int sf_infer_state_philox_fwd(const sf_pmodel_w* w, const float* s, const uint64_t* philox_state, int draw, float* p_out, float* q_out,
                               int n_img, int H, int W, float* ws, size_t ws_bytes, void* stream) {

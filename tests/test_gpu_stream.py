@@ -177,6 +177,41 @@ def test_segment_argument_rules():
     assert call([(1, 0)], None, st, p, None, None, carry) == -1                  # carry_out without p_out
 
 
+_STEP_NET = {}
+_STEP_CASES = ([(2, 8, 5, 7, s, i) for s in ("euler", "midpoint", "rk4") for i in (True, False)] +       # 70 pixels: a ragged last 64-pixel tile
+               [(2, 64, 10, 10, s, i) for s in ("euler", "midpoint", "rk4") for i in (True, False)] +    # the 7x7's K range split across workgroups
+               [(1, 8, 5, 7, "euler", i) for i in (True, False)])                                         # one latent (no carried branch: carry_in is NULL)
+
+
+@pytest.mark.parametrize("B,C,h,w,solver,impute", _STEP_CASES)
+def test_standalone_step_equals_one_step_segment_bitwise(B, C, h, w, solver, impute):
+    """sf_ode_step_fwd and a resumed segment of one SF_OP_STEP (state_in / p_in / p_out given, no carry, no targets, final_state as the
+    output) expand the step into the same solver stages: same launches on the same sizes, fixed-order reductions, so state and imputed
+    input are BITWISE equal."""
+    if C not in _STEP_NET:
+        _STEP_NET[C] = build_pair(C)[0]
+    ode, dev, L = _STEP_NET[C].gru_ode, torch.device("cuda"), _lib.lib()
+    s = (hashfill.normal("step_s", (B, h, w, C), 61) * 0.5).cuda()
+    p = (hashfill.normal("step_p", (B, h, w, C), 62) * 0.5).cuda()
+    eps = hashfill.normal("step_eps", (S.DRAWS_PER_STEP[solver], B, h, w, C), 63).cuda()
+    coef = torch.from_numpy(S.Schedule(dts=[0.05]).coef_array()).cuda()
+    weights = (ode.gru_c.packed().struct, ode.gru_obs.gru_d.packed().struct, ode.p_model.packed().struct)
+    s_a, p_a, s_b, p_b = (torch.full_like(s, float("nan")) for _ in range(4))
+    ws = runtime.workspace(L.sf_ode_step_ws_bytes(C, B, h, w), dev)
+    _lib.check(L.sf_ode_step_fwd(weights[0], weights[2], _lib.SOLVER[solver], int(impute), ptr(s), ptr(p), ptr(coef), ptr(eps), ptr(s_a), ptr(p_a),
+                                 B, h, w, ptr(ws), ws.numel() * 4, runtime.stream_ptr(dev)), "ode_step")
+    ops = np.asarray([_lib.OP_STEP, 0], dtype=np.int32)
+    ws = runtime.workspace(L.sf_nnfo_rollout_ws_bytes(C, B, h, w), dev)
+    _lib.check(L.sf_nnfo_rollout_resume_fwd(*weights, _lib.SOLVER[solver], int(impute), ops.ctypes.data_as(_lib.i32p), 1, None, ptr(eps), ptr(coef), 0,
+                                            None, 0, None, ptr(s_b), ptr(s), ptr(p), None, 0, ptr(p_b), None, B, h, w, ptr(ws), ws.numel() * 4,
+                                            runtime.stream_ptr(dev)), "resume")
+    d_s, d_p = maxabs(s_a, s_b), maxabs(p_a, p_b)
+    print(f"step vs one-step segment B={B} C={C} {h}x{w} {solver} impute={impute}: max-abs state {d_s:.3e}, p {d_p:.3e}")
+    assert torch.isfinite(s_a).all() and torch.isfinite(p_a).all()
+    assert torch.equal(s_a, s_b), d_s
+    assert torch.equal(p_a, p_b), d_p
+
+
 def _feed(sess, times, hx, upto=None):
     for i, t in enumerate(times[:upto]):
         sess.observe(t, hx[i])
