@@ -596,6 +596,29 @@ int sf_plan_metric_fwd(const float* trajs, const float* gt_trajs, long traj_stri
                        const float* dx, const float* bx, int B, int T, int H, int W, float* obj_col, float* obj_box_col, float* l2,
                        int64_t* total, void* stream);
 
+/* ---- the planner's trajectory sampler (streamingflow/utils/sampler.py:8-146 as datas/NuscenesData.py:526-551 calls it).  Device
+ * pointers throughout; both entry points enqueue only (no allocation, no synchronisation, nothing read back) and may be captured.
+ * sf_fresnel_fwd — S[i], C[i] = the Fresnel integrals int_0^z sin / cos(pi t^2 / 2) dt of z[i], i < n, in fp64 (scipy.special.fresnel's
+ *   convention): odd in z, within 1e-12 of scipy on [-4, 24] (measured: DESIGN §6b N6), the phase pi z^2 / 2 reduced exactly beyond,
+ *   +-1/2 for |z| >= 1e100, NaN for NaN.  SF_ERR_INVALID: a NULL pointer, n < 0.
+ * sf_plan_sample_fwd — per sample b < B, M rows of n_t points (x, y, heading) from speed v0 [B], curvature kappa [B], frame t0, n0
+ *   [B][2] (fp64) and uniforms [B][5][M] (fp64 in [0, 1): acceleration 10 (u - 0.5) + 2, random speed 15 u, speed choice (u >= 0.2
+ *   takes the random speed, else v0), alpha 74 u + 6, curve choice (u < 0.2: circle, else clothoid); the last two are indexed by curve,
+ *   n_left + n_right entries used).  Before the sort the rows are, for kappa > 0, [curves 0 .. n_left), n_straight lines, curves
+ *   [n_left, n_left + n_right) mirrored (-x, y, -heading)], otherwise [curves [n_left, n_left + n_right) mirrored, lines, curves
+ *   0 .. n_left)]; line i uses entry i of the first three draws, curve j entry n_straight + j.  Every row is evaluated at the n_t stamps
+ *   tt_kept (fp64; tt_kept[0] is the stamp whose point the clothoids are shifted by) and at t_key; the rows are ordered by x at t_key,
+ *   ascending and STABLY (equal keys keep their order before the sort), and written as out [B][M][n_t][3] fp32; order [B][M]
+ *   (may be NULL) receives each written row's position before the sort.  All arithmetic is fp64, cast at the store.  Non-finite inputs
+ *   give unspecified rows, never a write outside out / order.
+ *   SF_ERR_INVALID: a NULL pointer other than order, B / M / n_t < 1, B > 65535, a negative count, counts that do not sum to M;
+ *   SF_ERR_UNSUPPORTED: M > 4096; SF_ERR_WORKSPACE: ws_bytes < sf_plan_sample_ws_bytes(B, M, n_t) (0 for invalid sizes). */
+int sf_fresnel_fwd(const double* z, long n, double* S, double* C, void* stream);
+size_t sf_plan_sample_ws_bytes(int B, int M, int n_t);
+int sf_plan_sample_fwd(const double* v0, const double* kappa, const double* t0, const double* n0, const double* tt_kept, double t_key,
+                       const double* uniforms, int n_straight, int n_left, int n_right, int B, int M, int n_t, float* out, int32_t* order,
+                       void* ws, size_t ws_bytes, void* stream);
+
 /* hipGraph capture of whatever the caller enqueues between begin and end on `stream` (must not be
  * the legacy default stream). */
 int sf_graph_begin(void* stream);

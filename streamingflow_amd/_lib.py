@@ -177,6 +177,9 @@ SIGNATURES = {
                               _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sf_plan_select_refine_fwd": (_i, [_vp, _vp, C.c_long, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sf_plan_metric_fwd": (_i, [_vp, _vp, C.c_long, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "sf_fresnel_fwd": (_i, [_vp, C.c_long, _vp, _vp, _vp]),
+    "sf_plan_sample_ws_bytes": (_sz, [_i, _i, _i]),
+    "sf_plan_sample_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_double, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "sf_graph_begin": (_i, [_vp]),
     "sf_graph_end": (_i, [_vp, C.POINTER(_vp)]),
     "sf_graph_launch": (_i, [_vp, _vp]),
