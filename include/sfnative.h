@@ -481,7 +481,11 @@ int sf_hard_voxelize_fwd(const float* points, int num_points, int num_features, 
  *   out[j] = act(scale * sum_t W_t^T . feats[nbr[j][t]] + bias) + add   (act_after_add: act(... + add));
  *   w packs [Cout][Cin][ntaps][1] (kh = ntaps, kw = 1); feats has n_in rows of feats_cs floats.
  * sf_sparse_to_dense_fwd — SparseConvTensor.dense() + permute/view of sparse_encoder.py:131-137 as NHWC:
- *   out [batch][X][Y][C*D], channel c*D + z (zero where no site is active). */
+ *   out [batch][X][Y][C*D], channel c*D + z (zero where no site is active).
+ * Workspace of the two index entry points: sf_sparse_index_ws_bytes(n_in, ntaps) bytes (exactly that size is enough; 0 for n_in < 1 or
+ *   ntaps < 1); SF_ERR_WORKSPACE when ws_bytes is smaller, whatever the call itself would have used.  SF_ERR_INVALID: a NULL pointer,
+ *   n_in < 1, cap < 1, or a grid of batch * X * Y * Z >= 2^32 - 1 cells, input or output (keys are 32 bits, 0xFFFFFFFF is a sentinel).
+ *   sf_sparse_out_sites_fwd writes the TRUE number of sites into n_out even where it exceeds cap; rows from cap on are not written. */
 size_t sf_sparse_index_ws_bytes(int n_in, int ntaps);
 int sf_sparse_out_sites_fwd(const int32_t* in_coords, int n_in, int batch, const int32_t* shape, const int32_t* ksize,
                             const int32_t* stride, const int32_t* padding, int32_t* out_coords, int cap, int32_t* n_out,

@@ -214,6 +214,7 @@ int sf_sparse_table_fwd(const int32_t* in_coords, int n_in, const int32_t* out_c
   if (!in_coords || !out_coords || !nbr || n_in < 1 || n_out < 0 || !sp_geom(shape, ksize, stride, padding, subm, batch, &G, &ci, &co) || !ws)
     return SF_ERR_INVALID;
   if (n_out == 0) return SF_OK;
+  if (ws_bytes < sf_sparse_index_ws_bytes(n_in, G.k[0] * G.k[1] * G.k[2])) return SF_ERR_WORKSPACE;      // the documented size, not what this call happens to use
   hipStream_t st = static_cast<hipStream_t>(stream);
   char* p = static_cast<char*>(ws);
   size_t left = ws_bytes;
@@ -237,7 +238,7 @@ int sf_sparse_out_sites_fwd(const int32_t* in_coords, int n_in, int batch, const
   const size_t nc = (size_t)n_in * ntaps;
   const size_t c = a256s(nc * 4);
   const size_t tb_sort = sp_sort_keys_tmp(nc, st), tb_scan = sp_scan_tmp(nc, st);
-  if (ws_bytes < 4 * c + a256s(tb_sort) + a256s(tb_scan)) return SF_ERR_WORKSPACE;
+  if (ws_bytes < sf_sparse_index_ws_bytes(n_in, ntaps) || ws_bytes < 4 * c + a256s(tb_sort) + a256s(tb_scan)) return SF_ERR_WORKSPACE;
   char* p = static_cast<char*>(ws);
   unsigned* cand = reinterpret_cast<unsigned*>(p);
   unsigned* sorted = reinterpret_cast<unsigned*>(p + c);
