@@ -674,8 +674,9 @@ int sf_debug_occupancy(int which);
  *       (nprob > 1) cannot share a launch and runs one problem at a time; a single problem (nprob = 1) is beyond what the kernel's block
  *       decode computes exactly, and the call that asks for it returns SF_ERR_LAUNCH
  *   [3 + 4 s ..] per segment s: tile rows per block (4: 32-tile blocks, 2: 16-tile blocks), first tile row, tile rows, workgroups
- *   [11] workgroups of the whole launch on 32-tile blocks (what SF_WINO_SMALL_WGS is compared with) */
-#define SF_WINO_PLAN_INTS 12
+ *   [11] workgroups of the whole launch on 32-tile blocks (what SF_WINO_SMALL_WGS is compared with)
+ *   [12] arithmetic: bit s set = segment s runs the tall-tile form F(4,3) along y x F(2,3) along x (0: F(2x2, 3x3)) */
+#define SF_WINO_PLAN_INTS 13
 int sf_debug_wino_plan(const sf_conv_w* w, int epi, int n_img, int Hin, int Win, int in_up, int nprob, int flags, int32_t* out, int n_out);
 
 #ifdef __cplusplus

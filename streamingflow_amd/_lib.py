@@ -15,7 +15,7 @@ i32p = C.POINTER(C.c_int32)
 SF_COEF_STRIDE = 12
 SF_ABI_VERSION = 7       # include/sfnative.h: changes whenever a public struct changes layout
 SF_PROF_KEYS = 168
-SF_WINO_PLAN_INTS = 12     # include/sfnative.h: int32 entries sf_debug_wino_plan writes
+SF_WINO_PLAN_INTS = 13     # include/sfnative.h: int32 entries sf_debug_wino_plan writes
 PACK_TRANSPOSED, PACK_FOLD_DUP, PACK_INTERLEAVE, PACK_BF16X3, PACK_WINOGRAD = 1, 2, 4, 8, 16      # SF_PACK_* of sfnative.h
 ACT = {"none": 0, "lrelu": 1, "relu": 2, "tanh": 3, "sigmoid": 4, "gelu": 5}
 SOLVER = {"euler": 0, "midpoint": 1, "rk4": 2}

@@ -9,6 +9,8 @@
 //
 // Round 6: a 16-tile / three-workgroups-per-CU form for under-filled launches (Wino5Geo TH_ = 2) and the 7x7 + LayerNorm layer of the batched
 // cells as nine 3x3 tap groups (GRP = 9, EPI_LNG); both in front of conv_wino5_kernel.
+// The 32-tile AFFINE / BLEND launches run the tall-tile form F(4,3) along y x F(2,3) along x (conv_wino5t_kernel, TALL below: 12 multiplies
+// per 2x2 outputs; tools/winograd42_study.py: <= 9.4e-6 on the BEV outputs) from a second transformed copy of the weights behind the first.
 // Weights are transformed once at pack time (pack.hip: U[cin/16][16 positions][cout_pad][16], sf_conv_w::w_wino).  The kernel
 // (conv_wino5_kernel, round 5) is described in front of it; the round-4 kernel it replaced (U through an LDS ring, one wave = 16 cout x
 // 16 tiles x all 16 positions: 0.57-0.66 of the fp32 MFMA peak against 0.64-0.74) lives in the history of this file, the F(4x4, 3x3)
@@ -170,9 +172,12 @@ __device__ __forceinline__ float wn_gelu(float v) { return 0.5f * v * (1.f + spm
 // TH_: tile rows of the workgroup's block — 4 (8 x 16 output pixels, 32 tiles: the kernel as measured in DESIGN 4.3) or 2 (4 x 16 pixels, 16
 // tiles, three workgroups per CU: round 6, for launches of fewer than two rounds of the chip's 512 workgroup slots — a single 200x200 frame
 // with 64 / 128 output channels is nominally 313 / 626 workgroups of 32 tiles, 328 / 656 as launched; dispatch.hip: wino_plan holds the measured rule)
-template <bool DIL, bool CAT, int TH_ = 4>
+// TALL_ (32-tile blocks, not dilated): the tall-tile arithmetic F(4,3) along y x F(2,3) along x — the same 8 x 16 output pixels as 2 x 8 tall tiles
+// of 4 x 2 outputs, 6 x 4 inputs, 24 positions: 12 products per 2x2 outputs and (cin, cout) pair instead of 16 (described in front of the kernel)
+template <bool DIL, bool CAT, int TH_ = 4, bool TALL_ = false>
 struct Wino5Geo {
   static_assert(!(DIL && CAT), "one run structure at a time");
+  static_assert(!TALL_ || (!DIL && TH_ == WN_TH), "tall tiles: 32-tile blocks of the plain / concatenated forms");
   static_assert(TH_ == WN_TH || (TH_ == WN_TH_SMALL && !DIL), "tile rows per block");
   static constexpr int COUT_T = WN_COUT_T, TH = TH_, TW = WN_TW, WT = TH * TW, NB = WT / 16;      // (sf_launch.h: the planner counts blocks by them)
   static constexpr int RY = 2, RX = 4;
@@ -181,14 +186,17 @@ struct Wino5Geo {
   static constexpr int ND = (NPX * 4 + 63) / 64;                // 1-KB DMA pieces of a patch; wave w issues pieces w, w + 8, ...
   static constexpr int NP = (ND + 7) / 8;
   static constexpr int P_FLOATS = ND * 256;
-  static constexpr int V_FLOATS = 16 * WT * 16;
+  static constexpr int NPOS = TALL_ ? 24 : 16, NFT = TALL_ ? WT / 2 : WT;      // positions, transform-domain tiles of the block
+  static constexpr int V_FLOATS = NPOS * NFT * 16;
   static constexpr int NVB = DIL ? 1 : 2, NPB = DIL ? 2 : 1;
   static constexpr int PARK = DIL ? 512 + 64 : 0;               // DIL: the patch offset of every transform task + the per-axis tables of the block
   static constexpr int SB = 2 * COUT_T, SC = DIL ? 0 : (CAT ? 512 : 256);      // SE input scales: [c0 <= 256] of the image (CAT: and of the next one)
   static constexpr int T_FLOATS = 4 * 2 * WT * COUT_T;          // the exchange of the output transform: [row i][b][tile][cout]
-  static_assert(NVB * V_FLOATS + NPB * P_FLOATS >= T_FLOATS, "the exchange lives over V and the patch");
+  // the region V, the patch and later the exchange share (tall: two V buffers + the patch are smaller than the exchange)
+  static constexpr int WORK = (TALL_ && NVB * V_FLOATS + NPB * P_FLOATS < T_FLOATS) ? T_FLOATS : NVB * V_FLOATS + NPB * P_FLOATS;
+  static_assert(WORK >= T_FLOATS, "the exchange lives over V and the patch");
   static constexpr int PV = TH_ == 2 ? 2 * 512 : 0;             // 16-tile form (80 registers): the lanes' two patch offsets live in LDS between the chunks
-  static constexpr int LDS_FLOATS = NVB * V_FLOATS + NPB * P_FLOATS + PARK + SB + SC + PV;
+  static constexpr int LDS_FLOATS = WORK + PARK + SB + SC + PV;
   static_assert((TH_ == 2 ? 3 : 2) * LDS_FLOATS * 4 <= 160 * 1024, "two workgroups per CU (three of the 16-tile form)");
 };
 
@@ -203,19 +211,31 @@ struct Wino5Geo {
 // GRP = 9 (round 6, EPI_LNG only): a 7x7 / pad-3 layer as nine 3x3 sub-kernels of its 9x9 zero frame (wino_weights_kernel) — tap group (a, b)
 // convolves the input shifted by (3a - 3, 3b - 3), all nine accumulate into the same Winograd-domain sums: the K loop runs over
 // 9 x cin/16 chunks, the patch offsets move when a chunk starts a new group, everything else is the 3x3 kernel
-template <int EPI, bool DIL = false, bool CAT = false, int TH_ = 4, int GRP = 1>
-__global__ __launch_bounds__(WN_THREADS, TH_ == 2 ? 6 : 4) void conv_wino5_kernel(const ConvLaunch L) {
+//
+// TALL: F(4,3) along y, F(2,3) along x (Lavin's matrices).  The 4-output axis is y because concatenated blocks change image at arbitrary tile
+// columns.  The block's 32 2x2-tiles are 16 tall tiles (tall row t = tile rows 2t, 2t + 1) = ONE 16-tile B fragment; wave (xp, hh) owns
+// x-position xp of all six y-positions: 6 x 32 cout x 16 tiles = 48 accumulator registers, a chunk is 6 steps of 8 MFMAs, the A ring is three
+// steps deep (the same 16 MFMAs of cover as two steps of 16).  U is the second packed copy U42[cin/16][yp * 4 + xp][cout_pad][16] behind
+// the first (wino_tall_offset).  Input transform: the two waves of an x-position split a (tall tile, channel quad) task by channel pair:
+// one add per value on x (the F(2,3) row of the wave), then the 12-operation F(4,3) column form.  Output transform: A4^T along y in
+// registers (6 -> 4 rows), the exchange laid out [xp][row parity][2x2-tile][cout] — exactly where thread (2x2-tile, channel quad) finds
+// its operands in the F(2x2) form —, A2^T along x by the storing thread; everything behind Y is shared.
+// (the body of both kernels: conv_wino5_kernel = F(2x2) in all its forms, conv_wino5t_kernel = the tall form — a kernel of its own name, so
+// that profiles and the resource checks tell the two arithmetics apart)
+template <int EPI, bool DIL, bool CAT, int TH_, int GRP, bool TALL>
+__device__ __forceinline__ void conv_wino5_body(const ConvLaunch& L) {
+  static_assert(!TALL || (GRP == 1 && (EPI == EPI_AFFINE || EPI == EPI_BLEND)), "tall tiles: the 3x3 AFFINE / BLEND forms");
   static_assert(GRP == 1 || (GRP == 9 && !DIL && TH_ == 4), "tap groups: the 7x7 form");
   static_assert((EPI == EPI_LNG) == (GRP == 9), "the LayerNorm epilogue belongs to the 7x7 form");
   static_assert(EPI != EPI_SAMPLE || (!DIL && TH_ == 4), "the sampling layer: plain / concatenated 32-tile forms");
-  typedef Wino5Geo<DIL, CAT, TH_> G;
+  typedef Wino5Geo<DIL, CAT, TH_, TALL> G;
   constexpr int NB = G::NB;                                    // 16-tile fragments of the block
   constexpr int COUT_T = G::COUT_T, TH = G::TH, TW = G::TW, WT = G::WT, PW = G::PW, NP = G::NP;
   constexpr bool MODE_A = G::NVB == 2;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* const Vbuf = smem;
   float* const Pbuf = Vbuf + G::NVB * G::V_FLOATS;
-  float* const Park = Pbuf + G::NPB * G::P_FLOATS;
+  float* const Park = Vbuf + G::WORK;
   float* const SBuf = Park + G::PARK;                          // [scale COUT_T][bias COUT_T]
   float* const SCbuf = SBuf + G::SB;                           // [c0] input scales (SCALED)
   float* const PVbuf = SCbuf + G::SC;                          // [2][512] patch offsets of the lanes (16-tile form)
@@ -278,7 +298,7 @@ __global__ __launch_bounds__(WN_THREADS, TH_ == 2 ? 6 : 4) void conv_wino5_kerne
   const int cout0 = (slot_ - tb_ * ncb) * COUT_T;
   const int nkc_g = P.cin_pad >> 4;                            // 16-channel chunks (>= 2: cin_pad is a multiple of 32) of a tap group
   const int nkc = GRP * nkc_g;
-  const int NS = nkc * 4;                                      // steps: (chunk, position of the wave's row)
+  const int NS = nkc * 4;                                      // steps: (chunk, position of the wave's row); tall: six per chunk (load_A6)
   const int c0 = P.c0;
   const int img_px_i = P.Hin * P.Win;
   const int up = DIL ? 0 : P.in_up;
@@ -292,7 +312,8 @@ __global__ __launch_bounds__(WN_THREADS, TH_ == 2 ? 6 : 4) void conv_wino5_kerne
   const size_t n_in = (CAT && img + 1 < P.n_img) ? 2 : 1;
   const __amdgpu_buffer_rsrc_t rsrc0 = make_rsrc(PX.in0 + (size_t)img * img_px * P.in0_cs, n_in * img_px * P.in0_cs * sizeof(float));
   const __amdgpu_buffer_rsrc_t rsrc1 = make_rsrc(PX.in1 ? PX.in1 + (size_t)img * img_px * P.in1_cs : PX.in0, PX.in1 ? n_in * img_px * P.in1_cs * sizeof(float) : 0);
-  const __amdgpu_buffer_rsrc_t rsrc_u = make_rsrc(PX.w_wino, (size_t)nkc * 16 * P.cout_pad * 16 * sizeof(float));
+  const __amdgpu_buffer_rsrc_t rsrc_u = make_rsrc(PX.w_wino + (TALL ? wino_tall_offset(P.cout_pad, P.cin_pad, 3) : 0),
+                                                  (size_t)nkc * G::NPOS * P.cout_pad * 16 * sizeof(float));
 #endif
   constexpr bool SCALED = G::SC > 0 && (EPI == EPI_AFFINE || EPI == EPI_SAMPLE);
   const bool scaled = SCALED && PX.in_scale != nullptr;
@@ -483,8 +504,20 @@ __global__ __launch_bounds__(WN_THREADS, TH_ == 2 ? 6 : 4) void conv_wino5_kerne
     (void)s; (void)mb; return (f32x4){0.f, 0.f, 0.f, 0.f};
 #endif
   };
-  // B fragments: V[position][tile][16], slot swizzle as conv_wino_kernel
-  const int b_off = (ih * 4 * WT + j) * 16 + ((g ^ ((j >> 2) & 2)) << 2);
+  // tall: step p of chunk kc is y-position p of the wave's x-position; p >= 6 is the next chunk's, the tail re-loads the last step
+  auto load_A6 = [&](const int kc, const int p, const int mb) -> f32x4 {
+#if defined(__HIP_DEVICE_COMPILE__)
+    int k2 = p >= 6 ? kc + 1 : kc, p2 = p >= 6 ? p - 6 : p;
+    if (k2 >= nkc) { k2 = nkc - 1; p2 = 5; }
+    const int so = (k2 * 24 + p2 * 4 + ih) * u_pos_bytes;
+    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_u, u_voff + mb * 1024, so, 0));
+#else
+    (void)kc; (void)p; (void)mb; return (f32x4){0.f, 0.f, 0.f, 0.f};
+#endif
+  };
+  (void)load_A6;
+  // B fragments: V[position][tile][16], slot swizzle as conv_wino_kernel (tall: position xp * 6 + yp, 16 tall tiles)
+  const int b_off = TALL ? (ih * 6 * 16 + j) * 16 + ((g ^ ((j >> 2) & 2)) << 2) : (ih * 4 * WT + j) * 16 + ((g ^ ((j >> 2) & 2)) << 2);
   // ---- input transform: task (row ih, tile wt, channel quad): 8 reads, 8 add / sub, 4 writes (float4) -------------------------------------
   if constexpr (DIL) {
     const int quad = tid & 3, wt = (tid >> 2) % WT;
@@ -498,6 +531,36 @@ __global__ __launch_bounds__(WN_THREADS, TH_ == 2 ? 6 : 4) void conv_wino5_kerne
     }
     const float* const src = Pbuf + (G::NPB == 2 ? (kc & 1) : 0) * G::P_FLOATS;
     float* const dst = Vbuf + (G::NVB == 2 ? (kc & 1) : 0) * G::V_FLOATS;
+    if constexpr (TALL) {
+      // the wave's cout half hh takes tall-tile row hh; lane = (tile column, channel quad, channel pair of the quad): a (tile, quad) task is
+      // split by channel pair, not by output half, so the x stage is done once, and the lanes of a tile read and write 64 contiguous bytes
+      // (8-byte accesses at a 16-byte stride across a wave cost 4- to 8-way bank conflicts: 1.3 ms of the 128 -> 128 layer's 9.7).
+      // x stage: row ih of B2^T over the tile's six rows; y stage B4^T = [4 0 -5 0 1 0; 0 -4 -4 1 1 0; 0 4 -4 -1 1 0; 0 -2 -1 2 1 0;
+      // 0 2 -1 -2 1 0; 0 4 0 -5 0 1]
+      typedef const __attribute__((address_space(3))) f32x2 lds_f2;
+      typedef __attribute__((address_space(3))) f32x2 lds_f2w;
+      const int quad = (lane >> 1) & 3, tyt = hh, txl = lane >> 3, tt = tyt * 8 + txl, pr = lane & 1;
+      const int c1 = (ih == 0) ? 0 : (ih == 2 ? 2 : 1), c2 = (ih == 3) ? 3 : (ih == 2 ? 1 : 2);
+      const float sgf = (ih == 1) ? 1.f : -1.f;
+      const f32x2 sg = {sgf, sgf};
+      const int tp = ((4 * tyt) * PW + 2 * txl + ((CAT && txl >= cn0) ? 2 : 0)) * 16 + quad * 4 + pr * 2;
+      const float* const a = src + tp + c1 * 16;
+      const float* const bb = src + tp + c2 * 16;
+      f32x2 d[6];
+#pragma unroll
+      for (int y = 0; y < 6; ++y) d[y] = __builtin_elementwise_fma(sg, *(lds_f2*)(bb + y * PW * 16), *(lds_f2*)(a + y * PW * 16));
+      const f32x2 k2 = {2.f, 2.f}, k4 = {4.f, 4.f}, m2 = {-2.f, -2.f}, m4 = {-4.f, -4.f}, m5 = {-5.f, -5.f};
+      const f32x2 ea = __builtin_elementwise_fma(m4, d[2], d[4]), eb = __builtin_elementwise_fma(m4, d[1], d[3]);
+      const f32x2 ec = wn5_sub2(d[4], d[2]), ee = wn5_sub2(d[3], d[1]);
+      float* const o = dst + ((ih * 6) * 16 + tt) * 16 + ((quad ^ ((tt >> 2) & 2)) << 2) + pr * 2;
+      *(lds_f2w*)(o) = __builtin_elementwise_fma(k4, d[0], __builtin_elementwise_fma(m5, d[2], d[4]));
+      *(lds_f2w*)(o + 256) = ea + eb;
+      *(lds_f2w*)(o + 2 * 256) = wn5_sub2(ea, eb);
+      *(lds_f2w*)(o + 3 * 256) = __builtin_elementwise_fma(k2, ee, ec);
+      *(lds_f2w*)(o + 4 * 256) = __builtin_elementwise_fma(m2, ee, ec);
+      *(lds_f2w*)(o + 5 * 256) = __builtin_elementwise_fma(k4, d[1], __builtin_elementwise_fma(m5, d[3], d[5]));
+      return;
+    }
     const int quad = lane & 3, wt = (tid >> 2) & (WT - 1);
     const int tyl = wt / TW, txl = wt - tyl * TW;
     // B^T rows: 0: d0 - d2, 1: d1 + d2, 2: d2 - d1, 3: d1 - d3
@@ -525,9 +588,14 @@ __global__ __launch_bounds__(WN_THREADS, TH_ == 2 ? 6 : 4) void conv_wino5_kerne
     if (CAT_SC && scaled && tid >= c0 && tid < 2 * c0 && img + 1 < P.n_img) scv = PX.in_scale[(size_t)(img + 1) * c0 + (tid - c0)];
   }
   issue_patch(0);
-  f32x4 A[2][2];                                                // [ring slot = step & 1][mb]
-  A[0][0] = load_A(0, 0); A[0][1] = load_A(0, 1);
-  A[1][0] = load_A(1, 0); A[1][1] = load_A(1, 1);
+  f32x4 A[TALL ? 3 : 2][2];                                     // [ring slot = step & 1 (tall: step % 3)][mb]
+  if constexpr (TALL) {
+#pragma unroll
+    for (int p = 0; p < 3; ++p) { A[p][0] = load_A6(0, p, 0); A[p][1] = load_A6(0, p, 1); }
+  } else {
+    A[0][0] = load_A(0, 0); A[0][1] = load_A(0, 1);
+    A[1][0] = load_A(1, 0); A[1][1] = load_A(1, 1);
+  }
   float sbv = tid < COUT_T ? 1.f : 0.f;
   if (tid < 2 * COUT_T) {
     const int co = cout0 + (tid < COUT_T ? tid : tid - COUT_T);
@@ -537,7 +605,7 @@ __global__ __launch_bounds__(WN_THREADS, TH_ == 2 ? 6 : 4) void conv_wino5_kerne
     }
   }
   SF_STAMP_AT(L, 11);
-  wn_wait(4);                                                   // the patch is older than the four A loads (a wave that loaded scale / bias waits for one of them too)
+  wn_wait(TALL ? 6 : 4);                                        // the patch is older than the four (six) A loads (a wave that loaded scale / bias waits for one of them too)
   if constexpr (SCALED) {
     if (scaled) {
       if (tid < G::SC) SCbuf[tid] = scv;
@@ -557,8 +625,51 @@ __global__ __launch_bounds__(WN_THREADS, TH_ == 2 ? 6 : 4) void conv_wino5_kerne
   wn_barrier();                                                 // V(0) published; Mode A: the patch buffer is free
   SF_STAMP_AT(L, 1);
 
-  f32x4 acc[4][2][NB];
+  f32x4 acc[TALL ? 6 : 4][2][TALL ? 1 : NB];
   int b_cur = b_off;
+  // tall: step p = y-position p: one B fragment (the 16 tall tiles), two A fragments, 8 MFMAs
+  auto step6 = [&](const int kc, auto p_c, auto first_c) {
+    constexpr int p = decltype(p_c)::value, slot = p % 3;
+    constexpr bool first = decltype(first_c)::value;
+    const f32x4 Bf = wn_lds_read128(Vbuf + (kc & 1) * G::V_FLOATS + p * 256 + b_cur);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const f32x4 cin = (first && e == 0) ? (f32x4){0.f, 0.f, 0.f, 0.f} : acc[p][mb][0];
+        if (SF_W5_ABL & 16) acc[p][mb][0] = (e == 0 && mb == 0) ? cin + A[slot][mb] * Bf : cin;
+        else acc[p][mb][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[slot][mb][e], Bf[e], cin, 0, 0, 0);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      if (!(SF_W5_ABL & 4)) A[slot][mb] = load_A6(kc, p + 3, mb);                     // into the registers this half-step has released
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+  // (barrier M and the next chunk's transform after two, three, four or five of the six steps: within 0.6 % of each other on the 128 -> 128,
+  // 64 -> 64 and gate layers — profiles/wino_tall_ablations.txt)
+  auto chunk6 = [&](const int kc, auto first_c, auto more_c) {
+    constexpr bool more = decltype(more_c)::value;
+    if (more && !(SF_W5_ABL & 2)) issue_patch(kc + 1);                              // behind barrier B: every wave is done with transform(kc)
+    step6(kc, std::integral_constant<int, 0>{}, first_c);
+    step6(kc, std::integral_constant<int, 1>{}, first_c);
+    step6(kc, std::integral_constant<int, 2>{}, first_c);
+    if (more) {
+      wn_wait(6);                                               // younger than the patch: the A loads of steps 0 to 2
+      scale_patch(kc + 1);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      if (!(SF_W5_ABL & 8)) wn_barrier();                                             // M: patch(kc + 1) complete
+      if (!(SF_W5_ABL & 1)) transform(kc + 1);
+    }
+    step6(kc, std::integral_constant<int, 3>{}, first_c);
+    step6(kc, std::integral_constant<int, 4>{}, first_c);
+    step6(kc, std::integral_constant<int, 5>{}, first_c);
+    if (more) {
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      if (!(SF_W5_ABL & 8)) wn_barrier();                                             // B: V(kc + 1) published, patch buffer free
+    }
+  };
+  (void)step6; (void)chunk6;
   auto step = [&](const int kc, auto p_c, auto first_c) {
     constexpr int p = decltype(p_c)::value, slot = p & 1;
     constexpr bool first = decltype(first_c)::value;
@@ -610,6 +721,11 @@ __global__ __launch_bounds__(WN_THREADS, TH_ == 2 ? 6 : 4) void conv_wino5_kerne
       }
     }
   };
+  if constexpr (TALL) {
+    chunk6(0, std::true_type{}, std::true_type{});
+    for (int kc = 1; kc + 1 < nkc; ++kc) chunk6(kc, std::false_type{}, std::true_type{});
+    chunk6(nkc - 1, std::false_type{}, std::false_type{});
+  } else {
   chunk(0, std::true_type{}, std::true_type{});
   for (int kc = 1; kc + 1 < nkc; ++kc) chunk(kc, std::false_type{}, std::true_type{});
   if constexpr (WT == 16) {      // (80 registers: the last chunk is its own copy of the code, and hipcc carries its fragment offset past the loop in scratch)
@@ -619,6 +735,7 @@ __global__ __launch_bounds__(WN_THREADS, TH_ == 2 ? 6 : 4) void conv_wino5_kerne
     b_cur = (ih * 4 * WT + j2) * 16 + ((g2 ^ ((j2 >> 2) & 2)) << 2);
   }
   chunk(nkc - 1, std::false_type{}, std::false_type{});
+  }
   SF_STAMP_AT(L, 2);
 
   // ---- output transform, first half in registers: T[ih][b] = (M A)[ih][b] -------------------------------------------------------------------
@@ -626,11 +743,11 @@ __global__ __launch_bounds__(WN_THREADS, TH_ == 2 ? 6 : 4) void conv_wino5_kerne
   if (SF_W5_ABL & 32) {
     f32x4 sacc = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int p = 0; p < 4; ++p)
+    for (int p = 0; p < (TALL ? 6 : 4); ++p)
 #pragma unroll
       for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
-        for (int nb = 0; nb < NB; ++nb) sacc += acc[p][mb][nb];
+        for (int nb = 0; nb < (TALL ? 1 : NB); ++nb) sacc += acc[p][mb][nb];
     if (sacc[0] + sacc[1] + sacc[2] + sacc[3] == 1.2345f) PX.out[tid] = sacc[0];
     return;
   }
@@ -640,7 +757,25 @@ __global__ __launch_bounds__(WN_THREADS, TH_ == 2 ? 6 : 4) void conv_wino5_kerne
   // front of the loop and carry it through in scratch
   int tid_e = tid;
   if constexpr (WT == 16) asm volatile("" : "+v"(tid_e));
-  {
+  // tall: rows r = 0 .. 3 of tall tile j = A4^T [1 1 1 1 1 0; 0 1 -1 2 -2 0; 0 1 1 4 4 0; 0 1 -1 8 -8 1] over the six y-positions; row r is row
+  // r & 1 of 2x2-tile (2 (j >> 3) + (r >> 1), j & 7).  The slot key (wt & 7) | ((wt >> 1) & 8) is j here: 16 distinct slots per lane group
+  if constexpr (TALL) {
+    typedef __attribute__((address_space(3))) f32x4 lds_f4w;
+    const f32x4 k2 = {2.f, 2.f, 2.f, 2.f}, k4 = {4.f, 4.f, 4.f, 4.f}, k8 = {8.f, 8.f, 8.f, 8.f};
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb) {
+      const int sl = ((hh * 8 + mb * 4 + g) ^ j) << 2;
+      const f32x4 m0 = acc[0][mb][0], m1 = acc[1][mb][0], m2 = acc[2][mb][0], m3 = acc[3][mb][0], m4 = acc[4][mb][0], m5 = acc[5][mb][0];
+      const f32x4 s12 = m1 + m2, d12 = wn5_sub4(m1, m2), s34 = m3 + m4, d34 = wn5_sub4(m3, m4);
+      const f32x4 rr[4] = {(m0 + s12) + s34, __builtin_elementwise_fma(k2, d34, d12), __builtin_elementwise_fma(k4, s34, s12),
+                           __builtin_elementwise_fma(k8, d34, d12) + m5};
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int wt = (2 * (j >> 3) + (r >> 1)) * 8 + (j & 7);
+        *(lds_f4w*)(Tb + ((ih * 2 + (r & 1)) * WT + wt) * 64 + sl) = rr[r];
+      }
+    }
+  } else {
     typedef __attribute__((address_space(3))) f32x4 lds_f4w;
     const int j = tid_e & 15, g = (tid_e & 63) >> 4;
     const int tw_base = ((ih * 2) * WT + j) * 64;
@@ -733,15 +868,17 @@ __global__ __launch_bounds__(WN_THREADS, TH_ == 2 ? 6 : 4) void conv_wino5_kerne
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   wn_barrier();                                                 // the exchange is complete
   const f32x4 sc = wn_lds_read128(SBuf + cl), bi = wn_lds_read128(SBuf + COUT_T + cl);
-  const int tr = wt_e * 64 + ((cq ^ (wt_e & 15)) << 2);
+  const int tr = wt_e * 64 + ((cq ^ (TALL ? (wt_e & 7) | ((wt_e >> 1) & 8) : (wt_e & 15))) << 2);
   SF_STAMP_AT(L, 5);
   f32x4 y[4];
 #pragma unroll
   for (int bq = 0; bq < 2; ++bq) {
     const float* const tb = Tb + bq * WT * 64 + tr;
     const f32x4 t0 = wn_lds_read128(tb), t1 = wn_lds_read128(tb + 2 * WT * 64), t2 = wn_lds_read128(tb + 4 * WT * 64), t3 = wn_lds_read128(tb + 6 * WT * 64);
-    y[2 * bq] = (t0 + t1) + t2;
-    y[2 * bq + 1] = wn5_sub4(t1, t2 + t3);
+    // F(2x2): the exchange index is b (x offset), the sum runs over rows: pixels (b, 0), (b, 1).  Tall: the index is the row parity a, the sum
+    // runs over x-positions: pixels (0, a), (1, a)
+    y[TALL ? bq : 2 * bq] = (t0 + t1) + t2;
+    y[TALL ? 2 + bq : 2 * bq + 1] = wn5_sub4(t1, t2 + t3);
   }
   SF_STAMP_AT(L, 6);
   if constexpr (!lng) {
@@ -862,6 +999,15 @@ __global__ __launch_bounds__(WN_THREADS, TH_ == 2 ? 6 : 4) void conv_wino5_kerne
 #endif
 }
 
+template <int EPI, bool DIL = false, bool CAT = false, int TH_ = 4, int GRP = 1>
+__global__ __launch_bounds__(WN_THREADS, TH_ == 2 ? 6 : 4) void conv_wino5_kernel(const ConvLaunch L) {
+  conv_wino5_body<EPI, DIL, CAT, TH_, GRP, false>(L);
+}
+template <int EPI, bool CAT>
+__global__ __launch_bounds__(WN_THREADS, 4) void conv_wino5t_kernel(const ConvLaunch L) {
+  conv_wino5_body<EPI, false, CAT, WN_TH, 1, true>(L);
+}
+
 // weights: packed direct form w[cout_pad][kh * kw * cin_pad] (tap-major, channel-minor) -> U[group][cin_pad/16][16][cout_pad][16] = G g G^T.
 // 3x3: one group.  7x7 (round 6, the small-P kernel's Winograd block only): the kernel sits in a 9x9 frame of zeros and is cut into 3 x 3
 // sub-kernels of 3x3 — group (a, b) = rows 3a .. 3a+2, columns 3b .. 3b+2 of the frame, applied to the input shifted by (3a - 3, 3b - 3) —
@@ -901,9 +1047,49 @@ __global__ void wino_weights_kernel(const float* __restrict__ w, float* __restri
     for (int jj = 0; jj < 4; ++jj) U[((((size_t)grp * nkc + kc) * 16 + i * 4 + jj) * cout_pad + co) * 16 + cl] = uu[jj];
   }
 }
+// the tall form's copy: U42[group][cin_pad/16][24 = yp * 4 + xp][cout_pad][16] = G4 g G2^T with Lavin's F(4,3) matrix along y,
+// G4 = [[1/4, 0, 0], [-1/6, -1/6, -1/6], [-1/6, 1/6, -1/6], [1/24, 1/12, 1/6], [1/24, -1/12, 1/6], [0, 0, 1]], and G of F(2,3) along x; groups as above
+__global__ void wino_weights42_kernel(const float* __restrict__ w, float* __restrict__ U, int cout_pad, int cin_pad, int ksz) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;      // (group, co, ci)
+  const int ngrp = ksz == 7 ? 9 : 1;
+  if (idx >= (long)ngrp * cout_pad * cin_pad) return;
+  const int grp = (int)(idx / ((long)cout_pad * cin_pad));
+  const long rem = idx - (long)grp * cout_pad * cin_pad;
+  const int co = (int)(rem / cin_pad), ci = (int)(rem - (long)co * cin_pad);
+  const int ga = grp / 3, gb = grp - 3 * ga;
+  float g[3][3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+      const int ky = ksz == 7 ? 3 * ga + a - 1 : a, kx = ksz == 7 ? 3 * gb + b - 1 : b;
+      g[a][b] = (ky >= 0 && ky < ksz && kx >= 0 && kx < ksz) ? w[(size_t)co * ksz * ksz * cin_pad + (size_t)(ky * ksz + kx) * cin_pad + ci] : 0.f;
+    }
+  const float r4 = 0.25f, r6 = 1.f / 6.f, r12 = 1.f / 12.f, r24 = 1.f / 24.f;
+  float t[6][3];
+#pragma unroll
+  for (int b = 0; b < 3; ++b) {
+    t[0][b] = r4 * g[0][b];
+    t[1][b] = -r6 * ((g[0][b] + g[2][b]) + g[1][b]);
+    t[2][b] = -r6 * ((g[0][b] + g[2][b]) - g[1][b]);
+    t[3][b] = (r24 * g[0][b] + r6 * g[2][b]) + r12 * g[1][b];
+    t[4][b] = (r24 * g[0][b] + r6 * g[2][b]) - r12 * g[1][b];
+    t[5][b] = g[2][b];
+  }
+  const int kc = ci >> 4, cl = ci & 15, nkc = cin_pad >> 4;
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    const float uu[4] = {t[i][0], 0.5f * (t[i][0] + t[i][1] + t[i][2]), 0.5f * (t[i][0] - t[i][1] + t[i][2]), t[i][2]};
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) U[((((size_t)grp * nkc + kc) * 24 + i * 4 + jj) * cout_pad + co) * 16 + cl] = uu[jj];
+  }
+}
+// both copies: U at `U`, U42 behind it (sf_launch.h: wino_tall_offset; the blob holds wino_pack_floats)
 hipError_t launch_wino_weights(const float* w, float* U, int cout_pad, int cin_pad, int ksz, hipStream_t stream) {
   const long n = (long)(ksz == 7 ? 9 : 1) * cout_pad * cin_pad;
   hipLaunchKernelGGL(wino_weights_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, w, U, cout_pad, cin_pad, ksz);
+  hipLaunchKernelGGL(wino_weights42_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, w, U + wino_tall_offset(cout_pad, cin_pad, ksz),
+                     cout_pad, cin_pad, ksz);
   return hipGetLastError();
 }
 
@@ -978,10 +1164,12 @@ bool wino_same_geometry(const ConvProblem& a, const ConvProblem& b) {
 
 // ---- the instantiation table.  L arrives planned (dispatch.hip: wino_plan): window of tile rows, workgroups per problem in wg_base[1],
 // reciprocals of the block decode
-template <int EPI, bool DIL = false, bool CAT = false, int TH_ = WN_TH, int GRP = 1>
+template <int EPI, bool DIL = false, bool CAT = false, int TH_ = WN_TH, int GRP = 1, bool TALL = false>
 static hipError_t launch_wino5_t(const ConvLaunch& L, hipStream_t stream) {
-  auto kern = conv_wino5_kernel<EPI, DIL, CAT, TH_, GRP>;
-  constexpr int lds = Wino5Geo<DIL, CAT, TH_>::LDS_FLOATS * 4;
+  void (*kern)(const ConvLaunch);
+  if constexpr (TALL) kern = conv_wino5t_kernel<EPI, CAT>;
+  else kern = conv_wino5_kernel<EPI, DIL, CAT, TH_, GRP>;
+  constexpr int lds = Wino5Geo<DIL, CAT, TH_, TALL>::LDS_FLOATS * 4;
   static bool attr_done[64] = {};
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
@@ -993,10 +1181,21 @@ static hipError_t launch_wino5_t(const ConvLaunch& L, hipStream_t stream) {
   hipLaunchKernelGGL(kern, dim3((unsigned)((long)L.wg_base[1] * L.nprob), 1, 1), dim3(WN_THREADS), lds, stream, L);
   return hipGetLastError();
 }
+// what the tall-tile arithmetic can address: a launch of 32-tile blocks in the plain / concatenated AFFINE or BLEND form of a 3x3 layer whose
+// U42 copy stays inside a 32-bit byte offset (WHICH of them run tall is dispatch.hip: wino_tall)
+bool wino_takes_tall(const ConvProblem& q, int epi, WinoForm form, int th) {
+  return th == WN_TH && (form == WINO_PLAIN || form == WINO_CAT) && (epi == EPI_AFFINE || epi == EPI_BLEND) && q.KH == 3 && q.KW == 3 && q.dil == 1 &&
+         4.0 * 24 * q.cout_pad * q.cin_pad < 2147483648.0;
+}
 // one problem per launch, or up to SF_MAX_GROUP of identical geometry
-hipError_t launch_conv_wino(const ConvLaunch& L, int epi, WinoForm form, int th, hipStream_t stream) {
+hipError_t launch_conv_wino(const ConvLaunch& L, int epi, WinoForm form, int th, bool tall, hipStream_t stream) {
   if (L.nprob < 1 || L.nprob > SF_MAX_GROUP || (th != WN_TH && th != WN_TH_SMALL)) return hipErrorInvalidValue;
   const bool cat = form == WINO_CAT, small = th == WN_TH_SMALL;
+  if (tall) {
+    if (!wino_takes_tall(L.p[0], epi, form, th)) return hipErrorInvalidValue;
+    if (epi == EPI_AFFINE) return cat ? launch_wino5_t<EPI_AFFINE, false, true, WN_TH, 1, true>(L, stream) : launch_wino5_t<EPI_AFFINE, false, false, WN_TH, 1, true>(L, stream);
+    return cat ? launch_wino5_t<EPI_BLEND, false, true, WN_TH, 1, true>(L, stream) : launch_wino5_t<EPI_BLEND, false, false, WN_TH, 1, true>(L, stream);
+  }
   if (form != WINO_PLAIN && !cat) return (form == WINO_DIL && epi == EPI_AFFINE && !small) ? launch_wino5_t<EPI_AFFINE, true>(L, stream) : hipErrorInvalidValue;
   if (small && (epi == EPI_SAMPLE || epi == EPI_LNG || (cat && L.p[0].in_scale))) return hipErrorInvalidValue;      // no 16-tile form
   switch (epi) {

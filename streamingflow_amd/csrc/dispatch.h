@@ -30,8 +30,9 @@ inline size_t al(size_t n) { return (n + 63) & ~size_t(63); }
 
 // Switches, read once per process from the environment (experiments and A/B aids only; defaults are the shipped choice).  geti (atoi) and
 // getl (atol) in dispatch.hip are the only readers of the conv dispatch; isset: a debugging aid that is on when its variable is set at all.
-// Two switches are LIVE — re-read at every Winograd plan (dispatch.hip: wino_live), because tests/test_gpu_wino_split.py flips them inside one
-// process to compare both forms on the same tensors: SF_WINO_SPLIT_WGS (default 512) and SF_WINO_CAT_WIDE (default 1); see wino_plan.
+// Three switches are LIVE — re-read at every Winograd plan (dispatch.hip: wino_live), because tests/test_gpu_wino_split.py and
+// tests/test_gpu_wino_tall.py flip them inside one process to compare both forms on the same tensors: SF_WINO_SPLIT_WGS (default 512),
+// SF_WINO_CAT_WIDE (default 1) and SF_WINO_TALL (0: F(2x2) everywhere, 1: the tall form wherever the kernel has it, unset: the measured rule); see wino_plan.
 // Two readers remain in kernel files: SF_XCD_CHUNK (conv_igemm.hip) and SF_DWCONV_PK (aux_kernels.hip).
 int geti(const char* name, int dflt);
 long getl(const char* name, long dflt);

@@ -57,8 +57,8 @@ hipError_t zero_fill(void* p, size_t bytes, hipStream_t st) {     // p 16-byte a
 int geti(const char* k, int d) { const char* v = std::getenv(k); return v ? std::atoi(v) : d; }
 long getl(const char* k, long d) { const char* v = std::getenv(k); return v ? std::atol(v) : d; }
 // the two LIVE switches of the Winograd plan (dispatch.h), read once per plan
-struct WinoLive { long split_wgs; bool cat_wide; };
-static WinoLive wino_live() { return {getl("SF_WINO_SPLIT_WGS", 512), geti("SF_WINO_CAT_WIDE", 1) != 0}; }
+struct WinoLive { long split_wgs; bool cat_wide; int tall; };
+static WinoLive wino_live() { return {getl("SF_WINO_SPLIT_WGS", 512), geti("SF_WINO_CAT_WIDE", 1) != 0, geti("SF_WINO_TALL", -1)}; }
 const Tune& tune() { static const Tune t; return t; }
 
 static int pick_cfg(int P, int epi) {
@@ -436,12 +436,14 @@ static Cost direct_cost(int key, const ConvProblem* ps, int n) {
 // Winograd form, priced at its EXECUTED flops: 16 products per 2x2 outputs, (cin, cout) pair and tap group (nine for the 7x7); the
 // plan's form names the launch (_lib.KERNEL_NAMES: wino128x32t / wino64x64t / wino64x32t2, also its form with concatenated images /
 // wino64x32t2dil)
-static Cost wino_cost(const ConvProblem* ps, int n, int epi, WinoForm form) {
+// (tall_frac: the part of the layer's tile rows that runs in the tall form, 12 products per 2x2-tile equivalent)
+static double wino_products(double tall_frac) { return 16.0 - 4.0 * tall_frac; }
+static Cost wino_cost(const ConvProblem* ps, int n, int epi, WinoForm form, double tall_frac) {
   Cost c{(16 + (form == WINO_CAT ? 2 : (int)form)) * 8 + epi, 0, 0};
   for (int i = 0; i < n; ++i) {
     const ConvProblem& q = ps[i];
     const double grp = q.KH == 7 ? 9.0 : 1.0;
-    c.flops += 2.0 * 16.0 * grp * wino_tiles(q) * q.cout * (q.c0 + q.c1);
+    c.flops += 2.0 * wino_products(tall_frac) * grp * wino_tiles(q) * q.cout * (q.c0 + q.c1);
     c.bytes += 4.0 * ((double)q.n_img * q.Hin * q.Win * (q.c0 + q.c1) + 16.0 * grp * q.cout * (q.c0 + q.c1) + (double)q.n_img * q.Hout * q.Wout * q.cout);
   }
   return c;
@@ -477,6 +479,7 @@ static int run_wide_ln(ConvLaunch& L, int epi, hipStream_t st) {
 // arithmetic covers all of it.  Nothing is launched before the whole plan stands.
 struct WinoSeg {
   int th, row0, rows;      // blocks of th tile rows over the tile rows [row0, row0 + rows) of every image
+  bool tall;               // the launch's arithmetic: F(4,3) x F(2,3) tall tiles (wino_tall) or F(2x2)
   long grid1;              // workgroups per problem (the launch has grid1 * nprob)
   unsigned m[5];           // ConvLaunch::wn_m
 };
@@ -527,8 +530,20 @@ static bool wino_segment(const ConvProblem& P, int nprob, WinoForm form, int th,
       (nbx * WN_TW + WN_TW) * tiles_x >= 0x100000000L)
     return false;
   if (nprob > 1 && grid * grid1 >= 0x100000000L) return false;
-  s = WinoSeg{th, row0, rows, grid1, {nprob > 1 ? magic(grid1) : 1u, magic(ncb), magic(nbx), magic(nby), magic(tiles_x)}};
+  s = WinoSeg{th, row0, rows, false, grid1, {nprob > 1 ? magic(grid1) : 1u, magic(ncb), magic(nbx), magic(nby), magic(tiles_x)}};
   return true;
+}
+// The arithmetic of a planned launch, decided apart from the plan (forms, blocks, grids and windows do not depend on it).  SF_WINO_TALL: 0 =
+// F(2x2) everywhere, 1 = the tall form wherever the kernel has it (conv_wino.hip: wino_takes_tall — 32-tile blocks of the plain /
+// concatenated AFFINE and BLEND forms), unset = the measured rule, which is the same: profiles/wino_tall_layers_{off,on}.txt show no layer
+// class of the batched forward slower in the tall form.  Remainder launches of split layers are 16-tile blocks: F(2x2)
+static bool wino_tall(const ConvProblem& P, int epi, WinoForm form, const WinoSeg& s, const WinoLive& live) {
+  return live.tall != 0 && wino_takes_tall(P, epi, form, s.th);
+}
+static double wino_tall_frac(const WinoPlan& W) {
+  double rows = 0, tall = 0;
+  for (int s = 0; s < W.nseg; ++s) { rows += W.seg[s].rows; tall += W.seg[s].tall ? W.seg[s].rows : 0; }
+  return rows > 0 ? tall / rows : 0.0;
 }
 static WinoPlan wino_plan(const ConvProblem* ps, int n, int epi) {
   WinoPlan W;
@@ -565,6 +580,7 @@ static WinoPlan wino_plan(const ConvProblem* ps, int n, int epi) {
     W.nseg = 1;
     W.ok = wino_segment(P, n, W.form, small ? WN_TH_SMALL : WN_TH, 0, tiles_y, W.seg[0]);
   }
+  for (int s = 0; W.ok && s < W.nseg; ++s) W.seg[s].tall = wino_tall(P, epi, W.form, W.seg[s], live);
   return W;
 }
 // the plan's launches, in order
@@ -574,7 +590,7 @@ static hipError_t wino_issue(ConvLaunch& L, const WinoPlan& W, int epi, hipStrea
     L.wg_base[0] = 0; L.wg_base[1] = (int)g.grid1;
     L.wn_ty0 = g.row0; L.wn_nty = g.rows;
     for (int k = 0; k < 5; ++k) L.wn_m[k] = g.m[k];
-    const hipError_t e = launch_conv_wino(L, epi, W.form, g.th, st);
+    const hipError_t e = launch_conv_wino(L, epi, W.form, g.th, g.tall, st);
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
@@ -599,6 +615,7 @@ int debug_wino_plan(const sf_conv_w& w, int epi, int n_img, int Hin, int Win, in
     out[3 + 4 * s] = W.seg[s].th; out[4 + 4 * s] = W.seg[s].row0; out[5 + 4 * s] = W.seg[s].rows; out[6 + 4 * s] = (int)(W.seg[s].grid1 * nprob);
   }
   out[11] = (int)std::min(W.wgs32, 0x7fffffffL);
+  for (int s = 0; s < out[2]; ++s) out[12] |= W.seg[s].tall ? 1 << s : 0;
   return SF_OK;
 }
 
@@ -617,7 +634,7 @@ static int wino_list_launch(ConvLaunch& W1, const WinoPlan& W, int epi, hipStrea
   std::fprintf(stderr, "[sf-wino] n=%d %dx%d c=%d+%d->%d epi=%d act=%d mode=%d add=%d add_scale=%d out2=%d in_scale=%d bias_img=%d clamp=%d dil=%d up=%d var=%d us=%.1f gflop=%.3f\n",
                q.n_img, q.Hout, q.Wout, q.c0, q.c1, q.cout, epi, q.act, q.mode, q.add != nullptr, q.add_scale != nullptr, q.out2 != nullptr,
                q.in_scale != nullptr, q.bias_per_img, q.clamp_from >= 0, q.dil, q.in_up, (int)W.form, ms * 1e3,
-               2.0 * 16.0 * wino_tiles(q) * q.cout * (q.c0 + q.c1) * 1e-9);
+               2.0 * wino_products(wino_tall_frac(W)) * wino_tiles(q) * q.cout * (q.c0 + q.c1) * 1e-9);
   return SF_OK;
 }
 // SF_WINO_WHY: which large 3x3 launches keep the direct form, one line each on stderr
@@ -653,7 +670,7 @@ static int run_wino(const ConvProblem* ps, int n, int P, int epi, hipStream_t st
   // one profiler record per planned layer / group, whatever its number of launches
   auto issue = [&](ConvLaunch& L, const WinoPlan& W) {
     L.stamp_slot = next_stamp_slot();
-    return timed([&] { return wino_issue(L, W, epi, st); }, [&] { return wino_cost(L.p, L.nprob, epi, W.form); }, st);
+    return timed([&] { return wino_issue(L, W, epi, st); }, [&] { return wino_cost(L.p, L.nprob, epi, W.form, wino_tall_frac(W)); }, st);
   };
   // layers of identical geometry (the two branches of a dual cell) share ONE launch: their tails merge
   if (tune().wino_group && !tune().wino_list && n_wino >= 2) {

@@ -99,9 +99,7 @@ __global__ void pack_affine_kernel(const float* __restrict__ conv_bias, const fl
 
 }  // namespace sf
 
-namespace sf {
-hipError_t launch_wino_weights(const float* w, float* U, int cout_pad, int cin_pad, int ksz, hipStream_t stream);
-}
+#include "sf_launch.h"      // launch_wino_weights, wino_pack_floats (conv_wino.hip)
 using namespace sf;
 
 extern "C" {
@@ -122,7 +120,8 @@ static bool wino_packable(int cp, int ip, int cin, int kh, int kw, int flags) {
   //  7x7: nine 3x3 sub-kernels, conv_wino.hip: wino_weights_kernel — the trusting gate's first layer on one latent)
   return (flags & SF_PACK_WINOGRAD) && ((kh == 3 && kw == 3) || (kh == 7 && kw == 7)) && cin == ip && (cp % 64) == 0;
 }
-static size_t wino_floats(int cp, int ip, int kh) { return (size_t)(kh == 7 ? 9 : 1) * 16 * cp * ip; }
+// both transformed copies: the 16 positions of F(2x2) and behind them the 24 of the tall form
+static size_t wino_floats(int cp, int ip, int kh) { return wino_pack_floats(cp, ip, kh); }
 
 size_t sf_pack_conv_bytes(int cout, int cin, int kh, int kw, int flags) {
   int cp = 0, ip = 0;

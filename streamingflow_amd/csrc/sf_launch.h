@@ -19,7 +19,14 @@ hipError_t launch_conv_sp(const ConvLaunch& L, int epi, bool scaled, int bn, hip
 // blocks, SE-scaled concatenated images on 16-tile blocks)
 constexpr int WN_COUT_T = 64, WN_TW = 8, WN_TH = 4, WN_TH_SMALL = 2;
 enum WinoForm { WINO_PLAIN = 2, WINO_DIL = 3, WINO_CAT = 4 };
-hipError_t launch_conv_wino(const ConvLaunch& L, int epi, WinoForm form, int th, hipStream_t stream);
+// tall: the F(4,3) x F(2,3) arithmetic of the 32-tile plain / concatenated AFFINE and BLEND forms (dispatch.hip: wino_tall decides)
+hipError_t launch_conv_wino(const ConvLaunch& L, int epi, WinoForm form, int th, bool tall, hipStream_t stream);
+// the packed Winograd weights of a layer: U (16 positions) and behind it U42 (24 positions, the tall form), both [group][cin_pad / 16][position][cout_pad][16];
+// floats from sf_conv_w::w_wino to U42, and of both copies together (cout_pad is a multiple of 64: every part stays 256-byte aligned)
+__host__ __device__ inline size_t wino_tall_offset(int cout_pad, int cin_pad, int kh) { return (size_t)(kh == 7 ? 9 : 1) * 16 * cout_pad * cin_pad; }
+inline size_t wino_pack_floats(int cout_pad, int cin_pad, int kh) { return wino_tall_offset(cout_pad, cin_pad, kh) / 16 * (16 + 24); }
+hipError_t launch_wino_weights(const float* w, float* U, int cout_pad, int cin_pad, int ksz, hipStream_t stream);
+bool wino_takes_tall(const ConvProblem& q, int epi, WinoForm form, int th);
 bool wino_takes(const ConvProblem& q, int epi);
 bool wino_same_geometry(const ConvProblem& a, const ConvProblem& b);
 void wino_tile_grid(const ConvProblem& q, int& tiles_x, int& tiles_y);
