@@ -172,6 +172,8 @@ SIGNATURES = {
     "sf_instance_seq_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, C.c_float, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sf_instance_labels_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "sf_instance_labels_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.c_double, C.c_float, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sf_instance_track_ws_bytes": (_sz, [_i, _i, _i]),
+    "sf_instance_track_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, C.c_float, _vp, _vp, _vp, _sz, _vp]),
     "sf_plan_cost_ws_bytes": (_sz, []),
     "sf_plan_cost_fwd": (_i, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, C.POINTER(C.c_float * 7), C.c_float, C.c_float,
                               _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -11,17 +11,27 @@ How it is computed here.
     relabelling is a look-up table gathered on the device; "make ids consecutive" is the inverse index of a sorted unique.
   * A sequence — ``instance_segmentation_sequence``: centres, grouping and consecutive ids of all B*T frames by
     ``sf_instance_seq_fwd`` (a fixed number of launches, nothing read back; ids are at most ``max_n_instance_centers``).
-    Both ``predict_*`` functions go this way: one sequence call, one moments launch and one device->host copy for all
-    frames, the host matching per sample, one gather.  The host round trips of a call do not depend on B or T.
+    Both ``predict_*`` functions go this way: one sequence call, one moments launch, one tracking call, one gather.
+    Nothing is copied to the host (with ``compute_matched_centers``: one copy at the end), so a call only enqueues and
+    can be captured in a graph behind the forward.
   * Temporal consistency.  The ids a frame ends up with are a relabelling of its own raw instances, so everything the
     matching needs — each raw instance's pixel count, centre, and centre displaced by the predicted flow — is computed
-    for ALL frames by one launch (``sf_instance_moments_fwd``: integer atomics, order-independent) and copied to the
-    host once.  The frame-to-frame assignment (Hungarian method on a handful of centres, ``scipy``,
-    ``_consistent_tables``) then only produces one small table per frame, and the whole sequence is relabelled by a
-    single gather.  The regular matcher compares frame t+1 with the flow-displaced centres of frame t (closer than 3
-    pixels); the short-interval one ignores the flow and compares with the plain centres (closer than 10).
+    for ALL frames by one launch (``sf_instance_moments_fwd``: integer atomics, order-independent) and stays on the
+    device.  The frame-to-frame assignment (``sf_instance_track_fwd``: one workgroup per pair of frames solves the
+    minimum-distance assignment by shortest augmenting paths, one wavefront per sample hands the ids down the frames)
+    produces one small table per frame, and the whole sequence is relabelled by a single gather.  The regular matcher
+    compares frame t+1 with the flow-displaced centres of frame t (closer than 3 pixels); the short-interval one
+    ignores the flow and compares with the plain centres (closer than 10).
+  * ``_consistent_tables`` is the statement of that matching on the host (Hungarian method, ``scipy``), the one the
+    reference fixtures pin.  ``SF_TRACK_HOST=1`` (read at every call) selects it: one host copy of the moments, the
+    matching per sample, one upload.  The device tables equal it wherever every pair of frames has one optimal
+    assignment; where several are optimal the device returns one of them, the same on every run.  The stand-alone
+    ``make_instance_id_temporally_consistent[_short_interval]`` take arbitrary ids: one ``max().item()`` sizes the
+    tables, ids up to ``MAX_TRACK_ID`` go to the device call (its flag is read: ``ValueError`` where scipy raises),
+    larger ones to the host path.
 CUDA tensors only.
 """
+import os
 from typing import Tuple
 
 import numpy as np
@@ -33,6 +43,7 @@ from .runtime import ptr
 
 MOMENT_SCALE = 1.0 / 1048576.0      # sf_instance_moments_fwd: flow-warped sums are 2^-20 fixed point
 MAX_N_INSTANCE_CENTERS = 100        # the reference's default cut of a frame's centre list; raw ids of a frame are at most this
+MAX_TRACK_ID = 128                  # sf_instance_track_fwd: the largest raw id of a frame (its cost matrix lives in LDS)
 
 
 def find_instance_centers(center_prediction: torch.Tensor, conf_threshold: float = 0.1, nms_kernel_size: float = 3):
@@ -129,26 +140,59 @@ def instance_segmentation_sequence(center, offset, foreground, conf_threshold: f
     return ids, [found[f, :n].long() for f, n in enumerate(kept)]
 
 
-def _moments_to_host(ids, flow, top):
-    """ids [F, H, W] int64 with values <= ``top``, flow [F, 2, H, W] or None -> numpy (counts [F, K] int32, position sums
-    [F, K, 2] int64, flow-warped sums [F, K, 2] int64 in 2^-20 fixed point or None), K = top + 1: one launch, ONE copy."""
+def _moments_on_device(ids, flow, top, with_tables=False):
+    """ids [F, H, W] int64 with values <= ``top``, flow [F, 2, H, W] or None -> ONE int64 device buffer, K = top + 1, n = F * K:
+    position sums [n][2] | flow-warped sums [n][2] in 2^-20 fixed point (only with ``flow``) | room for the tables [n] (only
+    ``with_tables``) | counts int32 [n].  One launch, nothing read back.  Returns (buffer, sums, warped or None, tables or None,
+    counts): views of it."""
     F, H, W = ids.shape
     K = top + 1
-    dev = ids.device
     n = F * K
     fl = runtime.f32c(flow).view(F, 2, H, W) if flow is not None else None
-    parts = 2 if fl is not None else 1
-    buf = torch.empty((2 * n * parts + (n + 1) // 2,), dtype=torch.int64, device=dev)      # sums, then the int32 counts
+    head = 2 * n * (2 if fl is not None else 1)
+    tail = head + (n if with_tables else 0)
+    buf = torch.empty((tail + (n + 1) // 2,), dtype=torch.int64, device=ids.device)
     pos = buf[:2 * n]
     moved = buf[2 * n:4 * n] if fl is not None else None
-    cnt = buf[2 * n * parts:].view(torch.int32)
-    _lib.check(_lib.lib().sf_instance_moments_fwd(ptr(ids), ptr(fl), F, H, W, top, ptr(pos), ptr(moved), ptr(cnt), runtime.stream_ptr(dev)),
-               "instance_moments")
+    tables = buf[head:tail] if with_tables else None
+    cnt = buf[tail:].view(torch.int32)
+    _lib.check(_lib.lib().sf_instance_moments_fwd(ptr(ids), ptr(fl), F, H, W, top, ptr(pos), ptr(moved), ptr(cnt),
+                                                  runtime.stream_ptr(ids.device)), "instance_moments")
+    return buf, pos, moved, tables, cnt
+
+
+def _moments_to_host(ids, flow, top):
+    """ids [F, H, W] int64 with values <= ``top``, flow [F, 2, H, W] or None -> numpy (counts [F, K] int32, position sums
+    [F, K, 2] int64, flow-warped sums [F, K, 2] int64 in 2^-20 fixed point or None), K = top + 1: one launch, ONE copy.
+    The host path only (``SF_TRACK_HOST=1``, ids above ``MAX_TRACK_ID``, ``instance_moments``)."""
+    F, K = ids.shape[0], top + 1
+    n = F * K
+    buf, _, moved, _, _ = _moments_on_device(ids, flow, top)
+    parts = 2 if moved is not None else 1
     host = buf.cpu().numpy()
     counts = host[2 * n * parts:].view(np.int32)[:n].reshape(F, K)
     sums = host[:2 * n].reshape(F, K, 2)
-    warped = host[2 * n:4 * n].reshape(F, K, 2) if fl is not None else None
+    warped = host[2 * n:4 * n].reshape(F, K, 2) if moved is not None else None
     return counts, sums, warped
+
+
+def _track_on_device(counts, sums, warped, B, T, K, matching_threshold, tables=None):
+    """``sf_instance_track_fwd`` on device moments of B samples of T frames (``warped`` None: the short-interval matcher) ->
+    (tables [B*T, K] int64, flags [B] int32), both on the device.  Enqueues only."""
+    dev = counts.device
+    if tables is None:
+        tables = torch.empty((B * T * K,), dtype=torch.int64, device=dev)
+    flags = torch.empty((B,), dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    ws = runtime.workspace(L.sf_instance_track_ws_bytes(B, T, K), dev)
+    _lib.check(L.sf_instance_track_fwd(ptr(counts), ptr(sums), ptr(warped), B, T, K, float(matching_threshold), ptr(tables), ptr(flags),
+                                       ptr(ws), ws.numel() * 4, runtime.stream_ptr(dev)), "instance_track")
+    return tables.view(B * T, K), flags
+
+
+def _host_tracking():
+    """``SF_TRACK_HOST=1``: the frame-to-frame matching on the host (scipy).  Read at every call."""
+    return os.environ.get("SF_TRACK_HOST", "0") == "1"
 
 
 def _means(counts, sums, scale=1.0):
@@ -201,15 +245,31 @@ def _relabel(frames, tables):
     return torch.gather(lut, 1, frames.reshape(frames.shape[0], -1).long()).view_as(frames)
 
 
+def _consistent_sequence(frames, flow, matching_threshold):
+    """One sample's [T, h, w] instance maps with arbitrary ids, flow [T, 2, h, w] or None (the short-interval matcher) -> the
+    maps with consistent ids.  One ``max().item()`` sizes the tables; ids up to ``MAX_TRACK_ID`` are matched on the device
+    (one more ``.item()`` reads the flag: ``ValueError`` where scipy raises), larger ones on the host."""
+    ids = frames.to(torch.int64).contiguous()
+    top = int(ids.max().item())
+    if top > MAX_TRACK_ID or _host_tracking():
+        counts, sums, warped = _moments_to_host(ids, flow, top)
+        centres = _means(counts, sums)
+        anchors = _means(counts, warped, MOMENT_SCALE) if warped is not None else centres
+        return _relabel(frames, _consistent_tables(counts, centres, anchors, matching_threshold))
+    _, sums, warped, _, counts = _moments_on_device(ids, flow, top)
+    tables, flags = _track_on_device(counts, sums, warped, 1, ids.shape[0], top + 1, matching_threshold)
+    if int(flags.item()):
+        raise ValueError("matrix contains invalid numeric entries")      # scipy's, on the NaN centre of a missing raw id
+    return torch.gather(tables, 1, ids.view(ids.shape[0], -1)).view_as(frames)
+
+
 def make_instance_id_temporally_consistent(pred_inst, future_flow, matching_threshold=3.0):
     """pred_inst [1, T, h, w] per-frame instance maps, future_flow [1, T, 2, h, w] -> [1, T, h, w] with ids that follow the
     instances through time: an instance of frame t+1 inherits the id of the frame-t instance whose flow-displaced centre
     it is assigned to (Hungarian method) when they are closer than ``matching_threshold``; otherwise it gets a new id."""
     assert pred_inst.shape[0] == 1, "Assumes batch size = 1"
     runtime.require_cuda(pred_inst, future_flow)
-    frames = pred_inst[0]
-    counts, centres, displaced = instance_moments(frames, future_flow[0])
-    return _relabel(frames, _consistent_tables(counts, centres, displaced, matching_threshold)).unsqueeze(0)
+    return _consistent_sequence(pred_inst[0], future_flow[0], matching_threshold).unsqueeze(0)
 
 
 def make_instance_id_temporally_consistent_short_interval(pred_inst, future_flow=None, matching_threshold=10.0):
@@ -218,14 +278,14 @@ def make_instance_id_temporally_consistent_short_interval(pred_inst, future_flow
     to 10 pixels are accepted."""
     assert pred_inst.shape[0] == 1, "Assumes batch size = 1"
     runtime.require_cuda(pred_inst)
-    frames = pred_inst[0]
-    counts, centres, _ = instance_moments(frames)
-    return _relabel(frames, _consistent_tables(counts, centres, centres, matching_threshold)).unsqueeze(0)
+    return _consistent_sequence(pred_inst[0], None, matching_threshold).unsqueeze(0)
 
 
 def _predict(output, compute_matched_centers, make_consistent, vehicles_id, short_interval):
-    """Both ``predict_*`` functions: the sequence kernels on all B*T frames, one moments launch and host copy, the host
-    matching per sample, one gather."""
+    """Both ``predict_*`` functions: the sequence kernels on all B*T frames, one moments launch, the matching of all samples
+    (``sf_instance_track_fwd``), one gather with the device tables: nothing is read back unless ``compute_matched_centers``,
+    which copies tables and moments once at the end.  ``SF_TRACK_HOST=1``: one host copy of the moments and the host matching
+    per sample instead."""
     vehicles = output["segmentation"].detach().argmax(dim=2) == vehicles_id
     B, T, H, W = vehicles.shape
     cap = MAX_N_INSTANCE_CENTERS                                    # the reference calls with the default
@@ -237,11 +297,25 @@ def _predict(output, compute_matched_centers, make_consistent, vehicles_id, shor
     if not make_consistent and not compute_matched_centers:
         return raw.view(B, T, H, W)
     flow = output["instance_flow"].detach().reshape(B * T, 2, H, W) if make_consistent and not short_interval else None
+    thr = 10.0 if short_interval else 3.0
+    if make_consistent and not _host_tracking():
+        K = cap + 1                                                 # raw ids are <= cap by construction
+        buf, d_sums, d_warped, d_tables, d_counts = _moments_on_device(raw, flow, cap, with_tables=compute_matched_centers)
+        d_tables, _ = _track_on_device(d_counts, d_sums, d_warped, B, T, K, thr, d_tables)
+        tracked = torch.gather(d_tables, 1, raw.view(B * T, -1)).view(B, T, H, W)
+        if not compute_matched_centers:
+            return tracked                                          # nothing was read back
+        n = B * T * K
+        host = buf.cpu().numpy()                                    # the ONE copy: sums, tables and counts together
+        tail = host.size - (n + 1) // 2                             # _moments_on_device: sums | warped sums | tables | counts
+        sums = host[:2 * n].reshape(B * T, K, 2)
+        tables = host[tail - n:tail].reshape(B * T, K)
+        counts = host[tail:].view(np.int32)[:n].reshape(B * T, K)
+        return tracked, _tracks(tables, counts, sums, B, T, cap)
     counts, sums, warped = _moments_to_host(raw, flow, cap)        # raw ids are <= cap by construction
     if make_consistent:
         centres = _means(counts, sums)
         anchors = centres if short_interval else _means(counts, warped, MOMENT_SCALE)
-        thr = 10.0 if short_interval else 3.0
         tables = np.concatenate([_consistent_tables(counts[b * T:(b + 1) * T], centres[b * T:(b + 1) * T], anchors[b * T:(b + 1) * T], thr)
                                  for b in range(B)])
         tracked = _relabel(raw, tables).view(B, T, H, W)
@@ -250,8 +324,13 @@ def _predict(output, compute_matched_centers, make_consistent, vehicles_id, shor
         tracked = raw.view(B, T, H, W)
     if not compute_matched_centers:
         return tracked
+    return tracked, _tracks(tables, counts, sums, B, T, cap)
+
+
+def _tracks(tables, counts, sums, B, T, cap):
+    """{id: [n, 2] (x, y) centre track} of the instances of the first frame from the host copies of the tables [T, cap + 1] and
+    the raw moments: moments of the consistent ids from those of the raw ids (integer sums: exact)."""
     assert B == 1
-    # moments of the consistent ids from those of the raw ids (integer sums: exact)
     top = int(tables.max())
     t_idx = np.repeat(np.arange(T), cap + 1)
     c_cnt = np.zeros((T, top + 1), dtype=np.int64)
@@ -263,7 +342,7 @@ def _predict(output, compute_matched_centers, make_consistent, vehicles_id, shor
     for ident in (np.flatnonzero(c_cnt[0][1:]) + 1).tolist():       # the instances of the first frame, wherever they reappear
         seen = c_cnt[:, ident] > 0
         tracks[ident] = centres[seen, ident][:, ::-1]               # (row, col) -> (x, y)
-    return tracked, tracks
+    return tracks
 
 
 def predict_instance_segmentation_and_trajectories(output, compute_matched_centers=False, make_consistent=True, vehicles_id=1):
