@@ -698,6 +698,22 @@ int sf_debug_occupancy(int which);
  *   [12] arithmetic: bit s set = segment s runs the tall-tile form F(4,3) along y x F(2,3) along x (0: F(2x2, 3x3)) */
 #define SF_WINO_PLAN_INTS 13
 int sf_debug_wino_plan(const sf_conv_w* w, int epi, int n_img, int Hin, int Win, int in_up, int nprob, int flags, int32_t* out, int n_out);
+/* diagnostic, host only (as above: no HIP call, only w[0 .. nprob) is read): what the conv dispatch will decide for ONE launch group of the
+ * nprob (1..4) packed layers w[0 .. nprob) under epilogue family `epi` (0 affine, 1 blend, 2 LayerNorm + GELU, 3 trust, 4 sampling), each on
+ * n_img images of Hin x Win — the plan of the tiled kernels (tiled_plan in dispatch.hip; the rows are TILES of csrc/sf_launch.h) under the
+ * switches in force.  flags say what every problem carries beyond its layer: 1 = neighbour table (sparse gather), 2 = reset gate applied
+ * while staging, 4 = SE input scale, 8 = split-bf16 weights, 16 = the call has split-K scratch.
+ * out[0 .. SF_TILED_PLAN_INTS):
+ * Returns what a launch of the group would: SF_ERR_UNSUPPORTED for a LayerNorm / trust group over 65..128 channels that carries a gate, a
+ * neighbour table or an input scale, SF_ERR_LAUNCH where SF_NARROW names no tile.
+ *   [0] the kernel family that runs the group: 0 the tiled kernels, 1 Winograd (at least one layer of the group; the others are then planned
+ *       again as a group of their own), 2 small-P (1, 2: everything else is 0)
+ *   [1] the table row planned, [2] the row whose instantiation runs (differs for SE-scaled / sampling launches of the larger LDS-DMA tiles)
+ *   [3] mt, [4] ks: the direct kernel's run-time tile height and K groups (as planned; read by that row only)
+ *   [5] the profiler key (kernel key = [5] * 8 + epi)
+ *   [6 + i] K slices of problem i across workgroups (0: not split) */
+#define SF_TILED_PLAN_INTS 10
+int sf_debug_tiled_plan(const sf_conv_w* w, int epi, int n_img, int Hin, int Win, int in_up, int nprob, int flags, int32_t* out, int n_out);
 
 #ifdef __cplusplus
 }

@@ -16,6 +16,7 @@ SF_COEF_STRIDE = 12
 SF_ABI_VERSION = 7       # include/sfnative.h: changes whenever a public struct changes layout
 SF_PROF_KEYS = 168
 SF_WINO_PLAN_INTS = 13     # include/sfnative.h: int32 entries sf_debug_wino_plan writes
+SF_TILED_PLAN_INTS = 10    # ... and sf_debug_tiled_plan
 PACK_TRANSPOSED, PACK_FOLD_DUP, PACK_INTERLEAVE, PACK_BF16X3, PACK_WINOGRAD = 1, 2, 4, 8, 16      # SF_PACK_* of sfnative.h
 ACT = {"none": 0, "lrelu": 1, "relu": 2, "tanh": 3, "sigmoid": 4, "gelu": 5}
 SOLVER = {"euler": 0, "midpoint": 1, "rk4": 2}
@@ -196,15 +197,38 @@ SIGNATURES = {
     "sf_pack_conv_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "sf_debug_occupancy": (_i, [_i]),
     "sf_debug_wino_plan": (_i, [C.POINTER(ConvW), _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int32), _i]),
+    "sf_debug_tiled_plan": (_i, [C.POINTER(ConvW), _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int32), _i]),
     "sf_bn_fold": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_float, _i, _vp, _vp, _vp]),
     "sf_pack_conv": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_float, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, C.POINTER(ConvW), _vp]),
 }
 
-# kernel key = tile_config*8 + epilogue  (csrc/conv_igemm.hip launch_conv; configs 10..13: the LDS-DMA kernel conv_glds_kernel)
+# kernel key = KEY_NAMES key * 8 + epilogue.  Keys 0..15 are the tiled conv kernels: beside each name the rows of the tile table (csrc/sf_launch.h:
+# TILES) that report it — the table's key column is the authority; DESIGN.md 4.2 lists the launches reported under another tile's name
+KEY_NAMES = {
+    0: "S16x64k4",            # TILE_S16x64K4
+    1: "L64x64",              # TILE_L64x64
+    2: "LN64x128",            # TILE_LN64x128
+    3: "direct16px",          # TILE_DIRECT16
+    4: "T64x64splitK",        # TILE_SPLIT64x64
+    5: "dmaLN128x64",         # TILE_DMA_LN128x64
+    6: "L64x128",             # retired name: no row reports this key
+    7: "L128x128w4",          # retired name
+    8: "L64x128w8",           # retired name
+    9: "L128x128w8",          # TILE_L128x128
+    10: "dma128x128w8",       # TILE_DMA128x128 (SE-scaled launches: the 64x64 SCALE instantiation runs)
+    11: "dma64x64",           # TILE_DMA64x64, and reported as it: TILE_DMA32x128 (narrow layers), TILE_DMA32x32 (one latent), TILE_DMA64x128W4 (SF_NARROW=7)
+    12: "dma64x128w8",        # TILE_DMA64x128, TILE_DMA64x256 (SE-scaled launches: the 64x64 SCALE instantiation runs)
+    13: "dmaLN64x128",        # TILE_DMA_LN64x128
+    14: "sp64x32",            # the small-P kernel (conv_sp.hip)
+    15: "dmaT64x64splitK",    # TILE_DMA_SPLIT64x64
+    16: "wino128x32t",        # the Winograd kernel (conv_wino.hip): 16 + form
+    17: "wino64x64t",
+    18: "wino64x32t2",
+    19: "wino64x32t2dil",
+    20: "mlp64-256-64",       # convnext_mlp.hip
+}
 KERNEL_NAMES = {c * 8 + e: (f"convnext_mlp<{cn[3:]},gelu+residual>" if cn.startswith("mlp") else f"conv_wino<{cn[4:]},{en}>" if cn.startswith("wino") else f"conv_glds<{cn[3:]},{en}>" if cn.startswith("dma") else f"conv_sp<{cn[2:]},{en}>" if cn.startswith("sp") else f"conv_igemm<{cn},{en}>")
-                for c, cn in enumerate(("S16x64k4", "L64x64", "LN64x128", "direct16px", "T64x64splitK", "dmaLN128x64", "L64x128", "L128x128w4", "L64x128w8", "L128x128w8",
-                                        "dma128x128w8", "dma64x64", "dma64x128w8", "dmaLN64x128", "sp64x32", "dmaT64x64splitK", "wino128x32t", "wino64x64t", "wino64x32t2", "wino64x32t2dil",
-                                        "mlp64-256-64"))
+                for c, cn in KEY_NAMES.items()
                 for e, en in enumerate(("affine", "blend", "ln_gelu", "trust", "sample"))}
 
 _LIB = None

@@ -1158,6 +1158,13 @@ int sf_debug_wino_plan(const sf_conv_w* w, int epi, int n_img, int Hin, int Win,
   if (!w || !valid_w(*w)) return SF_ERR_INVALID;
   return debug_wino_plan(*w, epi, n_img, Hin, Win, in_up, nprob, flags, out, n_out);
 }
+/* diagnostic, host only: the plan of the tiled kernels for a launch group (dispatch.hip: debug_tiled_plan) */
+int sf_debug_tiled_plan(const sf_conv_w* w, int epi, int n_img, int Hin, int Win, int in_up, int nprob, int flags, int32_t* out, int n_out) {
+  if (!w || nprob < 1 || nprob > SF_MAX_GROUP) return SF_ERR_INVALID;
+  for (int i = 0; i < nprob; ++i)
+    if (!valid_w(w[i])) return SF_ERR_INVALID;
+  return debug_tiled_plan(w, epi, n_img, Hin, Win, in_up, nprob, flags, out, n_out);
+}
 
 int sf_prof_enable(int on) {
   prof_enable(on != 0);

@@ -21,6 +21,7 @@
 #include "sf_launch.h"
 
 #include <type_traits>
+#include <utility>
 #include <cstdlib>
 
 namespace sf {
@@ -1177,118 +1178,51 @@ __global__ __launch_bounds__(64 * WM * WN, (B3 && !SF_B3_DEEP && WM * WN >= 8 ? 
 #endif
 }
 
-template <int MT, int NT, int WM, int WN, int EPI, bool SCALE, bool B3>
-static hipError_t launch_glds_tb(const ConvLaunch& L, hipStream_t stream);
-// bf16x3 (opt-in math mode): every problem of the launch carries split weights (dispatch.hip decides); block-uniform host switch
-template <int MT, int NT, int WM, int WN, int EPI, bool SCALE = false>
-static hipError_t launch_glds_t(const ConvLaunch& L, hipStream_t stream) {
-  bool b3 = L.nprob > 0;
-  for (int i = 0; i < L.nprob; ++i) b3 = b3 && L.p[i].w3 != nullptr && L.p[i].use_w3;
-  return b3 ? launch_glds_tb<MT, NT, WM, WN, EPI, SCALE, true>(L, stream) : launch_glds_tb<MT, NT, WM, WN, EPI, SCALE, false>(L, stream);
-}
+// dynamic LDS of an LDS-DMA launch: NB staging buffers (+ the SE scale rows of up to 4 images x 256 channels)
+template <int MT, int NT, int WM, int WN, bool B3>
+constexpr int glds_nb() { return B3 ? b3_nb<MT, NT, WM, WN>() : 2; }
+template <int MT, int NT, int WM, int WN, bool SCALE, bool B3>
+constexpr int glds_lds() { return glds_nb<MT, NT, WM, WN, B3>() * 16 * (MT * WM + NT * WN) * 32 * 4 + (SCALE ? 4 * 256 * 4 : 0); }
 template <int MT, int NT, int WM, int WN, int EPI, bool SCALE, bool B3>
 static hipError_t launch_glds_tb(const ConvLaunch& L, hipStream_t stream) {
-  constexpr int BM = 16 * MT * WM, BN = 16 * NT * WN;
-  constexpr int NB = B3 ? b3_nb<MT, NT, WM, WN>() : 2;
-  constexpr int lds = NB * (BM + BN) * 32 * 4 + (SCALE ? 4 * 256 * 4 : 0);   // staging buffers (+ the SE scale rows of up to 4 images x 256 channels)
-  auto kern = conv_glds_kernel<MT, NT, WM, WN, EPI, NB, SCALE, B3>;
-  // the attribute is per device (a process may touch more than one GPU); one process per GPU and one launching
-  // thread per device are the documented use (include/sfnative.h), so the flag needs no lock
-  static bool attr_done[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-  if (!attr_done[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return e;
-    attr_done[dev] = true;
-  }
-  int maxblocks = 0;
-  for (int i = 0; i < L.nprob; ++i) {
-    const ConvProblem& P = L.p[i];
-    int Ptot = P.n_img * P.Hout * P.Wout;
-    int nb = ((Ptot + BN - 1) / BN) * ((P.cout_pad + BM - 1) / BM);
-    if (nb > maxblocks) maxblocks = nb;
-  }
-  if (maxblocks == 0) return hipSuccess;
-  int zs = 1;
-  for (int i = 0; i < L.nprob; ++i) zs = L.p[i].nsplit > zs ? L.p[i].nsplit : zs;
+  constexpr int lds = glds_lds<MT, NT, WM, WN, SCALE, B3>();
+  constexpr auto kern = conv_glds_kernel<MT, NT, WM, WN, EPI, glds_nb<MT, NT, WM, WN, B3>(), SCALE, B3>;
+  const hipError_t e = set_max_dynamic_lds<kern>(lds);
+  if (e != hipSuccess) return e;
+  TileGrid g = tile_grid(L, 16 * MT * WM, 16 * NT * WN);
+  if (g.maxblocks == 0) return hipSuccess;
   ConvLaunch LL = L;
   LL.xcd_shift = 0;
-  if (xcd_chunk_log2() >= 0 && maxblocks >= 4096 && zs == 1) {      // see the tile order in the kernel
+  if (xcd_chunk_log2() >= 0 && g.maxblocks >= 4096 && g.zs == 1) {      // see the tile order in the kernel
     const int span = 8 << xcd_chunk_log2();
-    maxblocks = (maxblocks + span - 1) / span * span;
+    g.maxblocks = (g.maxblocks + span - 1) / span * span;
     LL.xcd_shift = xcd_chunk_log2() + 1;
   }
-  hipLaunchKernelGGL(kern, dim3(maxblocks, L.nprob, zs), dim3(64 * WM * WN), lds, stream, LL);
+  hipLaunchKernelGGL(kern, dim3(g.maxblocks, L.nprob, g.zs), dim3(64 * WM * WN), lds, stream, LL);
   return hipGetLastError();
 }
-
-template <int MT, int NT, int WM, int WN>
-static hipError_t launch_glds_e(const ConvLaunch& L, int epi, hipStream_t stream) {
-  if (epi == EPI_AFFINE) return launch_glds_t<MT, NT, WM, WN, EPI_AFFINE>(L, stream);
-  if (epi == EPI_BLEND) return launch_glds_t<MT, NT, WM, WN, EPI_BLEND>(L, stream);
-  return hipErrorInvalidValue;
-}
-// SE-scaled inputs (the two p_model layers behind an SELayer): affine and sampling epilogues
-template <int MT, int NT, int WM, int WN>
-static hipError_t launch_glds_s(const ConvLaunch& L, int epi, hipStream_t stream) {
-  if (epi == EPI_AFFINE) return launch_glds_t<MT, NT, WM, WN, EPI_AFFINE, true>(L, stream);
-  if (epi == EPI_SAMPLE) return launch_glds_t<MT, NT, WM, WN, EPI_SAMPLE, true>(L, stream);
-  return hipErrorInvalidValue;
+template <int MT, int NT, int WM, int WN, int EPI, bool SCALE = false>
+static hipError_t launch_glds_t(const ConvLaunch& L, hipStream_t stream) {      // block-uniform host switch
+  return launch_runs_bf16x3(L) ? launch_glds_tb<MT, NT, WM, WN, EPI, SCALE, true>(L, stream) : launch_glds_tb<MT, NT, WM, WN, EPI, SCALE, false>(L, stream);
 }
 
 // diagnostic: workgroups per CU the runtime grants the 128 x 128 and 64 x 128 (8-wave) AFFINE tiles with their LDS (tools/r03/occupancy.py)
-int glds_occupancy(int which) {
+template <TileId T, bool B3>
+static int glds_occupancy_of() {
+  constexpr TileRow R = TILES[T];
   int n = -1;
-  hipError_t e = hipErrorInvalidValue;
-  if (which == 0) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv_glds_kernel<4, 2, 2, 4, EPI_AFFINE, 2, false, false>, 512, 2 * 256 * 32 * 4);
-  if (which == 1) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv_glds_kernel<4, 2, 2, 4, EPI_AFFINE, b3_nb<4, 2, 2, 4>(), false, true>, 512, b3_nb<4, 2, 2, 4>() * 256 * 32 * 4);
-  if (which == 2) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv_glds_kernel<2, 2, 2, 4, EPI_AFFINE, 2, false, false>, 512, 2 * 192 * 32 * 4);
-  if (which == 3) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv_glds_kernel<2, 2, 2, 4, EPI_AFFINE, b3_nb<2, 2, 2, 4>(), false, true>, 512, b3_nb<2, 2, 2, 4>() * 192 * 32 * 4);
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv_glds_kernel<R.MT, R.NT, R.WM, R.WN, EPI_AFFINE, glds_nb<R.MT, R.NT, R.WM, R.WN, B3>(), false, B3>,
+                                                                    64 * R.WM * R.WN, glds_lds<R.MT, R.NT, R.WM, R.WN, false, B3>());
   return e == hipSuccess ? n : -1;
 }
-
-// tile: 0 = 128 cout x 128 px (2x4 waves of 64x32), 1 = 64 x 64 (2x2 waves of 32x32);  variant: buffers / issue placement
-hipError_t launch_conv_glds(const ConvLaunch& L, int epi, int tile, int variant, hipStream_t stream) {
-  bool scaled = false;
-  for (int i = 0; i < L.nprob; ++i) scaled = scaled || (L.p[i].in_scale != nullptr);
-  if (scaled || epi == EPI_SAMPLE) {     // 64x64 tiles (large P), 32x32 (one latent)
-    if (tile == 3) return launch_glds_s<1, 1, 2, 2>(L, epi, stream);
-    if (tile == 1 || tile == 0) return launch_glds_s<2, 2, 2, 2>(L, epi, stream);
-    if (tile == 4) return launch_glds_s<4, 1, 1, 4>(L, epi, stream);      // cross-workgroup split-K launches (a few batched samples)
-    return hipErrorInvalidValue;
+int glds_occupancy(int which) {
+  switch (which) {
+    case 0: return glds_occupancy_of<TILE_DMA128x128, false>();
+    case 1: return glds_occupancy_of<TILE_DMA128x128, true>();
+    case 2: return glds_occupancy_of<TILE_DMA64x128, false>();
+    case 3: return glds_occupancy_of<TILE_DMA64x128, true>();
   }
-  if (tile == 2) {   // LayerNorm epilogues: one wave holds all (<= 64) output channels of its pixels; 64 cout x 128 px, 4 waves
-    if (epi == EPI_LNG) return launch_glds_t<4, 2, 1, 4, EPI_LNG>(L, stream);
-    if (epi == EPI_TRUST) return launch_glds_t<4, 2, 1, 4, EPI_TRUST>(L, stream);
-    return hipErrorInvalidValue;
-  }
-  if (tile == 5) {   // LayerNorm epilogues over 65..128 output channels (hidden sizes no shipped config uses): 128 cout x 64 px, 4 waves of 128x16
-    if (epi == EPI_LNG) return launch_glds_t<8, 1, 1, 4, EPI_LNG>(L, stream);
-    if (epi == EPI_TRUST) return launch_glds_t<8, 1, 1, 4, EPI_TRUST>(L, stream);
-    return hipErrorInvalidValue;
-  }
-  if (tile == 4) {   // cross-workgroup split-K launches: 64 cout x 64 px, 4 waves of 64x16 (all channels of a pixel in one wave)
-    switch (epi) {
-      case EPI_AFFINE: return launch_glds_t<4, 1, 1, 4, EPI_AFFINE>(L, stream);
-      case EPI_BLEND:  return launch_glds_t<4, 1, 1, 4, EPI_BLEND>(L, stream);
-      case EPI_LNG:    return launch_glds_t<4, 1, 1, 4, EPI_LNG>(L, stream);
-      case EPI_TRUST:  return launch_glds_t<4, 1, 1, 4, EPI_TRUST>(L, stream);
-    }
-    return hipErrorInvalidValue;
-  }
-  if (tile == 3) {   // small pixel counts (one 50x50 latent): 32 cout x 32 px, 4 waves of 16x16
-    return launch_glds_e<1, 1, 2, 2>(L, epi, stream);
-  }
-  if (tile == 0) return launch_glds_e<4, 2, 2, 4>(L, epi, stream);     // 128 cout x 128 px, 8 waves of 64x32
-  switch (variant) {
-    case 4: return launch_glds_e<2, 2, 2, 2>(L, epi, stream);   // 64 cout x 64 px, 4 waves of 32x32
-    case 6: return launch_glds_e<2, 2, 2, 4>(L, epi, stream);   // 64 cout x 128 px, 8 waves of 32x32
-    case 7: return launch_glds_e<4, 2, 1, 4>(L, epi, stream);   // 64 cout x 128 px, 4 waves of 64x32
-    case 9: return launch_glds_e<1, 4, 2, 2>(L, epi, stream);   // 32 cout x 128 px, 4 waves of 16x64 (narrow layers: 16- / 32-channel sparse stages)
-    case 10: return launch_glds_e<2, 4, 2, 4>(L, epi, stream);  // 64 cout x 256 px, 8 waves of 32x64 (64-channel layers at large P: the staged bytes per FLOP of the 128 x 128 tile)
-  }
-  return hipErrorInvalidValue;
+  return -1;
 }
 
 // ---- direct-fragment kernel (small pixel counts: the 50x50 BEV latent of the GRU-ODE) -------
@@ -1462,19 +1396,12 @@ __global__ __launch_bounds__(512) void conv_direct_kernel(const ConvLaunch L) {
 
 template <int MT, int EPI>
 static hipError_t launch_direct_t(const ConvLaunch& L, int ks, hipStream_t stream) {
-  int maxblocks = 0;
-  for (int i = 0; i < L.nprob; ++i) {
-    const ConvProblem& P = L.p[i];
-    int Ptot = P.n_img * P.Hout * P.Wout;
-    int nb = ((Ptot + 15) / 16) * ((P.cout_pad + 16 * MT - 1) / (16 * MT));
-    if (nb > maxblocks) maxblocks = nb;
-  }
+  const int maxblocks = tile_grid(L, 16 * MT, 16).maxblocks;
   if (maxblocks == 0) return hipSuccess;
   const int lds = (ks - 1) * MT * 4 * 64 * 4;
   hipLaunchKernelGGL((conv_direct_kernel<MT, EPI>), dim3(maxblocks, L.nprob), dim3(64 * ks), lds, stream, L);
   return hipGetLastError();
 }
-
 template <int EPI>
 static hipError_t launch_direct_e(const ConvLaunch& L, int mt, int ks, hipStream_t stream) {
   switch (mt) {
@@ -1485,95 +1412,61 @@ static hipError_t launch_direct_e(const ConvLaunch& L, int mt, int ks, hipStream
   return hipErrorInvalidValue;
 }
 
-// mt: 16-row cout tiles per wave (1, 2, 4); ks: K-groups per workgroup (1..8)
-hipError_t launch_conv_direct(const ConvLaunch& L, int epi, int mt, int ks, hipStream_t stream) {
-  if (ks < 1 || ks > 8) return hipErrorInvalidValue;
-  switch (epi) {
-    case EPI_AFFINE: return launch_direct_e<EPI_AFFINE>(L, mt, ks, stream);
-    case EPI_BLEND:  return launch_direct_e<EPI_BLEND>(L, mt, ks, stream);
-    case EPI_LNG:    return launch_direct_e<EPI_LNG>(L, mt, ks, stream);
-    case EPI_TRUST:  return launch_direct_e<EPI_TRUST>(L, mt, ks, stream);
-    case EPI_SAMPLE: return launch_direct_e<EPI_SAMPLE>(L, mt, ks, stream);
-  }
-  return hipErrorInvalidValue;
-}
-
-// ---- host-side launcher --------------------------------------------------------------------
+// ---- host-side launcher of the staged kernel ------------------------------------------------
 template <int MT, int NT, int WM, int WN, int KS, int EPI, int KB = 32, bool SWZ = false>
 static hipError_t launch_cfg(const ConvLaunch& L, hipStream_t stream) {
   constexpr int BM = 16 * MT * WM, BN = 16 * NT * WN;
   constexpr int stage_bytes = KS * 2 * (BM + BN) * (SWZ ? KB : KB + 4) * 4;
   constexpr int red_bytes = (KS - 1) * WM * WN * MT * NT * 4 * 64 * 4;
   constexpr int lds = stage_bytes > red_bytes ? stage_bytes : red_bytes;
-  auto kern = conv_igemm_kernel<MT, NT, WM, WN, KS, EPI, KB, SWZ>;
-  // the attribute is per device (a process may touch more than one GPU); one process per GPU and one launching
-  // thread per device are the documented use (include/sfnative.h), so the flag needs no lock
-  static bool attr_done[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-  if (!attr_done[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return e;
-    attr_done[dev] = true;
-  }
-  int maxblocks = 0;
-  for (int i = 0; i < L.nprob; ++i) {
-    const ConvProblem& P = L.p[i];
-    int Ptot = P.n_img * P.Hout * P.Wout;
-    int nb = ((Ptot + BN - 1) / BN) * ((P.cout_pad + BM - 1) / BM);
-    if (nb > maxblocks) maxblocks = nb;
-  }
-  if (maxblocks == 0) return hipSuccess;
-  int zs = 1;
-  for (int i = 0; i < L.nprob; ++i) zs = L.p[i].nsplit > zs ? L.p[i].nsplit : zs;
-  dim3 grid(maxblocks, L.nprob, zs), block(64 * WM * WN * KS);
-  hipLaunchKernelGGL(kern, grid, block, lds, stream, L);
+  constexpr auto kern = conv_igemm_kernel<MT, NT, WM, WN, KS, EPI, KB, SWZ>;
+  const hipError_t e = set_max_dynamic_lds<kern>(lds);
+  if (e != hipSuccess) return e;
+  const TileGrid g = tile_grid(L, BM, BN);
+  if (g.maxblocks == 0) return hipSuccess;
+  hipLaunchKernelGGL(kern, dim3(g.maxblocks, L.nprob, g.zs), dim3(64 * WM * WN * KS), lds, stream, L);
   return hipGetLastError();
 }
 
-// Tile configurations.  "S": small pixel counts (BEV latent 50x50): 16 px x 64 cout per
-// workgroup, 4-way in-workgroup split-K.  "L": large pixel counts (200x200 head): 64x64 tile.
-hipError_t launch_conv(const ConvLaunch& L, int epi, int cfg, hipStream_t stream) {
-  switch (cfg) {
-    case 0:   // S: MT4 NT1 1x1 waves, KS 4
-      switch (epi) {
-        case EPI_AFFINE: return launch_cfg<4, 1, 1, 1, 4, EPI_AFFINE>(L, stream);
-        case EPI_BLEND:  return launch_cfg<4, 1, 1, 1, 4, EPI_BLEND>(L, stream);
-        case EPI_LNG:    return launch_cfg<4, 1, 1, 1, 4, EPI_LNG>(L, stream);
-        case EPI_TRUST:  return launch_cfg<4, 1, 1, 1, 4, EPI_TRUST>(L, stream);
-        case EPI_SAMPLE: return launch_cfg<4, 1, 1, 1, 4, EPI_SAMPLE>(L, stream);
-      }
-      break;
-    case 1:   // L: 2x2 waves of 32x32
-      switch (epi) {
-        case EPI_AFFINE: return launch_cfg<2, 2, 2, 2, 1, EPI_AFFINE>(L, stream);
-        case EPI_BLEND:  return launch_cfg<2, 2, 2, 2, 1, EPI_BLEND>(L, stream);
-        case EPI_SAMPLE: return launch_cfg<2, 2, 2, 2, 1, EPI_SAMPLE>(L, stream);
-      }
-      break;
-    case 4:   // T: 4 waves x (64 cout x 16 px) = 64x64 tile, every epilogue; used with cross-WG split-K
-      switch (epi) {
-        case EPI_AFFINE: return launch_cfg<4, 1, 1, 4, 1, EPI_AFFINE>(L, stream);
-        case EPI_BLEND:  return launch_cfg<4, 1, 1, 4, 1, EPI_BLEND>(L, stream);
-        case EPI_LNG:    return launch_cfg<4, 1, 1, 4, 1, EPI_LNG>(L, stream);
-        case EPI_TRUST:  return launch_cfg<4, 1, 1, 4, 1, EPI_TRUST>(L, stream);
-        case EPI_SAMPLE: return launch_cfg<4, 1, 1, 4, 1, EPI_SAMPLE>(L, stream);
-      }
-      break;
-    case 9:   // 128 x 128, 8 waves (2x4) of 64x32
-      switch (epi) {
-        case EPI_AFFINE: return launch_cfg<4, 2, 2, 4, 1, EPI_AFFINE>(L, stream);
-        case EPI_BLEND:  return launch_cfg<4, 2, 2, 4, 1, EPI_BLEND>(L, stream);
-      }
-      break;
-    case 2:   // LN-capable large tile: 4 waves x (64 cout x 32 px)
-      switch (epi) {
-        case EPI_LNG:    return launch_cfg<4, 2, 1, 4, 1, EPI_LNG>(L, stream);
-        case EPI_TRUST:  return launch_cfg<4, 2, 1, 4, 1, EPI_TRUST>(L, stream);
-      }
-      break;
+// ---- the one mapping from (row of TILES, epilogue) to the instantiation: what the table does not list is not compiled and answers
+// hipErrorInvalidValue.  scale: the SCALE instantiation of an LDS-DMA row; mt / ks: the direct kernel's run-time tile
+template <int I>      // I = row * EPI_COUNT + epilogue
+static hipError_t launch_tile_i(const ConvLaunch& L, bool scale, int mt, int ks, hipStream_t stream) {
+  constexpr TileRow R = TILES[I / EPI_COUNT];
+  constexpr int EPI = I % EPI_COUNT;
+  constexpr bool listed = (R.epis >> EPI) & 1, has_scale = R.scaled_as == I / EPI_COUNT && ((E_SCALE >> EPI) & 1);
+  if constexpr (R.staging == TILE_STAGED && listed) return launch_cfg<R.MT, R.NT, R.WM, R.WN, R.KS, EPI>(L, stream);
+  if constexpr (R.staging == TILE_DIRECT && listed) return launch_direct_e<EPI>(L, mt, ks, stream);
+  if constexpr (R.staging == TILE_DMA && has_scale) {
+    if (scale) return launch_glds_t<R.MT, R.NT, R.WM, R.WN, EPI, true>(L, stream);
+  }
+  if constexpr (R.staging == TILE_DMA && listed) {
+    if (!scale) return launch_glds_t<R.MT, R.NT, R.WM, R.WN, EPI>(L, stream);
   }
   return hipErrorInvalidValue;
+}
+template <int... I>
+static hipError_t launch_tile(std::integer_sequence<int, I...>, const ConvLaunch& L, int epi, TileId tile, TileStaging staging, bool scale, int mt, int ks, hipStream_t stream) {
+  if (tile < 0 || tile >= TILE_COUNT || epi < 0 || epi >= EPI_COUNT || TILES[tile].staging != staging) return hipErrorInvalidValue;
+  hipError_t e = hipErrorInvalidValue;
+  (void)((tile * EPI_COUNT + epi == I && ((e = launch_tile_i<I>(L, scale, mt, ks, stream)), true)) || ...);
+  return e;
+}
+using AllTiles = std::make_integer_sequence<int, TILE_COUNT * EPI_COUNT>;
+
+hipError_t launch_conv(const ConvLaunch& L, int epi, TileId tile, hipStream_t stream) {
+  return launch_tile(AllTiles{}, L, epi, tile, TILE_STAGED, false, 0, 0, stream);
+}
+hipError_t launch_conv_direct(const ConvLaunch& L, int epi, int mt, int ks, hipStream_t stream) {
+  if (ks < 1 || ks > 8) return hipErrorInvalidValue;
+  return launch_tile(AllTiles{}, L, epi, TILE_DIRECT16, TILE_DIRECT, false, mt, ks, stream);
+}
+// a launch with an SE input scale, and the sampling epilogue, run the SCALE instantiation of the row the table names for them
+hipError_t launch_conv_glds(const ConvLaunch& L, int epi, TileId tile, hipStream_t stream) {
+  bool scaled = epi == EPI_SAMPLE;
+  for (int i = 0; i < L.nprob; ++i) scaled = scaled || (L.p[i].in_scale != nullptr);
+  if (scaled && tile >= 0 && tile < TILE_COUNT) tile = TILES[tile].scaled_as;
+  return launch_tile(AllTiles{}, L, epi, tile, TILE_DMA, scaled, 0, 0, stream);
 }
 
 }  // namespace sf

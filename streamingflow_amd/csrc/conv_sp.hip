@@ -1740,43 +1740,25 @@ constexpr int sp_launch_lds(bool fused) {
   return (direct > wino ? direct : wino) * 4;
 }
 template <int EPI, bool SCALE, int NT, bool B3>
-static hipError_t launch_sp_tb(const ConvLaunch& L, hipStream_t stream);
-template <int EPI, bool SCALE, int NT>
-static hipError_t launch_sp_t(const ConvLaunch& L, hipStream_t stream) {      // bf16x3: every problem carries split weights (dispatch.hip decides)
-  bool b3 = L.nprob > 0;
-  for (int i = 0; i < L.nprob; ++i) b3 = b3 && L.p[i].w3 != nullptr && L.p[i].use_w3;
-  return b3 ? launch_sp_tb<EPI, SCALE, NT, true>(L, stream) : launch_sp_tb<EPI, SCALE, NT, false>(L, stream);
-}
-template <int EPI, bool SCALE, int NT, bool B3>
 static hipError_t launch_sp_tb(const ConvLaunch& L, hipStream_t stream) {
-  auto kern = conv_sp_kernel<EPI, SCALE, NT, B3>;
-  static bool attr_done[64] = {};      // the attribute is per device
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-  if (!attr_done[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, sp_launch_lds<EPI, SCALE, NT, B3>(EPI == EPI_LNG));      // (only a LayerNorm launch can carry a fused 1x1 layer)
-    if (e != hipSuccess) return e;
-    attr_done[dev] = true;
-  }
-  int maxblocks = 0, zs = 1;
+  constexpr auto kern = conv_sp_kernel<EPI, SCALE, NT, B3>;
+  // the limit is set once, to the largest launch of the instantiation (only a LayerNorm launch can carry a fused 1x1 layer); a launch asks for what it needs
+  const hipError_t e = set_max_dynamic_lds<kern>(sp_launch_lds<EPI, SCALE, NT, B3>(EPI == EPI_LNG));
+  if (e != hipSuccess) return e;
+  const TileGrid g = tile_grid(L, SP_BM, 16 * NT);
   bool fused = false;
-  for (int i = 0; i < L.nprob; ++i) {
-    const ConvProblem& P = L.p[i];
-    fused = fused || P.fuse_w != nullptr;
-    const int Ptot = P.n_img * P.Hout * P.Wout;
-    const int nb = ((Ptot + 16 * NT - 1) / (16 * NT)) * ((P.cout_pad + SP_BM - 1) / SP_BM);
-    maxblocks = nb > maxblocks ? nb : maxblocks;
-    zs = P.nsplit > zs ? P.nsplit : zs;
-  }
-  if (maxblocks == 0) return hipSuccess;
+  for (int i = 0; i < L.nprob; ++i) fused = fused || L.p[i].fuse_w != nullptr;
+  if (g.maxblocks == 0) return hipSuccess;
   if (fused && EPI != EPI_LNG) return hipErrorInvalidValue;
   const int lds = sp_launch_lds<EPI, SCALE, NT, B3>(fused);      // + the fused 1x1 layer's chunk buffer
-  if (L.wg_base[L.nprob] > 0) {      // compact 1-D grid (the host filled wg_base for this tile size)
-    hipLaunchKernelGGL(kern, dim3(L.wg_base[L.nprob], 1, 1), dim3(SP_THREADS), lds, stream, L);
-    return hipGetLastError();
-  }
-  hipLaunchKernelGGL(kern, dim3(maxblocks, L.nprob, zs), dim3(SP_THREADS), lds, stream, L);
+  // compact 1-D grid where the host filled wg_base for this tile size
+  const dim3 grid = L.wg_base[L.nprob] > 0 ? dim3(L.wg_base[L.nprob], 1, 1) : dim3(g.maxblocks, L.nprob, g.zs);
+  hipLaunchKernelGGL(kern, grid, dim3(SP_THREADS), lds, stream, L);
   return hipGetLastError();
+}
+template <int EPI, bool SCALE, int NT>
+static hipError_t launch_sp_t(const ConvLaunch& L, hipStream_t stream) {
+  return launch_runs_bf16x3(L) ? launch_sp_tb<EPI, SCALE, NT, true>(L, stream) : launch_sp_tb<EPI, SCALE, NT, false>(L, stream);
 }
 
 template <int NT>

@@ -1166,18 +1166,13 @@ bool wino_same_geometry(const ConvProblem& a, const ConvProblem& b) {
 // reciprocals of the block decode
 template <int EPI, bool DIL = false, bool CAT = false, int TH_ = WN_TH, int GRP = 1, bool TALL = false>
 static hipError_t launch_wino5_t(const ConvLaunch& L, hipStream_t stream) {
-  void (*kern)(const ConvLaunch);
-  if constexpr (TALL) kern = conv_wino5t_kernel<EPI, CAT>;
-  else kern = conv_wino5_kernel<EPI, DIL, CAT, TH_, GRP>;
+  constexpr void (*kern)(const ConvLaunch) = [] {
+    if constexpr (TALL) return conv_wino5t_kernel<EPI, CAT>;
+    else return conv_wino5_kernel<EPI, DIL, CAT, TH_, GRP>;
+  }();
   constexpr int lds = Wino5Geo<DIL, CAT, TH_, TALL>::LDS_FLOATS * 4;
-  static bool attr_done[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-  if (!attr_done[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return e;
-    attr_done[dev] = true;
-  }
+  const hipError_t e = set_max_dynamic_lds<kern>(lds);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3((unsigned)((long)L.wg_base[1] * L.nprob), 1, 1), dim3(WN_THREADS), lds, stream, L);
   return hipGetLastError();
 }

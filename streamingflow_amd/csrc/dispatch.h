@@ -45,7 +45,7 @@ struct Tune {
   // 3x3 / 7x7 layers run in the Winograd form the flow kernel does not have.  Off by default
   int persist = geti("SF_PERSIST", 0);
   int b3_small_tiles = geti("SF_B3_SMALL_TILES", 0);   // experiment: bf16x3 layers with 128-multiple cout on 64 x 128 tiles (3 workgroups per CU) instead of 128 x 128 (2)
-  int wide64 = geti("SF_WIDE64", 0);               // 1: 64-cout layers at >= 131072 pixels on 64 x 256 tiles (variant 10) instead of 64 x 128
+  int wide64 = geti("SF_WIDE64", 0);               // 1: 64-cout layers at >= 131072 pixels on 64 x 256 tiles (TILE_DMA64x256) instead of 64 x 128
   int seg_maxph = geti("SF_SEG_MAXPH", 1 << 30);   // diagnostic: at most this many phases per persistent flow launch (1: every phase its own launch of the flow kernel)
   int wino = geti("SF_WINO", 1);                   // layers packed with Winograd weights run conv_wino.hip from wino_min_p pixels (0: direct form everywhere)
   int wino_min_p = geti("SF_WINO_MIN_P", 14000);   // measured (profiles/r04_zz_wino_min_p_sweep.txt, r04_zz_step_min_p_batched_latents.txt): 6 or more batched 50x50 latents
@@ -75,9 +75,8 @@ struct Tune {
   int split_min_chunks = geti("SF_SPLIT_MINCH", 2);
   int mid_tiles = geti("SF_MID_TILES", 1300);      // round 2: 640 -> 1300 (the 200x200 latent splits its 7x7 too: 1364 -> 1311 us)
   int glds = geti("SF_GLDS", 15);                  // LDS-DMA staging for large plain layers: bit 0 = 128-cout tiles, bit 1 = 64-cout tiles, bit 2 = LayerNorm-epilogue tiles, bit 3 = cross-workgroup split-K launches (0: register staging everywhere)
-  int glds_var = geti("SF_GLDS_VAR", -1);          // -1: shipped choice; 0..8: force a variant of launch_conv_glds (experiments)
   int small_dma = geti("SF_SMALL_DMA", 1);         // >= 0: plain layers below LARGE_P run on the LDS-DMA kernel (32x32 tiles); bit 0: GRU candidates too (pre-gated state)
-  int narrow = geti("SF_NARROW", 9);               // tile variant for layers with <= 32 output channels (32 cout x 128 px; -1: the 64-row tiles)
+  int narrow = geti("SF_NARROW", 9);               // tile for layers with <= 32 output channels (dispatch.hip: narrow_tile — 9: TILE_DMA32x128, 32 cout x 128 px; 4 / 6 / 7 / 10: 64 x 64 / 64 x 128 / 64 x 128 on four waves / 64 x 256; -1: the 64-row tiles as planned)
   int large_p = geti("SF_LARGE_P", 8192);          // measured: a 4-sample rollout (10000 px) is 18 % faster on the small-P kernels, 8 samples (20000 px) on the large tiles
   int mid_minch_ln = geti("SF_MID_MINCH_LN", 1);   // LayerNorm-epilogue layers at mid P take the 64x64 tiles from this many K chunks (the 1x1 of the trusting gate: 4-sample step 415 -> 408 us; 8: the round-1 rule, 64x128 tiles for short K)
   int sp_fuse_1x1 = geti("SF_SP_FUSE_1X1", 1);     // small-P kernel: the trusting gate's 1x1 layer runs inside the 7x7 layer's launch
@@ -133,6 +132,7 @@ void prof_enable(bool on);
 int prof_collect(int32_t* calls, double* ms, double* flops, double* bytes);      // sf_prof_collect
 int debug_stamps(void* buf);                                                     // sf_debug_stamps
 int debug_wino_plan(const sf_conv_w& w, int epi, int n_img, int Hin, int Win, int in_up, int nprob, int flags, int32_t* out, int n_out);   // sf_debug_wino_plan
+int debug_tiled_plan(const sf_conv_w* w, int epi, int n_img, int Hin, int Win, int in_up, int nprob, int flags, int32_t* out, int n_out);   // sf_debug_tiled_plan
 
 // Scratch for the cross-workgroup split-K path, carved from the caller's workspace by the top-level entry points for the duration of one
 // call (RAII; the pointer to it is thread-local inside dispatch.hip, no global allocation)

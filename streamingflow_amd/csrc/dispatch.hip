@@ -61,9 +61,9 @@ struct WinoLive { long split_wgs; bool cat_wide; int tall; };
 static WinoLive wino_live() { return {getl("SF_WINO_SPLIT_WGS", 512), geti("SF_WINO_CAT_WIDE", 1) != 0, geti("SF_WINO_TALL", -1)}; }
 const Tune& tune() { static const Tune t; return t; }
 
-static int pick_cfg(int P, int epi) {
-  if (epi == EPI_LNG || epi == EPI_TRUST) return P >= LARGE_P ? 2 : 0;
-  return P >= LARGE_P ? 1 : 0;
+static TileId pick_tile(int P, int epi) {
+  if (epi == EPI_LNG || epi == EPI_TRUST) return P >= LARGE_P ? TILE_LN64x128 : TILE_S16x64K4;
+  return P >= LARGE_P ? TILE_L64x64 : TILE_S16x64K4;
 }
 
 // Fill a problem from a packed layer + geometry.  Output spatial size follows the conv formula.
@@ -114,7 +114,7 @@ hipError_t prof_timed(const Cost& c, const std::function<hipError_t()>& launch, 
   }
   return e;
 }
-// Aggregates (and clears) the recorded launches by kernel key = cfg*8 + epi.  Arrays of length SF_PROF_KEYS (include/sfnative.h; part of the ABI version):
+// Aggregates (and clears) the recorded launches by kernel key = (key of the tile row / kernel family, _lib.py KEY_NAMES) * 8 + epi.  Arrays of length SF_PROF_KEYS (include/sfnative.h; part of the ABI version):
 // calls, total ms, total algorithmic flops, total algorithmic bytes.  Synchronises.
 int prof_collect(int32_t* calls, double* ms, double* flops, double* bytes) {
   for (int i = 0; i < SF_PROF_KEYS; ++i) { calls[i] = 0; ms[i] = 0; flops[i] = 0; bytes[i] = 0; }
@@ -302,8 +302,7 @@ struct FlowBuilder {
   }
   // record one launch group as a phase.  SF_ERR_UNSUPPORTED: the caller launches it the ordinary way (after flush()).
   int add(const ConvLaunch& L, int epi, bool scaled, int bn) {
-    bool all3 = L.nprob > 0;
-    for (int i = 0; i < L.nprob; ++i) all3 = all3 && L.p[i].w3 != nullptr && L.p[i].use_w3;
+    const bool all3 = launch_runs_bf16x3(L);
     const int cap = sp_flow_capacity(all3);
     if (L.wg_base[L.nprob] < 1 || L.wg_base[L.nprob] > cap || !sp_flow_has(epi, scaled, bn)) return SF_ERR_UNSUPPORTED;
     if (!phases.empty() && (all3 != b3 || (int)phases.size() >= tune().seg_maxph)) SF_TRY(flush());
@@ -462,15 +461,18 @@ constexpr int NOT_MINE = 1;      // (every SF_* status is <= 0)
 
 // A LayerNorm / trust epilogue over 65..128 channels (hidden sizes above every shipped config): all channels of a pixel must sit in one
 // wave: 128 cout x 64 px tiles of the LDS-DMA kernel, whatever the pixel count
-static int run_wide_ln(ConvLaunch& L, int epi, hipStream_t st) {
-  SF_TRY(seg_flush());
+static bool wide_ln_takes(const ConvLaunch& L) {
   for (int i = 0; i < L.nprob; ++i) {
     const ConvProblem& q = L.p[i];
-    if (q.gate || q.gather || q.in_scale || q.se_sum || !one_source_per_chunk(q) || !offsets_fit32(q, 256.0)) return SF_ERR_UNSUPPORTED;
+    if (q.gate || q.gather || q.in_scale || q.se_sum || !one_source_per_chunk(q) || !offsets_fit32(q, 256.0)) return false;
   }
+  return true;
+}
+static int run_wide_ln(ConvLaunch& L, int epi, hipStream_t st) {
+  SF_TRY(seg_flush());
+  if (!wide_ln_takes(L)) return SF_ERR_UNSUPPORTED;
   select_bf16x3(L);
-  // key 5 = "dmaLN128x64" (streamingflow_amd/_lib.py KERNEL_NAMES)
-  SF_HIP(timed([&] { return launch_conv_glds(L, epi, 5, 0, st); }, [&] { return direct_cost(5 * 8 + epi, L.p, L.nprob); }, st));
+  SF_HIP(timed([&] { return launch_conv_glds(L, epi, TILE_DMA_LN128x64, st); }, [&] { return direct_cost(TILES[TILE_DMA_LN128x64].key * 8 + epi, L.p, L.nprob); }, st));
   return SF_OK;
 }
 
@@ -650,8 +652,11 @@ static void wino_why(const ConvProblem* ps, int n, int epi) {
 // 7x7 + LayerNorm layer as nine 3x3 tap groups (EPI_LNG) and the sampling layer (EPI_SAMPLE).  The profiler prices a launch at its EXECUTED
 // FLOPs (key 16).  The members of a group are independent layers: those the kernel takes run on it, the others stay one group (the ASPP
 // group: three dilated 3x3 branches + the 1x1 branch)
+static bool wino_considers(int P, int epi) {      // run_wino looks at the layers of a group at all
+  return tune().wino && P >= tune().wino_min_p && (epi == EPI_AFFINE || epi == EPI_BLEND || epi == EPI_LNG || epi == EPI_SAMPLE);
+}
 static int run_wino(const ConvProblem* ps, int n, int P, int epi, hipStream_t st) {
-  if (!tune().wino || P < tune().wino_min_p || !(epi == EPI_AFFINE || epi == EPI_BLEND || epi == EPI_LNG || epi == EPI_SAMPLE)) return NOT_MINE;
+  if (!wino_considers(P, epi)) return NOT_MINE;
   bool takes[SF_MAX_GROUP];
   int n_wino = 0;
   for (int i = 0; i < n; ++i) n_wino += (takes[i] = wino_runs(ps[i], epi)) ? 1 : 0;
@@ -832,9 +837,8 @@ static int run_sp(ConvLaunch& L, int epi, hipStream_t st) {
   return SF_OK;
 }
 
-// Tiled / LDS-DMA kernels, deciding.  cfg: tile config of launch_conv (3: launch_conv_direct with mt / ks); glds_tile >= 0: launch_conv_glds
-// with that tile and variant instead
-struct TiledPlan { int cfg = 0, mt = 0, ks = 1, glds_tile = -1, glds_var = 4; };
+// Tiled / LDS-DMA kernels, deciding: the row of TILES (sf_launch.h) the launch runs on; mt / ks: the direct kernel's run-time tile
+struct TiledPlan { TileId tile = TILE_S16x64K4; int mt = 0, ks = 1; };
 // cross-workgroup split-K on 64x64 tiles: K slices, slabs and tickets into L, or L untouched where the scratch does not hold them
 static bool tiled_split(ConvLaunch& L, const SplitCtx& scratch) {
   // workgroup budget shared in proportion to each problem's work (tiles x chunks)
@@ -862,9 +866,22 @@ static bool tiled_split(ConvLaunch& L, const SplitCtx& scratch) {
   if (!fits) for (int i = 0; i < L.nprob; ++i) { L.p[i].nsplit = 0; L.p[i].slab = nullptr; L.p[i].counters = nullptr; }
   return fits;
 }
+// SF_NARROW: the tile of a 64-cout-family launch whose problems all have <= 32 output channels.  The values are the variant numbers the switch
+// has always taken; one that names no tile fails the launch (TILE_NONE, tiled_plan)
+static TileId narrow_tile(int v) {
+  switch (v) {
+    case 4: return TILE_DMA64x64;
+    case 6: return TILE_DMA64x128;
+    case 7: return TILE_DMA64x128W4;
+    case 9: return TILE_DMA32x128;
+    case 10: return TILE_DMA64x256;
+  }
+  return TILE_NONE;
+}
 // LDS-DMA staging (conv_glds_kernel) where the launch qualifies
 static void tiled_glds(const ConvLaunch& L, int epi, TiledPlan& T) {
-  const int n = L.nprob, cfg = T.cfg;
+  const int n = L.nprob;
+  const TileId staged = T.tile;
   const bool plain_epi = epi == EPI_AFFINE || epi == EPI_BLEND || epi == EPI_SAMPLE;
   bool plain = true;      // what every form needs: no reset gate while staging, a stageable SE scale, one source tensor per chunk
   int nscaled = 0;
@@ -878,37 +895,36 @@ static void tiled_glds(const ConvLaunch& L, int epi, TiledPlan& T) {
   // Plain large layers (no reset gate / SE scale / neighbour table / split-K): LDS-DMA staging with the barrier in the
   // middle of the MFMA stream.  Measured (profiles/r01_v_*): 128x128 tiles +2 %, 64-cout layers
   // +7 % on 64x128 tiles once there are >= 1024 of them, +3 % on 64x64 tiles below that.
-  if (tune().glds && (((cfg == 1 || cfg == 9) && plain_epi) || (cfg == 2 && (epi == EPI_LNG || epi == EPI_TRUST) && (tune().glds & 4)))) {
+  if (tune().glds && (((staged == TILE_L64x64 || staged == TILE_L128x128) && plain_epi) || (staged == TILE_LN64x128 && (epi == EPI_LNG || epi == EPI_TRUST) && (tune().glds & 4)))) {
     bool ok = plain;
     for (int i = 0; i < n; ++i) ok = ok && L.p[i].nsplit <= 1 && offsets_fit32(L.p[i], 256.0);
-    if (ok && cfg == 9 && (tune().glds & 1)) T.glds_tile = 0;
-    if (ok && cfg == 1 && (tune().glds & 2)) {
-      T.glds_tile = 1; T.glds_var = pmin >= 131072 ? (tune().wide64 ? 10 : 6) : 4;
+    if (ok && staged == TILE_L128x128 && (tune().glds & 1)) T.tile = TILE_DMA128x128;
+    if (ok && staged == TILE_L64x64 && (tune().glds & 2)) {
+      T.tile = pmin >= 131072 ? (tune().wide64 ? TILE_DMA64x256 : TILE_DMA64x128) : TILE_DMA64x64;
       bool narrow = true;      // every problem has at most 32 output channels: half of a 64-row tile would multiply zeros
       for (int i = 0; i < n; ++i) narrow = narrow && L.p[i].cout_pad <= 32;
-      if (narrow && tune().narrow >= 0) T.glds_var = tune().narrow;
+      if (narrow && tune().narrow >= 0) T.tile = narrow_tile(tune().narrow);
     }
-    if (ok && cfg == 2 && nscaled == 0) T.glds_tile = 2;
+    if (ok && staged == TILE_LN64x128 && nscaled == 0) T.tile = TILE_DMA_LN64x128;
   }
-  if ((tune().glds & 8) && cfg == 4) {   // cross-workgroup split-K launches (the slab hand-off is shared); SE-scaled layers on the SCALE instantiation
+  if ((tune().glds & 8) && staged == TILE_SPLIT64x64) {   // cross-workgroup split-K launches (the slab hand-off is shared); SE-scaled layers on the SCALE instantiation
     bool ok = plain && ((nscaled == 0 && epi != EPI_SAMPLE) || (nscaled == n && (epi == EPI_AFFINE || epi == EPI_SAMPLE)));
     for (int i = 0; i < n; ++i) ok = ok && !L.p[i].gather && offsets_fit32(L.p[i], 256.0);
-    if (ok) T.glds_tile = 4;
+    if (ok) T.tile = TILE_DMA_SPLIT64x64;
   }
   // small pixel counts: the same kernel on 32x32 tiles beats the direct-fragment kernel by 5-15 % per plain layer
   // (profiles/r01_v_sweep_glds_wide_tiles.txt; single-sample rollout 5.10 -> 4.64 ms with the pre-gated candidates).
   // SF_SMALL_DMA=-1 switches it off, 0 keeps the reset gate in the candidate's staging.  LayerNorm epilogues on
   // 64x32 tiles were slower than the direct kernel and stay there.
-  if (tune().small_dma >= 0 && (cfg == 0 || cfg == 3) && plain_epi) {
+  if (tune().small_dma >= 0 && (staged == TILE_S16x64K4 || staged == TILE_DIRECT16) && plain_epi) {
     bool ok = plain;
     for (int i = 0; i < n; ++i) ok = ok && !L.p[i].gather && L.p[i].nsplit <= 1;
-    if (ok) { T.glds_tile = 3; T.glds_var = tune().small_dma; }
-    if (tune().glds_var >= 0) T.glds_var = tune().glds_var;
+    if (ok) T.tile = TILE_DMA32x32;
   }
 }
 static int tiled_plan(ConvLaunch& L, int P, int epi, const SplitCtx* scratch, TiledPlan& T) {
   const int n = L.nprob;
-  T.cfg = pick_cfg(P, epi);
+  T.tile = pick_tile(P, epi);
   bool gathered = false;
   int chunks_max = 0, tiles_total = 0;
   for (int i = 0; i < n; ++i) {
@@ -918,17 +934,17 @@ static int tiled_plan(ConvLaunch& L, int P, int epi, const SplitCtx* scratch, Ti
   }
   if (gathered) {            // sparse convolution: only the LDS-staged kernels read the neighbour table
     if (epi != EPI_AFFINE) return SF_ERR_UNSUPPORTED;
-    if (T.cfg == 0) T.cfg = 1;
+    if (T.tile == TILE_S16x64K4) T.tile = TILE_L64x64;
   }
-  if (T.cfg == 1 && (epi == EPI_AFFINE || epi == EPI_BLEND)) {
+  if (T.tile == TILE_L64x64 && (epi == EPI_AFFINE || epi == EPI_BLEND)) {
     // measured (profiles/r01_e_sweep_large_tiles.txt): 128x128 tiles with 8 waves win 7-10 % once
     // there are >= ~1000 of them and cout is a multiple of 128; 64x64 wins everywhere else
     bool big = true;
     for (int i = 0; i < n; ++i) big = big && (L.p[i].cout_pad % 128 == 0) && (pixels(L.p[i]) >= 131072);
-    if (big && !(tune().b3_small_tiles && L.p[0].w3 != nullptr)) T.cfg = 9;
+    if (big && !(tune().b3_small_tiles && L.p[0].w3 != nullptr)) T.tile = TILE_L128x128;
   }
   // small pixel counts: direct-fragment kernel (no LDS staging), see conv_igemm.hip
-  if (T.cfg == 0 && tune().direct && !gathered) {
+  if (T.tile == TILE_S16x64K4 && tune().direct && !gathered) {
     const bool ln = (epi == EPI_LNG || epi == EPI_TRUST);
     int cp_max = 0, cp_gcd = 0;
     bool ok = true;
@@ -944,33 +960,76 @@ static int tiled_plan(ConvLaunch& L, int P, int epi, const SplitCtx* scratch, Ti
     else T.mt = tune().mt ? tune().mt : ((cp_gcd % 32 == 0) ? 2 : 1)   /* measured: 32-row tiles (twice the workgroups) beat 64-row ones */;
     T.ks = tune().ks ? tune().ks : (chunks_max + tune().chunks_per_wave - 1) / tune().chunks_per_wave;
     T.ks = T.ks < 1 ? 1 : (T.ks > 8 ? 8 : T.ks);
-    if (ok && T.mt) T.cfg = 3;
+    if (ok && T.mt) T.tile = TILE_DIRECT16;
   }
   // ... or, preferred: 64x64 tiles with the K range split across workgroups (4x fewer weight
   // re-reads than 16-pixel tiles, and enough workgroups for all 256 CUs)
   // measured (profiles/r01_d_sweep_convs.txt): the slab publish + ticket + acquire costs ~8 us, so
   // it only pays for the long-K layers (7x7: 196 chunks, 68 -> 44 us)
-  const bool split_small = (T.cfg == 0 || T.cfg == 3) && chunks_max >= tune().split_from;
+  const bool split_small = (T.tile == TILE_S16x64K4 || T.tile == TILE_DIRECT16) && chunks_max >= tune().split_from;
   // a few batched samples (P = 8k..40k pixels): the large-tile kernels would have too few tiles,
   // each walking the whole K range; split the K range instead (also keeps LayerNorm layers on 64x64)
-  const bool split_mid = (T.cfg == 1 || T.cfg == 2) && tiles_total < tune().mid_tiles && chunks_max >= (T.cfg == 2 ? tune().mid_minch_ln : 8);
+  const bool split_mid = (T.tile == TILE_L64x64 || T.tile == TILE_LN64x128) && tiles_total < tune().mid_tiles && chunks_max >= (T.tile == TILE_LN64x128 ? tune().mid_minch_ln : 8);
   if ((split_small || split_mid) && tune().split && scratch && tiled_split(L, *scratch))
-    T.cfg = (split_mid && tune().split_cfg == 1 && (epi == EPI_AFFINE || epi == EPI_BLEND || epi == EPI_SAMPLE)) ? 1 : 4;
+    T.tile = (split_mid && tune().split_cfg == 1 && (epi == EPI_AFFINE || epi == EPI_BLEND || epi == EPI_SAMPLE)) ? TILE_L64x64 : TILE_SPLIT64x64;
   tiled_glds(L, epi, T);
-  return SF_OK;
+  return T.tile == TILE_NONE ? SF_ERR_LAUNCH : SF_OK;      // (an SF_NARROW that names no tile: what the launcher's hipErrorInvalidValue became)
 }
 static int run_tiled(ConvLaunch& L, int P, int epi, hipStream_t st) {
   SF_TRY(seg_flush());
   TiledPlan T;
   SF_TRY(tiled_plan(L, P, epi, g_split, T));
   L.stamp_slot = next_stamp_slot();
-  if (T.glds_tile >= 0) select_bf16x3(L);
+  const TileStaging staging = TILES[T.tile].staging;
+  if (staging == TILE_DMA) select_bf16x3(L);
   auto launch = [&]() -> hipError_t {
-    if (T.glds_tile >= 0) return launch_conv_glds(L, epi, T.glds_tile, T.glds_var, st);
-    return T.cfg == 3 ? launch_conv_direct(L, epi, T.mt, T.ks, st) : launch_conv(L, epi, T.cfg, st);
+    if (staging == TILE_DMA) return launch_conv_glds(L, epi, T.tile, st);
+    return staging == TILE_DIRECT ? launch_conv_direct(L, epi, T.mt, T.ks, st) : launch_conv(L, epi, T.tile, st);
   };
-  const int key = T.glds_tile < 0 ? T.cfg : T.glds_tile == 4 ? 15 : T.glds_tile == 0 ? 10 : T.glds_tile == 2 ? 13 : (T.glds_var == 6 || T.glds_var == 10) ? 12 : 11;
-  SF_HIP(timed(launch, [&] { return direct_cost(key * 8 + epi, L.p, L.nprob); }, st));
+  SF_HIP(timed(launch, [&] { return direct_cost(TILES[T.tile].key * 8 + epi, L.p, L.nprob); }, st));
+  return SF_OK;
+}
+
+// sf_debug_tiled_plan (include/sfnative.h): what run() will decide for a group of the layers w[0 .. nprob) on one geometry, by run()'s own
+// family predicates (wide_ln_takes, wino_considers + wino_runs, sp_takes) in run()'s order.  Host only: the pointers that decide are non-null
+// placeholders, nothing is dereferenced, no HIP call
+int debug_tiled_plan(const sf_conv_w* w, int epi, int n_img, int Hin, int Win, int in_up, int nprob, int flags, int32_t* out, int n_out) {
+  if (!out || n_out < SF_TILED_PLAN_INTS || nprob < 1 || nprob > SF_MAX_GROUP || epi < 0 || epi >= EPI_COUNT || n_img < 1 || Hin < 1 || Win < 1 || in_up < 0 || in_up > 1) return SF_ERR_INVALID;
+  float* const ph = reinterpret_cast<float*>(uintptr_t(64));
+  const bool ln_epi = epi == EPI_LNG || epi == EPI_TRUST;
+  ConvLaunch L;
+  std::memset(&L, 0, sizeof(L));
+  L.nprob = nprob;
+  int P = 0;
+  bool wide_ln = false;
+  for (int i = 0; i < nprob; ++i) {
+    ConvProblem& q = L.p[i];
+    q = problem(w[i], ph, w[i].c1 > 0 ? ph : nullptr, ph, n_img, Hin, Win, in_up);
+    if (flags & 1) q.gather = reinterpret_cast<const int*>(ph);
+    if (flags & 2) q.gate = ph;
+    if (flags & 4) q.in_scale = ph;
+    if (flags & 8) q.w3 = ph;
+    P = std::max(P, (int)pixels(q));
+    if (ln_epi && q.cout_pad > 128) return SF_ERR_UNSUPPORTED;
+    wide_ln = wide_ln || (ln_epi && q.cout_pad > 64);
+  }
+  for (int i = 0; i < SF_TILED_PLAN_INTS; ++i) out[i] = 0;
+  TiledPlan T;
+  if (wide_ln) {
+    if (!wide_ln_takes(L)) return SF_ERR_UNSUPPORTED;
+    T.tile = TILE_DMA_LN128x64;
+  } else {
+    for (int i = 0; i < nprob; ++i)
+      if (wino_considers(P, epi) && wino_runs(L.p[i], epi)) out[0] = 1;
+    if (!out[0] && sp_takes(L.p, nprob, epi)) out[0] = 2;
+    if (out[0]) return SF_OK;
+    const SplitCtx scratch{ph, SPLIT_SLAB_FLOATS, reinterpret_cast<unsigned*>(ph), SPLIT_COUNTERS};
+    SF_TRY(tiled_plan(L, P, epi, (flags & 16) ? &scratch : nullptr, T));
+  }
+  const bool scaled = epi == EPI_SAMPLE || (flags & 4);
+  out[1] = T.tile; out[2] = TILES[T.tile].staging == TILE_DMA && scaled ? TILES[T.tile].scaled_as : T.tile;
+  out[3] = T.mt; out[4] = T.ks; out[5] = TILES[T.tile].key;
+  for (int i = 0; i < nprob; ++i) out[6 + i] = L.p[i].nsplit;
   return SF_OK;
 }
 

@@ -47,6 +47,23 @@ def wino_plan(c0, c1, cout, n, H, W, dil=1, in_up=0, k=3, epi=0, nprob=1, flags=
     return dict(takes=bool(out[0]), form=out[1], segs=[tuple(out[3 + 4 * s:7 + 4 * s]) for s in range(out[2])], wgs32=out[11])
 
 
+def tiled_plan(layers, n, H, W, epi=0, flags=0, in_up=0):
+    """What the conv dispatch decides for ONE launch group of `layers` (dicts: c0, c1, cout, k, and optionally dil, stride, wino = the layer
+    was packed with Winograd weights) on n images of H x W (sf_debug_tiled_plan: host arithmetic under the switches in force, no GPU; the
+    weight pointers are placeholders nobody reads).  flags: 1 neighbour table, 2 reset gate while staging, 4 SE input scale, 8 split-bf16
+    weights, 16 split-K scratch.  dict(family 0 tiled / 1 Winograd / 2 small-P, row planned, row run, mt, ks, key, nsplit per layer)"""
+    import ctypes
+    from streamingflow_amd import _lib
+    ws = (_lib.ConvW * len(layers))()
+    for w, l in zip(ws, layers):
+        k, dil, cin = l["k"], l.get("dil", 1), l["c0"] + l["c1"]
+        w.w, w.cout, w.cout_pad, w.c0, w.c1, w.cin_pad = 64, l["cout"], (l["cout"] + 15) // 16 * 16, l["c0"], l["c1"], (cin + 31) // 32 * 32
+        w.kh, w.kw, w.dil, w.stride, w.pad, w.act, w.w_wino = k, k, dil, l.get("stride", 1), dil * (k - 1) // 2, 0, 64 if l.get("wino") else None
+    out = (ctypes.c_int32 * _lib.SF_TILED_PLAN_INTS)()
+    _lib.check(_lib.lib().sf_debug_tiled_plan(ws, epi, n, H, W, in_up, len(layers), flags, out, len(out)), "sf_debug_tiled_plan")
+    return dict(family=out[0], row=out[1], runs=out[2], mt=out[3], ks=out[4], key=out[5], nsplit=list(out[6:6 + len(layers)]))
+
+
 def gold(name):
     return np.load(os.path.join(GOLD, name))
 

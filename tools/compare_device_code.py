@@ -53,16 +53,23 @@ def kernels(so):
                 cur = {}
             cur[k] = v.strip()
         recs.append(cur)
-        code = {}
+        lines = {}
         name = None
         for ln in dis.split("\n"):
             m = re.match(r"[0-9a-f]+ <(.+)>:$", ln)
             if m:
                 name = m.group(1)
-                code[name] = hashlib.sha1()
+                lines[name] = []
             elif name and ln.strip():
                 # instruction text without its address / encoding comment; branch targets are relative to the kernel's own symbol
-                code[name].update(re.sub(r"\s*//.*$", "", ln).encode())
+                lines[name].append(re.sub(r"\s*//.*$", "", ln))
+        code = {}
+        for name, ls in lines.items():
+            # a "..." that ENDS a symbol is objdump's mark for the zero fill behind the last kernel of a section: which kernel that is follows
+            # the order of instantiation, and the fill is no instruction.  A "..." anywhere else counts
+            while ls and ls[-1].strip() == "...":
+                ls.pop()
+            code[name] = hashlib.sha1("".join(ls).encode())
         for r in recs:
             if "name" in r and "vgpr_count" in r:
                 n = r["name"]
