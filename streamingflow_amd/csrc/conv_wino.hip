@@ -11,6 +11,8 @@
 // cells as nine 3x3 tap groups (GRP = 9, EPI_LNG); both in front of conv_wino5_kernel.
 // The 32-tile AFFINE / BLEND launches run the tall-tile form F(4,3) along y x F(2,3) along x (conv_wino5t_kernel, TALL below: 12 multiplies
 // per 2x2 outputs; tools/winograd42_study.py: <= 9.4e-6 on the BEV outputs) from a second transformed copy of the weights behind the first.
+// The 7x7 + LayerNorm layer's tap groups run the same tall arithmetic on 32-tile blocks, without the y-positions whose weights are zero for
+// every layer (conv_wino7t_kernel: 96 executed products per 2x2 outputs instead of 144; described at step7 in the kernel body).
 // Weights are transformed once at pack time (pack.hip: U[cin/16][16 positions][cout_pad][16], sf_conv_w::w_wino).  The kernel
 // (conv_wino5_kernel, round 5) is described in front of it; the round-4 kernel it replaced (U through an LDS ring, one wave = 16 cout x
 // 16 tiles x all 16 positions: 0.57-0.66 of the fp32 MFMA peak against 0.64-0.74) lives in the history of this file, the F(4x4, 3x3)
@@ -224,7 +226,8 @@ struct Wino5Geo {
 // that profiles and the resource checks tell the two arithmetics apart)
 template <int EPI, bool DIL, bool CAT, int TH_, int GRP, bool TALL>
 __device__ __forceinline__ void conv_wino5_body(const ConvLaunch& L) {
-  static_assert(!TALL || (GRP == 1 && (EPI == EPI_AFFINE || EPI == EPI_BLEND)), "tall tiles: the 3x3 AFFINE / BLEND forms");
+  static_assert(!TALL || (GRP == 1 && (EPI == EPI_AFFINE || EPI == EPI_BLEND)) || (GRP == 9 && EPI == EPI_LNG),
+                "tall tiles: the 3x3 AFFINE / BLEND forms and the 7x7 tap groups");
   static_assert(GRP == 1 || (GRP == 9 && !DIL && TH_ == 4), "tap groups: the 7x7 form");
   static_assert((EPI == EPI_LNG) == (GRP == 9), "the LayerNorm epilogue belongs to the 7x7 form");
   static_assert(EPI != EPI_SAMPLE || (!DIL && TH_ == 4), "the sampling layer: plain / concatenated 32-tile forms");
@@ -312,7 +315,7 @@ __device__ __forceinline__ void conv_wino5_body(const ConvLaunch& L) {
   const size_t n_in = (CAT && img + 1 < P.n_img) ? 2 : 1;
   const __amdgpu_buffer_rsrc_t rsrc0 = make_rsrc(PX.in0 + (size_t)img * img_px * P.in0_cs, n_in * img_px * P.in0_cs * sizeof(float));
   const __amdgpu_buffer_rsrc_t rsrc1 = make_rsrc(PX.in1 ? PX.in1 + (size_t)img * img_px * P.in1_cs : PX.in0, PX.in1 ? n_in * img_px * P.in1_cs * sizeof(float) : 0);
-  const __amdgpu_buffer_rsrc_t rsrc_u = make_rsrc(PX.w_wino + (TALL ? wino_tall_offset(P.cout_pad, P.cin_pad, 3) : 0),
+  const __amdgpu_buffer_rsrc_t rsrc_u = make_rsrc(PX.w_wino + (TALL ? wino_tall_offset(P.cout_pad, P.cin_pad, GRP == 9 ? 7 : 3) : 0),
                                                   (size_t)nkc * G::NPOS * P.cout_pad * 16 * sizeof(float));
 #endif
   constexpr bool SCALED = G::SC > 0 && (EPI == EPI_AFFINE || EPI == EPI_SAMPLE);
@@ -591,7 +594,7 @@ __device__ __forceinline__ void conv_wino5_body(const ConvLaunch& L) {
   f32x4 A[TALL ? 3 : 2][2];                                     // [ring slot = step & 1 (tall: step % 3)][mb]
   if constexpr (TALL) {
 #pragma unroll
-    for (int p = 0; p < 3; ++p) { A[p][0] = load_A6(0, p, 0); A[p][1] = load_A6(0, p, 1); }
+    for (int p = 0; p < 3; ++p) { A[p][0] = load_A6(0, p + (GRP > 1 ? 1 : 0), 0); A[p][1] = load_A6(0, p + (GRP > 1 ? 1 : 0), 1); }      // (tap groups: chunk 0 starts at y-position 1)
   } else {
     A[0][0] = load_A(0, 0); A[0][1] = load_A(0, 1);
     A[1][0] = load_A(1, 0); A[1][1] = load_A(1, 1);
@@ -670,7 +673,88 @@ __device__ __forceinline__ void conv_wino5_body(const ConvLaunch& L) {
     }
   };
   (void)step6; (void)chunk6;
-  auto step = [&](const int kc, auto p_c, auto first_c) {
+  // tall tap groups (the 7x7): rows 0 and 8 of the 9x9 frame are zero, so U42 of the groups a = 0 is zero at y-position 0 (G4 row 0 reads g0
+  // alone) and U42 of the groups a = 2 at y-position 5 (G4 row 5 reads g2 alone), for every layer (wino_weights42_kernel).  Those steps are
+  // not run: chunks of the a = 0 groups are y-positions 1 .. 5, chunks of the a = 2 groups 0 .. 4 — 16 of 18 steps.  The 3 nkc_g chunks of
+  // one a run as triples of 15 steps, so that the A ring (three steps deep) keeps compile-time slots: slot = (step of the triple) % 3, and
+  // the step re-loads its slot with the step three behind it — in this triple, or in the next triple / six-step chunk, whose first
+  // y-position (o_next) is wave-uniform scalar arithmetic.
+  auto u_so = [&](int k2, int yp2) -> int {
+    if (k2 >= nkc) { k2 = nkc - 1; yp2 = 4; }                    // the tail re-loads the last step (no branch in the MFMA stream)
+    return (k2 * 24 + yp2 * 4 + ih) * u_pos_bytes;
+  };
+  auto step7 = [&](const int kc, auto yp_c, auto slot_c, const int so_next) {
+    constexpr int yp = decltype(yp_c)::value, slot = decltype(slot_c)::value;
+    const f32x4 Bf = wn_lds_read128(Vbuf + (kc & 1) * G::V_FLOATS + yp * 256 + b_cur);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        if (SF_W5_ABL & 16) acc[yp][mb][0] = (e == 0 && mb == 0) ? acc[yp][mb][0] + A[slot][mb] * Bf : acc[yp][mb][0];
+        else acc[yp][mb][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[slot][mb][e], Bf[e], acc[yp][mb][0], 0, 0, 0);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#if defined(__HIP_DEVICE_COMPILE__)
+      if (!(SF_W5_ABL & 4)) A[slot][mb] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_u, u_voff + mb * 1024, so_next, 0));
+#endif
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+  // barrier M and the next chunk's transform behind the third step of the chunk, as in chunk6
+  auto mid7 = [&](const int kc, const bool more) {
+    if (more) {
+      wn_wait(6);                                               // younger than the patch: the A loads of the chunk's first three steps
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      if (!(SF_W5_ABL & 8)) wn_barrier();                                             // M: patch(kc + 1) complete
+      if (!(SF_W5_ABL & 1)) transform(kc + 1);
+    }
+  };
+  auto end7 = [&](const bool more) {
+    if (more) {
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      if (!(SF_W5_ABL & 8)) wn_barrier();                                             // B: V(kc + 1) published, patch buffer free
+    }
+  };
+  // chunk c of the triple that starts at chunk kc0: five steps, y-positions O .. O + 4 (O = 1: groups a = 0, O = 0: groups a = 2)
+  auto chunk5 = [&](const int kc0, auto o_c, auto c_c, const int o_next) {
+    constexpr int O = decltype(o_c)::value, c = decltype(c_c)::value;
+    const int kc = kc0 + c;
+    const bool more = kc + 1 < nkc;
+    auto so_of = [&](auto l_c) -> int {
+      constexpr int s3 = c * 5 + decltype(l_c)::value + 3;
+      if constexpr (s3 < 15) return u_so(kc0 + s3 / 5, s3 % 5 + O);
+      else return u_so(kc0 + 3, s3 - 15 + o_next);
+    };
+    if (more && !(SF_W5_ABL & 2)) issue_patch(kc + 1);                              // behind barrier B: every wave is done with transform(kc)
+    step7(kc, std::integral_constant<int, O>{}, std::integral_constant<int, (c * 5) % 3>{}, so_of(std::integral_constant<int, 0>{}));
+    step7(kc, std::integral_constant<int, O + 1>{}, std::integral_constant<int, (c * 5 + 1) % 3>{}, so_of(std::integral_constant<int, 1>{}));
+    step7(kc, std::integral_constant<int, O + 2>{}, std::integral_constant<int, (c * 5 + 2) % 3>{}, so_of(std::integral_constant<int, 2>{}));
+    mid7(kc, more);
+    step7(kc, std::integral_constant<int, O + 3>{}, std::integral_constant<int, (c * 5 + 3) % 3>{}, so_of(std::integral_constant<int, 3>{}));
+    step7(kc, std::integral_constant<int, O + 4>{}, std::integral_constant<int, (c * 5 + 4) % 3>{}, so_of(std::integral_constant<int, 4>{}));
+    end7(more);
+  };
+  auto triple7 = [&](const int kc0, auto o_c) {
+    const int o_next = (decltype(o_c)::value == 1 && kc0 + 3 < 3 * nkc_g) ? 1 : 0;      // the next triple's first y-position
+    chunk5(kc0, o_c, std::integral_constant<int, 0>{}, o_next);
+    chunk5(kc0, o_c, std::integral_constant<int, 1>{}, o_next);
+    chunk5(kc0, o_c, std::integral_constant<int, 2>{}, o_next);
+  };
+  // a chunk of the groups a = 1: all six y-positions; the chunk behind it (a = 1 or a = 2) starts at y-position 0
+  auto chunk6g = [&](const auto kc) {      // (generic: instantiated by the tall tap-group kernel alone)
+    if (!(SF_W5_ABL & 2)) issue_patch(kc + 1);
+    step7(kc, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, u_so(kc, 3));
+    step7(kc, std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{}, u_so(kc, 4));
+    step7(kc, std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{}, u_so(kc, 5));
+    mid7(kc, true);
+    step7(kc, std::integral_constant<int, 3>{}, std::integral_constant<int, 0>{}, u_so(kc + 1, 0));
+    step7(kc, std::integral_constant<int, 4>{}, std::integral_constant<int, 1>{}, u_so(kc + 1, 1));
+    step7(kc, std::integral_constant<int, 5>{}, std::integral_constant<int, 2>{}, u_so(kc + 1, 2));
+    end7(true);
+  };
+  (void)u_so; (void)step7; (void)mid7; (void)end7; (void)chunk5; (void)triple7; (void)chunk6g;
+  auto step =[&](const int kc, auto p_c, auto first_c) {
     constexpr int p = decltype(p_c)::value, slot = p & 1;
     constexpr bool first = decltype(first_c)::value;
     const float* const vb = Vbuf + (G::NVB == 2 ? (kc & 1) : 0) * G::V_FLOATS + p * WT * 16 + b_cur;
@@ -721,7 +805,15 @@ __device__ __forceinline__ void conv_wino5_body(const ConvLaunch& L) {
       }
     }
   };
-  if constexpr (TALL) {
+  if constexpr (TALL && GRP > 1) {
+    // with steps left out, no chunk touches every accumulator first: they start at zero explicitly
+#pragma unroll
+    for (int p = 0; p < 6; ++p) { acc[p][0][0] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc[p][1][0] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
+    const int nka = 3 * nkc_g;                                  // chunks of one group row a (a multiple of three)
+    for (int kc = 0; kc < nka; kc += 3) triple7(kc, std::integral_constant<int, 1>{});
+    for (int kc = nka; kc < 2 * nka; ++kc) chunk6g(kc);
+    for (int kc = 2 * nka; kc < nkc; kc += 3) triple7(kc, std::integral_constant<int, 0>{});
+  } else if constexpr (TALL) {
     chunk6(0, std::true_type{}, std::true_type{});
     for (int kc = 1; kc + 1 < nkc; ++kc) chunk6(kc, std::false_type{}, std::true_type{});
     chunk6(nkc - 1, std::false_type{}, std::false_type{});
@@ -1007,6 +1099,11 @@ template <int EPI, bool CAT>
 __global__ __launch_bounds__(WN_THREADS, 4) void conv_wino5t_kernel(const ConvLaunch L) {
   conv_wino5_body<EPI, false, CAT, WN_TH, 1, true>(L);
 }
+// the 7x7 + LayerNorm layer's nine tap groups in the tall form, zero y-positions left out (a kernel of its own name, as above)
+template <bool CAT>
+__global__ __launch_bounds__(WN_THREADS, 4) void conv_wino7t_kernel(const ConvLaunch L) {
+  conv_wino5_body<EPI_LNG, false, CAT, WN_TH, 9, true>(L);
+}
 
 // weights: packed direct form w[cout_pad][kh * kw * cin_pad] (tap-major, channel-minor) -> U[group][cin_pad/16][16][cout_pad][16] = G g G^T.
 // 3x3: one group.  7x7 (round 6, the small-P kernel's Winograd block only): the kernel sits in a 9x9 frame of zeros and is cut into 3 x 3
@@ -1167,7 +1264,8 @@ bool wino_same_geometry(const ConvProblem& a, const ConvProblem& b) {
 template <int EPI, bool DIL = false, bool CAT = false, int TH_ = WN_TH, int GRP = 1, bool TALL = false>
 static hipError_t launch_wino5_t(const ConvLaunch& L, hipStream_t stream) {
   constexpr void (*kern)(const ConvLaunch) = [] {
-    if constexpr (TALL) return conv_wino5t_kernel<EPI, CAT>;
+    if constexpr (TALL && GRP == 9) return conv_wino7t_kernel<CAT>;
+    else if constexpr (TALL) return conv_wino5t_kernel<EPI, CAT>;
     else return conv_wino5_kernel<EPI, DIL, CAT, TH_, GRP>;
   }();
   constexpr int lds = Wino5Geo<DIL, CAT, TH_, TALL>::LDS_FLOATS * 4;
@@ -1176,11 +1274,12 @@ static hipError_t launch_wino5_t(const ConvLaunch& L, hipStream_t stream) {
   hipLaunchKernelGGL(kern, dim3((unsigned)((long)L.wg_base[1] * L.nprob), 1, 1), dim3(WN_THREADS), lds, stream, L);
   return hipGetLastError();
 }
-// what the tall-tile arithmetic can address: a launch of 32-tile blocks in the plain / concatenated AFFINE or BLEND form of a 3x3 layer whose
-// U42 copy stays inside a 32-bit byte offset (WHICH of them run tall is dispatch.hip: wino_tall)
+// what the tall-tile arithmetic can address: a launch of 32-tile blocks in the plain / concatenated AFFINE or BLEND form of a 3x3 layer, or
+// the 7x7 LayerNorm layer's tap groups, whose U42 copy stays inside a 32-bit byte offset (WHICH of them run tall is dispatch.hip: wino_tall)
 bool wino_takes_tall(const ConvProblem& q, int epi, WinoForm form, int th) {
-  return th == WN_TH && (form == WINO_PLAIN || form == WINO_CAT) && (epi == EPI_AFFINE || epi == EPI_BLEND) && q.KH == 3 && q.KW == 3 && q.dil == 1 &&
-         4.0 * 24 * q.cout_pad * q.cin_pad < 2147483648.0;
+  if (th != WN_TH || (form != WINO_PLAIN && form != WINO_CAT) || q.dil != 1) return false;
+  if (epi == EPI_LNG) return q.KH == 7 && q.KW == 7 && 4.0 * 9 * 24 * q.cout_pad * q.cin_pad < 2147483648.0;
+  return (epi == EPI_AFFINE || epi == EPI_BLEND) && q.KH == 3 && q.KW == 3 && 4.0 * 24 * q.cout_pad * q.cin_pad < 2147483648.0;
 }
 // one problem per launch, or up to SF_MAX_GROUP of identical geometry
 hipError_t launch_conv_wino(const ConvLaunch& L, int epi, WinoForm form, int th, bool tall, hipStream_t stream) {
@@ -1188,6 +1287,7 @@ hipError_t launch_conv_wino(const ConvLaunch& L, int epi, WinoForm form, int th,
   const bool cat = form == WINO_CAT, small = th == WN_TH_SMALL;
   if (tall) {
     if (!wino_takes_tall(L.p[0], epi, form, th)) return hipErrorInvalidValue;
+    if (epi == EPI_LNG) return cat ? launch_wino5_t<EPI_LNG, false, true, WN_TH, 9, true>(L, stream) : launch_wino5_t<EPI_LNG, false, false, WN_TH, 9, true>(L, stream);
     if (epi == EPI_AFFINE) return cat ? launch_wino5_t<EPI_AFFINE, false, true, WN_TH, 1, true>(L, stream) : launch_wino5_t<EPI_AFFINE, false, false, WN_TH, 1, true>(L, stream);
     return cat ? launch_wino5_t<EPI_BLEND, false, true, WN_TH, 1, true>(L, stream) : launch_wino5_t<EPI_BLEND, false, false, WN_TH, 1, true>(L, stream);
   }

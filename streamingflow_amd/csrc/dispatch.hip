@@ -435,14 +435,17 @@ static Cost direct_cost(int key, const ConvProblem* ps, int n) {
 // Winograd form, priced at its EXECUTED flops: 16 products per 2x2 outputs, (cin, cout) pair and tap group (nine for the 7x7); the
 // plan's form names the launch (_lib.KERNEL_NAMES: wino128x32t / wino64x64t / wino64x32t2, also its form with concatenated images /
 // wino64x32t2dil)
-// (tall_frac: the part of the layer's tile rows that runs in the tall form, 12 products per 2x2-tile equivalent)
-static double wino_products(double tall_frac) { return 16.0 - 4.0 * tall_frac; }
+// (tall_frac: the part of the layer's tile rows that runs in the tall form, 12 products per 2x2-tile equivalent and tap group; the tall
+// tap groups of the 7x7 leave out the two y-positions of 18 whose weights are zero: 9 x 12 x 16 / 18 = 96 executed products)
+static double wino_products(const ConvProblem& q, double tall_frac) {
+  return q.KH == 7 ? 144.0 - 48.0 * tall_frac : 16.0 - 4.0 * tall_frac;
+}
 static Cost wino_cost(const ConvProblem* ps, int n, int epi, WinoForm form, double tall_frac) {
   Cost c{(16 + (form == WINO_CAT ? 2 : (int)form)) * 8 + epi, 0, 0};
   for (int i = 0; i < n; ++i) {
     const ConvProblem& q = ps[i];
     const double grp = q.KH == 7 ? 9.0 : 1.0;
-    c.flops += 2.0 * wino_products(tall_frac) * grp * wino_tiles(q) * q.cout * (q.c0 + q.c1);
+    c.flops += 2.0 * wino_products(q, tall_frac) * wino_tiles(q) * q.cout * (q.c0 + q.c1);
     c.bytes += 4.0 * ((double)q.n_img * q.Hin * q.Win * (q.c0 + q.c1) + 16.0 * grp * q.cout * (q.c0 + q.c1) + (double)q.n_img * q.Hout * q.Wout * q.cout);
   }
   return c;
@@ -537,7 +540,7 @@ static bool wino_segment(const ConvProblem& P, int nprob, WinoForm form, int th,
 }
 // The arithmetic of a planned launch, decided apart from the plan (forms, blocks, grids and windows do not depend on it).  SF_WINO_TALL: 0 =
 // F(2x2) everywhere, 1 = the tall form wherever the kernel has it (conv_wino.hip: wino_takes_tall — 32-tile blocks of the plain /
-// concatenated AFFINE and BLEND forms), unset = the measured rule, which is the same: profiles/wino_tall_layers_{off,on}.txt show no layer
+// concatenated AFFINE and BLEND forms and of the 7x7 LayerNorm layer's tap groups), unset = the measured rule, which is the same: profiles/wino_tall_layers_{off,on}.txt show no layer
 // class of the batched forward slower in the tall form.  Remainder launches of split layers are 16-tile blocks: F(2x2)
 static bool wino_tall(const ConvProblem& P, int epi, WinoForm form, const WinoSeg& s, const WinoLive& live) {
   return live.tall != 0 && wino_takes_tall(P, epi, form, s.th);
@@ -636,7 +639,7 @@ static int wino_list_launch(ConvLaunch& W1, const WinoPlan& W, int epi, hipStrea
   std::fprintf(stderr, "[sf-wino] n=%d %dx%d c=%d+%d->%d epi=%d act=%d mode=%d add=%d add_scale=%d out2=%d in_scale=%d bias_img=%d clamp=%d dil=%d up=%d var=%d us=%.1f gflop=%.3f\n",
                q.n_img, q.Hout, q.Wout, q.c0, q.c1, q.cout, epi, q.act, q.mode, q.add != nullptr, q.add_scale != nullptr, q.out2 != nullptr,
                q.in_scale != nullptr, q.bias_per_img, q.clamp_from >= 0, q.dil, q.in_up, (int)W.form, ms * 1e3,
-               2.0 * wino_products(wino_tall_frac(W)) * wino_tiles(q) * q.cout * (q.c0 + q.c1) * 1e-9);
+               2.0 * wino_products(q, wino_tall_frac(W)) * wino_tiles(q) * q.cout * (q.c0 + q.c1) * 1e-9);
   return SF_OK;
 }
 // SF_WINO_WHY: which large 3x3 launches keep the direct form, one line each on stderr

@@ -113,7 +113,7 @@ hipError_t launch_conv_sp(const ConvLaunch& L, int epi, bool scaled, int bn, hip
 // blocks, SE-scaled concatenated images on 16-tile blocks)
 constexpr int WN_COUT_T = 64, WN_TW = 8, WN_TH = 4, WN_TH_SMALL = 2;
 enum WinoForm { WINO_PLAIN = 2, WINO_DIL = 3, WINO_CAT = 4 };
-// tall: the F(4,3) x F(2,3) arithmetic of the 32-tile plain / concatenated AFFINE and BLEND forms (dispatch.hip: wino_tall decides)
+// tall: the F(4,3) x F(2,3) arithmetic of the 32-tile plain / concatenated AFFINE and BLEND forms and of the 7x7 LNG tap groups (dispatch.hip: wino_tall decides)
 hipError_t launch_conv_wino(const ConvLaunch& L, int epi, WinoForm form, int th, bool tall, hipStream_t stream);
 // the packed Winograd weights of a layer: U (16 positions) and behind it U42 (24 positions, the tall form), both [group][cin_pad / 16][position][cout_pad][16];
 // floats from sf_conv_w::w_wino to U42, and of both copies together (cout_pad is a multiple of 64: every part stays 256-byte aligned)
