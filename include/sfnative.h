@@ -589,6 +589,32 @@ int sf_instance_track_fwd(const int32_t* counts, const int64_t* pos_sums, const 
 size_t sf_instance_labels_ws_bytes(int B, int T, int H, int W, int num_instances);
 int sf_instance_labels_fwd(const int64_t* instance, const float* theta, int B, int T, int H, int W, int num_instances, double sigma,
                            float ignore_index, float* center, float* offset, float* flow, void* ws, size_t ws_bytes, void* stream);
+/* sf_panoptic_score_fwd — PanopticMetric.update's scoring (metrics.py:143-229) of B samples of T frames on the joint histograms
+ *   sf_confusion_frames_fwd wrote: hist [B*T][K][K] int64 (rows = ground-truth id, columns = predicted id, id 0 = background),
+ *   n_per_frame = the pixels of a frame, `bad` = that call's flag.  ADDS one update's tallies into iou, true_positive, false_positive
+ *   and false_negative (fp32, n_classes entries each; class 0 = background, class 1 = the vehicles; the others are left alone).
+ *   Per frame: areas = row / column sums, union = area_gt[g] + area_pred[p] - joint, IoU = union > 0 ? (float(joint) + 1e-9f) /
+ *   (float(union) + 1e-9f) : 0 in fp32, every operation rounded on its own, a hit when IoU > 0.5f.  A hit at [0][0]: one class-0 true
+ *   positive and its IoU.  A hit at [g >= 1][p >= 1]: with `track` != 0 and g's latest hit in an earlier frame of the same sample on
+ *   another p, one false negative and one false positive; otherwise one true positive and its IoU.  A ground-truth / predicted thing
+ *   with pixels and no hit in its row / column: one false negative / false positive.  IoU sums are exact fp64 sums rounded to fp32
+ *   once; every counter receives ONE add per call, from one thread: the counters are bitwise those of the host statement
+ *   (streamingflow_amd/metrics.py: _score_frame) and the same on every run.
+ *   *errors (int32) is OR-ed with SF_PANOPTIC_ERR_RANGE when *bad != 0 and with SF_PANOPTIC_ERR_NO_BACKGROUND when no frame of the
+ *   call has a ground-truth pixel of id 0 (metrics.py:107); a call that sets a bit adds NOTHING to the counters.
+ *   Launch 1: one workgroup per frame (areas through LDS; per g the hit column and IoU, the frame's unmatched counts, into the
+ *   workspace).  Launch 2: one workgroup, a lane per (sample, g) walks the frames with the partner in a register.  Workspace: hit
+ *   column int32 [B*T][K] | hit IoU fp32 [B*T][K] | frame tallies int32 [B*T][4], each part on a multiple of 256 bytes.  Enqueues only:
+ *   no allocation, no synchronisation, nothing read back.  SF_ERR_INVALID: a NULL pointer, B / T / K / n_per_frame < 1, n_classes < 2,
+ *   K > SF_PANOPTIC_MAX_K, n_per_frame >= 2^23 (beyond it fp32 no longer holds the areas exactly and a row could hold two hits),
+ *   B*T*K >= 2^31; SF_ERR_WORKSPACE: ws_bytes < sf_panoptic_score_ws_bytes(B, T, K) (0 for invalid sizes). */
+#define SF_PANOPTIC_MAX_K 256
+#define SF_PANOPTIC_ERR_RANGE 1
+#define SF_PANOPTIC_ERR_NO_BACKGROUND 2
+size_t sf_panoptic_score_ws_bytes(int B, int T, int K);
+int sf_panoptic_score_fwd(const int64_t* hist, long n_per_frame, int B, int T, int K, int n_classes, int track, const int32_t* bad,
+                          float* iou, float* true_positive, float* false_positive, float* false_negative, int32_t* errors, void* ws,
+                          size_t ws_bytes, void* stream);
 
 /* ---- the planner (streamingflow/cost.py, models/planning_model.py, metrics.py:263-396).  Every pointer below is a device pointer
  * except `factors`; every call enqueues only: no allocation, no synchronisation, nothing read back.  Grids are square (H == W = G).

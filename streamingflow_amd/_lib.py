@@ -18,6 +18,8 @@ SF_PROF_KEYS = 168
 SF_WINO_PLAN_INTS = 13     # include/sfnative.h: int32 entries sf_debug_wino_plan writes
 SF_TILED_PLAN_INTS = 10    # ... and sf_debug_tiled_plan
 PACK_TRANSPOSED, PACK_FOLD_DUP, PACK_INTERLEAVE, PACK_BF16X3, PACK_WINOGRAD = 1, 2, 4, 8, 16      # SF_PACK_* of sfnative.h
+SF_PANOPTIC_MAX_K = 256      # include/sfnative.h: ids 0 .. 255 per frame in sf_panoptic_score_fwd
+SF_PANOPTIC_ERR_RANGE, SF_PANOPTIC_ERR_NO_BACKGROUND = 1, 2
 ACT = {"none": 0, "lrelu": 1, "relu": 2, "tanh": 3, "sigmoid": 4, "gelu": 5}
 SOLVER = {"euler": 0, "midpoint": 1, "rk4": 2}
 OP_JUMP, OP_STEP = 0, 1
@@ -175,6 +177,8 @@ SIGNATURES = {
     "sf_instance_labels_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.c_double, C.c_float, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sf_instance_track_ws_bytes": (_sz, [_i, _i, _i]),
     "sf_instance_track_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, C.c_float, _vp, _vp, _vp, _sz, _vp]),
+    "sf_panoptic_score_ws_bytes": (_sz, [_i, _i, _i]),
+    "sf_panoptic_score_fwd": (_i, [_vp, C.c_long, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sf_plan_cost_ws_bytes": (_sz, []),
     "sf_plan_cost_fwd": (_i, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, C.POINTER(C.c_float * 7), C.c_float, C.c_float,
                               _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),

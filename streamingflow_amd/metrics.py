@@ -11,7 +11,8 @@ How it is computed here.  Every statistic of both metrics is a function of joint
     false negatives / false positives; a matched vehicle whose ground-truth id was matched to a different predicted id
     in an earlier frame is an id switch and counts as one false negative plus one false positive (:190-197).
 The histograms of a whole [batch, time] block come from ONE kernel launch (``sf_confusion_frames_fwd``, integer
-atomics: exact) and one device -> host copy; the bookkeeping on the resulting few-dozen-entry matrices is numpy.
+atomics: exact) and one device -> host copy; the bookkeeping on the resulting few-dozen-entry matrices is numpy.  With a bound on the
+ids (``PanopticMetric(max_instances=M)``) the bookkeeping is ``sf_panoptic_score_fwd`` on the device instead and nothing is copied.
 """
 from typing import Optional
 
@@ -126,16 +127,70 @@ class IntersectionOverUnion(_Accumulator):
 
 
 class PanopticMetric(_Accumulator):
-    def __init__(self, n_classes: int, temporally_consistent: bool = True, vehicles_id: int = 1, compute_on_step: bool = False):
+    """Panoptic quality of instance id maps (module docstring).  Two paths:
+
+    ``max_instances=None`` (the default): ``update`` sizes its tables from the data — it copies three maxima and then every per-frame
+    histogram to the host, scores them in numpy and raises at once on a negative id or a ground truth without background.
+
+    ``max_instances=M`` (an int in 1 .. ``MAX_INSTANCES``): ``update`` only enqueues — the conversion of the maps to int64,
+    ``sf_confusion_frames_fwd`` into a [batch * time, M + 1, M + 1] table and ``sf_panoptic_score_fwd``, which adds into the four
+    counters in place — and returns; nothing is read back, so a whole evaluation step can be captured in a graph.  The counters are
+    bitwise those of the default path.  M MUST bound every id of both maps: the ground-truth ids AND the predicted ids after tracking
+    (tracking hands out new ids over a sequence, so a sequence's ids can exceed the 100 raw ids a frame is capped to).  Data errors
+    cannot raise in ``update`` any more; they are OR-ed into a device int over the updates since the last ``reset()``: an id of either
+    map outside [0, M] (negative ids included), or an update whose ``gt_instance`` holds no pixel of id 0.  Such an update adds nothing
+    to the counters, and ``compute()`` — which reads the int once — raises ``ValueError`` naming the cause until ``reset()``.  Frames
+    must have fewer than 2^23 pixels, and ``n_classes`` must be at least 2 (class 1 takes the vehicles)."""
+
+    MAX_INSTANCES = _lib.SF_PANOPTIC_MAX_K - 1
+    MAX_FRAME_PIXELS = 1 << 23
+
+    def __init__(self, n_classes: int, temporally_consistent: bool = True, vehicles_id: int = 1, compute_on_step: bool = False,
+                 max_instances: Optional[int] = None):
         super().__init__(("iou", "true_positive", "false_positive", "false_negative"), n_classes)
         self.keys = list(self._counter_names)
         self.n_classes, self.temporally_consistent, self.vehicles_id = n_classes, temporally_consistent, vehicles_id
+        if max_instances is not None:
+            if isinstance(max_instances, bool) or not isinstance(max_instances, int) or not 1 <= max_instances <= self.MAX_INSTANCES:
+                raise ValueError("max_instances must be an int in 1 .. %d, got %r" % (self.MAX_INSTANCES, max_instances))
+            if n_classes < THING_CLASS + 1:
+                raise ValueError("max_instances needs n_classes >= 2: class 1 takes the vehicles")
+            self.register_buffer("_errors", torch.zeros(1, dtype=torch.int32), persistent=False)      # SF_PANOPTIC_ERR_* bits since reset()
+        self.max_instances = max_instances
+
+    def _update_device(self, pred_instance, gt_instance):
+        batch, steps, h, w = gt_instance.shape
+        if batch * steps < 1 or not 1 <= h * w < self.MAX_FRAME_PIXELS:
+            raise ValueError("max_instances: expected at least one frame of 1 .. 2^23 - 1 pixels")
+        dev, K = pred_instance.device, self.max_instances + 1
+        if self.iou.device != dev:                  # first update on another device: the state moves, not the data
+            for n in self._counter_names + ("_errors",):
+                setattr(self, n, getattr(self, n).to(dev))
+        if any(getattr(self, n).dtype != torch.float32 for n in self._counter_names):
+            raise RuntimeError("PanopticMetric: the counters must stay float32")
+        hist, flag = frame_confusions(pred_instance, gt_instance, batch * steps, K)
+        L = _lib.lib()
+        need = L.sf_panoptic_score_ws_bytes(batch, steps, K)
+        if need == 0:
+            raise ValueError("max_instances: batch * time * (max_instances + 1) must stay below 2^31")
+        ws = torch.empty((need + 3) // 4, dtype=torch.int32, device=dev)
+        track = bool(self.temporally_consistent) and THING_CLASS == self.vehicles_id
+        _lib.check(L.sf_panoptic_score_fwd(ptr(hist), h * w, batch, steps, K, self.n_classes, int(track), ptr(flag), ptr(self.iou),
+                                           ptr(self.true_positive), ptr(self.false_positive), ptr(self.false_negative), ptr(self._errors),
+                                           ptr(ws), need, runtime.stream_ptr(dev)), "panoptic_score")
+
+    def reset(self):
+        super().reset()
+        if self.max_instances is not None:
+            self._errors.zero_()
 
     def update(self, pred_instance, gt_instance):
         """pred_instance, gt_instance: [batch, time, H, W] instance ids (0 = background)."""
         runtime.require_cuda(pred_instance, gt_instance)
         if pred_instance.shape != gt_instance.shape or gt_instance.dim() != 4:
             raise ValueError("expected two [batch, time, H, W] id tensors of the same shape")
+        if self.max_instances is not None:
+            return self._update_device(pred_instance, gt_instance)
         batch, steps = gt_instance.shape[:2]
         top = torch.stack([pred_instance.max(), gt_instance.max(), -gt_instance.min()]).cpu()
         assert int(top[2]) == 0, "ID 0 of gt_instance must be background"
@@ -180,6 +235,13 @@ class PanopticMetric(_Accumulator):
         tally["false_positive"][THING_CLASS] += int(np.count_nonzero(present_pred & ~matched_pred))
 
     def compute(self):
+        if self.max_instances is not None:
+            bits = int(self._errors.item())
+            causes = [text for bit, text in ((_lib.SF_PANOPTIC_ERR_RANGE, "an instance id outside [0, max_instances = %d]" % self.max_instances),
+                                             (_lib.SF_PANOPTIC_ERR_NO_BACKGROUND, "an update whose gt_instance has no pixel of id 0 (ID 0 of "
+                                                                                  "gt_instance must be background)")) if bits & bit]
+            if causes:
+                raise ValueError("PanopticMetric: since the last reset() there was " + " and ".join(causes) + "; those updates were not counted")
         one = torch.ones_like(self.true_positive)
         denominator = torch.maximum(self.true_positive + 0.5 * self.false_positive + 0.5 * self.false_negative, one)
         return {"pq": self.iou / denominator, "sq": self.iou / torch.maximum(self.true_positive, one),
