@@ -1,10 +1,17 @@
 """ctypes binding of libsfnative.so (C ABI: include/sfnative.h).
 
+The header is the only place a prototype or a public constant is written: `SIGNATURES` and every `SF_*` name below are read from
+it at import (_header.py), so the binding cannot drift from the contract.  What stays by hand are the `Structure` classes, whose
+field names the Python code uses and whose sizes `lib()` proves against the library (sf_abi_check).  Arguments: scalars by their C
+type, a pointer to a public struct as POINTER(its class), every other pointer or array as c_void_p.
+
 The library is the product: there is no CPU or PyTorch fallback.  `lib()` raises if the shared
 object is missing or does not export every symbol the header declares.
 """
 import ctypes as C
 import os
+
+from . import _header
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SF_LIB_PATH") or os.path.join(_HERE, "libsfnative.so")   # SF_LIB_PATH: experiment builds only
@@ -12,17 +19,19 @@ LIB_PATH = os.environ.get("SF_LIB_PATH") or os.path.join(_HERE, "libsfnative.so"
 f32p = C.POINTER(C.c_float)
 i32p = C.POINTER(C.c_int32)
 
-SF_COEF_STRIDE = 12
-SF_ABI_VERSION = 7       # include/sfnative.h: changes whenever a public struct changes layout
-SF_PROF_KEYS = 168
-SF_WINO_PLAN_INTS = 13     # include/sfnative.h: int32 entries sf_debug_wino_plan writes
-SF_TILED_PLAN_INTS = 10    # ... and sf_debug_tiled_plan
-PACK_TRANSPOSED, PACK_FOLD_DUP, PACK_INTERLEAVE, PACK_BF16X3, PACK_WINOGRAD = 1, 2, 4, 8, 16      # SF_PACK_* of sfnative.h
-SF_PANOPTIC_MAX_K = 256      # include/sfnative.h: ids 0 .. 255 per frame in sf_panoptic_score_fwd
-SF_PANOPTIC_ERR_RANGE, SF_PANOPTIC_ERR_NO_BACKGROUND = 1, 2
-ACT = {"none": 0, "lrelu": 1, "relu": 2, "tanh": 3, "sigmoid": 4, "gelu": 5}
-SOLVER = {"euler": 0, "midpoint": 1, "rk4": 2}
-OP_JUMP, OP_STEP = 0, 1
+_PROTOS, CONSTANTS, _STRUCT_NAMES = _header.read()
+globals().update(CONSTANTS)      # SF_OK, SF_ERR_*, SF_ABI_VERSION, SF_COEF_STRIDE, SF_PROF_KEYS, SF_*_PLAN_INTS, SF_PANOPTIC_*, ... under their header names
+
+
+def _family(prefix):
+    return {k[len(prefix):].lower(): v for k, v in CONSTANTS.items() if k.startswith(prefix)}
+
+
+PACK_TRANSPOSED, PACK_FOLD_DUP, PACK_INTERLEAVE, PACK_BF16X3, PACK_WINOGRAD = (
+    CONSTANTS["SF_PACK_" + n] for n in ("TRANSPOSED", "FOLD_DUP", "INTERLEAVE", "BF16X3", "WINOGRAD"))
+ACT = _family("SF_ACT_")            # {"none": 0, "lrelu": 1, ...}
+SOLVER = _family("SF_SOLVER_")      # {"euler": 0, "midpoint": 1, "rk4": 2}
+OP_JUMP, OP_STEP = CONSTANTS["SF_OP_JUMP"], CONSTANTS["SF_OP_STEP"]
 
 
 class ConvW(C.Structure):
@@ -79,132 +88,29 @@ class BottleneckW(C.Structure):
     _fields_ = [("down", ConvW), ("conv", ConvW), ("up", ConvW), ("proj", ConvW), ("downsample", C.c_int32)]
 
 
-# SF_STRUCT_* order of sfnative.h: what lib() hands to sf_abi_check
-ABI_STRUCTS = (ConvW, GruW, DualW, ResW, PModelW, EncoderW, DecoderW, ConvNextW, DeepLabW, BottleneckW, BottleW)
+STRUCTS = {"sf_conv_w": ConvW, "sf_gru_w": GruW, "sf_dual_w": DualW, "sf_res_w": ResW, "sf_pmodel_w": PModelW, "sf_encoder_w": EncoderW,
+           "sf_decoder_w": DecoderW, "sf_convnext_w": ConvNextW, "sf_deeplab_w": DeepLabW, "sf_bottleneck_w": BottleneckW, "sf_bottle_w": BottleW}
+assert set(STRUCTS) == set(_STRUCT_NAMES), set(STRUCTS) ^ set(_STRUCT_NAMES)
+# in the header's SF_STRUCT_* order (SF_STRUCT_CONV_W = 0 is sf_conv_w): what lib() hands to sf_abi_check
+_ids = _family("SF_STRUCT_")
+ABI_STRUCTS = tuple(STRUCTS["sf_" + k] for k in sorted(_ids, key=_ids.get) if k != "count")
+assert len(ABI_STRUCTS) == _ids["count"]
 
-_vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t
-# name -> (restype, argtypes); every symbol declared in include/sfnative.h
-_f3 = C.POINTER(C.c_float * 3)
-_i3 = C.POINTER(C.c_int32 * 3)
-_f6 = C.POINTER(C.c_float * 6)
-SIGNATURES = {
-    "sf_version": (_i, []),
-    "sf_set_flow_mode": (_i, [_i]),
-    "sf_flow_errors": (_i, [_vp]),
-    "sf_abi_version": (_i, []),
-    "sf_abi_sizeof": (_sz, [_i]),
-    "sf_abi_check": (_i, [_i, C.POINTER(_sz), _i]),
-    "sf_status_string": (C.c_char_p, [_i]),
-    "sf_nchw_to_nhwc": (_i, [_vp, _vp, _i, _i, _i, _vp]),
-    "sf_nhwc_to_nchw": (_i, [_vp, _vp, _i, _i, _i, _vp]),
-    "sf_nchw_to_nhwc_strided": (_i, [_vp, _sz, _vp, _sz, _i, _i, _i, _vp]),
-    "sf_nhwc_to_nchw_strided": (_i, [_vp, _sz, _vp, _sz, _i, _i, _i, _vp]),
-    "sf_conv2d_fwd": (_i, [C.POINTER(ConvW), _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "sf_conv2d_repeat": (_i, [C.POINTER(ConvW), _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
-    "sf_gru_cell_fwd": (_i, [C.POINTER(GruW), _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
-    "sf_gru_cell_ws_bytes": (_sz, [_i, _i, _i, _i]),
-    "sf_gru_ode_cell_fwd": (_i, [C.POINTER(GruW), _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
-    "sf_spatial_gru_fwd": (_i, [C.POINTER(GruW), _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
-    "sf_spatial_gru_ws_bytes": (_sz, [_i, _i, _i, _i]),
-    "sf_dual_cell_fwd": (_i, [C.POINTER(DualW), _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
-    "sf_dual_cell_ws_bytes": (_sz, [_i, _i, _i, _i]),
-    "sf_trust_mix_fwd": (_i, [C.POINTER(DualW), _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
-    "sf_bottleblock_fwd": (_i, [C.POINTER(BottleW), _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
-    "sf_bottleblock_ws_bytes": (_sz, [_i, _i, _i, _i]),
-    "sf_infer_state_fwd": (_i, [C.POINTER(PModelW), _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
-    "sf_infer_state_ws_bytes": (_sz, [_i, _i, _i, _i]),
-    "sf_ode_step_fwd": (_i, [C.POINTER(DualW), C.POINTER(PModelW), _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i,
-                             _vp, _sz, _vp]),
-    "sf_ode_step_ws_bytes": (_sz, [_i, _i, _i, _i]),
-    "sf_nnfo_rollout_fwd": (_i, [C.POINTER(DualW), C.POINTER(DualW), C.POINTER(PModelW), _i, _i, i32p, _i, _vp, _vp,
-                                 _vp, _i, i32p, _i, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
-    "sf_nnfo_rollout_philox_fwd": (_i, [C.POINTER(DualW), C.POINTER(DualW), C.POINTER(PModelW), _i, _i, i32p, _i, _vp, _vp,
-                                        _vp, _i, i32p, _i, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
-    "sf_nnfo_rollout_resume_fwd": (_i, [C.POINTER(DualW), C.POINTER(DualW), C.POINTER(PModelW), _i, _i, i32p, _i, _vp, _vp,
-                                        _vp, _i, i32p, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
-    "sf_nnfo_rollout_resume_philox_fwd": (_i, [C.POINTER(DualW), C.POINTER(DualW), C.POINTER(PModelW), _i, _i, i32p, _i, _vp, _vp,
-                                               _vp, _i, i32p, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
-    "sf_nnfo_rollout_carry_bytes": (_sz, [_i, _i, _i, _i]),
-    "sf_infer_state_philox_fwd": (_i, [C.POINTER(PModelW), _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
-    "sf_nnfo_rollout_ws_bytes": (_sz, [_i, _i, _i, _i]),
-    "sf_small_encoder_fwd": (_i, [C.POINTER(EncoderW), _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
-    "sf_small_encoder_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "sf_small_decoder_fwd": (_i, [C.POINTER(DecoderW), _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
-    "sf_small_decoder_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "sf_convnext_block_fwd": (_i, [C.POINTER(ConvNextW), _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
-    "sf_convnext_block_ws_bytes": (_sz, [_i, _i, _i, _i]),
-    "sf_deeplab_head_fwd": (_i, [C.POINTER(DeepLabW), _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
-    "sf_deeplab_head_planar_fwd": (_i, [C.POINTER(DeepLabW), _vp, _vp, _i, _i, _i, _i, _sz, _sz, _vp, _sz, _vp]),
-    "sf_deeplab_head_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "sf_bottleneck_fwd": (_i, [C.POINTER(BottleneckW), _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
-    "sf_bottleneck_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "sf_dist_head_fwd": (_i, [C.POINTER(ConvW), _vp, _vp, _i, _i, _i, _i, _i, C.c_float, C.c_float, _vp, _sz, _vp]),
-    "sf_dist_head_ws_bytes": (_sz, [_i, _i]),
-    "sf_conv2d_ex_fwd": (_i, [C.POINTER(ConvW), _vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
-    "sf_conv2d_ex_ws_bytes": (_sz, []),
-    "sf_upsample_bilinear2_add_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "sf_channel_mean_ws_bytes": (_sz, [_i, _i]),
-    "sf_channel_mean_fwd": (_i, [_vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
-    "sf_broadcast_channels_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "sf_bev_pool_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "sf_lift_index_ws_bytes": (_sz, [_i, _i]),
-    "sf_lift_index_fwd": (_i, [_vp, _i, _i, _f3, _f3, _i3, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "sf_lift_index_coords_fwd": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "sf_lift_index_rig_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f3, _f3, _i3, _vp, _vp, _vp, _sz, _vp]),
-    "sf_lift_pool_fwd": (_i, [_vp, _vp, _vp, _i, _i, _vp, C.c_float, _vp, _vp]),
-    "sf_lift_pool_fused_fwd": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, C.c_float, _vp, _vp]),
-    "sf_depth_softmax_fwd": (_i, [_vp, _vp, _i, _i, _i, _vp]),
-    "sf_hard_voxelize_ws_bytes": (_sz, [_i]),
-    "sf_logsigmoid_fwd": (_i, [_vp, _vp, _sz, _vp]),
-    "sf_dynamic_voxelize_fwd": (_i, [_vp, _i, _i, _f3, _f6, _vp, _vp]),
-    "sf_hard_voxelize_fwd": (_i, [_vp, _i, _i, _f3, _f6, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "sf_sparse_index_ws_bytes": (_sz, [_i, _i]),
-    "sf_sparse_out_sites_fwd": (_i, [_vp, _i, _i, _i3, _i3, _i3, _i3, _vp, _i, _vp, _vp, _sz, _vp]),
-    "sf_sparse_table_fwd": (_i, [_vp, _i, _vp, _i, _i, _i3, _i3, _i3, _i3, _i, _vp, _vp, _sz, _vp]),
-    "sf_sparse_conv_fwd": (_i, [C.POINTER(ConvW), _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _sz, _vp]),
-    "sf_sparse_conv_masked_fwd": (_i, [C.POINTER(ConvW), _vp, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _sz, _vp]),
-    "sf_sparse_to_dense_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "sf_warp_affine_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "sf_confusion_fwd": (_i, [_vp, _vp, C.c_long, _i, _vp, _vp, _vp]),
-    "sf_instance_centers_ws_bytes": (_sz, [_i, _i]),
-    "sf_instance_centers_fwd": (_i, [_vp, _i, _i, C.c_float, _vp, _i, _vp, _vp, _sz, _vp]),
-    "sf_group_pixels_fwd": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
-    "sf_instance_moments_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "sf_confusion_frames_fwd": (_i, [_vp, _vp, C.c_long, _i, _i, _vp, _vp, _vp]),
-    "sf_instance_seq_ws_bytes": (_sz, [_i, _i, _i, _i]),
-    "sf_instance_seq_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, C.c_float, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "sf_instance_labels_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "sf_instance_labels_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.c_double, C.c_float, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "sf_instance_track_ws_bytes": (_sz, [_i, _i, _i]),
-    "sf_instance_track_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, C.c_float, _vp, _vp, _vp, _sz, _vp]),
-    "sf_panoptic_score_ws_bytes": (_sz, [_i, _i, _i]),
-    "sf_panoptic_score_fwd": (_i, [_vp, C.c_long, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "sf_plan_cost_ws_bytes": (_sz, []),
-    "sf_plan_cost_fwd": (_i, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, C.POINTER(C.c_float * 7), C.c_float, C.c_float,
-                              _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "sf_plan_select_refine_fwd": (_i, [_vp, _vp, C.c_long, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "sf_plan_metric_fwd": (_i, [_vp, _vp, C.c_long, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-    "sf_fresnel_fwd": (_i, [_vp, C.c_long, _vp, _vp, _vp]),
-    "sf_plan_sample_ws_bytes": (_sz, [_i, _i, _i]),
-    "sf_plan_sample_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_double, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "sf_graph_begin": (_i, [_vp]),
-    "sf_graph_end": (_i, [_vp, C.POINTER(_vp)]),
-    "sf_graph_launch": (_i, [_vp, _vp]),
-    "sf_graph_destroy": (_i, [_vp]),
-    "sf_event_create": (_i, [C.POINTER(_vp)]),
-    "sf_event_record": (_i, [_vp, _vp]),
-    "sf_event_elapsed_ms": (_i, [_vp, _vp, C.POINTER(C.c_float)]),
-    "sf_event_destroy": (_i, [_vp]),
-    "sf_prof_enable": (_i, [_i]),
-    "sf_prof_collect": (_i, [i32p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
-    "sf_debug_stamps": (_i, [_vp]),
-    "sf_pack_conv_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "sf_debug_occupancy": (_i, [_i]),
-    "sf_debug_wino_plan": (_i, [C.POINTER(ConvW), _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int32), _i]),
-    "sf_debug_tiled_plan": (_i, [C.POINTER(ConvW), _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int32), _i]),
-    "sf_bn_fold": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_float, _i, _vp, _vp, _vp]),
-    "sf_pack_conv": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_float, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, C.POINTER(ConvW), _vp]),
-}
+_sz = C.c_size_t
+CTYPES = {"int": C.c_int, "long": C.c_long, "size_t": _sz, "float": C.c_float, "double": C.c_double, "const char*": C.c_char_p}
+
+
+def ctype(t):
+    """The ctypes class of a C type as _header spells it: a pointer to a public struct is typed, any other pointer is c_void_p, which
+    takes what the callers pass (ctypes arrays, byref(), data_as() pointers, data_ptr() integers, None)."""
+    if t in CTYPES:
+        return CTYPES[t]
+    struct = STRUCTS.get(t.replace("const ", "")[:-1])
+    return C.POINTER(struct) if struct else C.c_void_p
+
+
+# name -> (restype, argtypes); every function include/sfnative.h declares
+SIGNATURES = {name: (ctype(ret), [ctype(a) for a in args]) for name, (ret, args) in _PROTOS.items()}
 
 # kernel key = KEY_NAMES key * 8 + epilogue.  Keys 0..15 are the tiled conv kernels: beside each name the rows of the tile table (csrc/sf_launch.h:
 # TILES) that report it — the table's key column is the authority; DESIGN.md 4.2 lists the launches reported under another tile's name

@@ -25,6 +25,63 @@ def test_build_and_symbols():
     assert lib.sf_dual_cell_ws_bytes(64, 1, 50, 50) >= 10 * 64 * 2500 * 4
 
 
+def test_binding_read_from_header_agrees_with_compiler(tmp_path):
+    """gcc, reading include/sfnative.h itself, accepts every prototype as the header reader (_header.py) saw it — a wrong argument count
+    or type fails the compile — and prints the same sizes for the vocabulary's C types and the same values for the SF_* constants as
+    the binding holds."""
+    import subprocess
+    from streamingflow_amd import _header, _lib
+    protos, consts, structs = _header.read()
+    types = sorted(set(_header.SCALARS + _header.RETURNS) | {t + "*" for t in _header.POINTEES + tuple(structs)}
+                   | {t for ret, args in protos.values() for t in [ret] + args})
+    gcc = ["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include")]
+    src = tmp_path / "protos.c"      # compiled only: an initialiser of another function type is an error (not static: nothing uses them)
+    src.write_text('#include "sfnative.h"\n'
+                   + "".join(f"{ret} (*const chk_{name})({', '.join(args) or 'void'}) = {name};\n" for name, (ret, args) in protos.items()))
+    subprocess.run(gcc + ["-c", str(src), "-o", str(tmp_path / "protos.o")], check=True)
+    src = tmp_path / "values.c"
+    src.write_text('#include <stdio.h>\n#include "sfnative.h"\nint main(void) {\n'
+                   + "".join(f'  printf("%zu\\n", sizeof({t}));\n' for t in types)
+                   + "".join(f'  printf("%ld\\n", (long){k});\n' for k in consts)
+                   + "  return 0;\n}\n")
+    exe = tmp_path / "values"
+    subprocess.run(gcc + [str(src), "-o", str(exe)], check=True)
+    out = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
+    assert len(protos) == len(_lib.SIGNATURES)
+    assert out[:len(types)] == [ctypes.sizeof(_lib.ctype(t)) for t in types], types
+    assert out[len(types):] == [getattr(_lib, k) for k in consts] == list(consts.values())
+    assert _lib.SIGNATURES == {name: (_lib.ctype(ret), [_lib.ctype(a) for a in args]) for name, (ret, args) in protos.items()}
+
+
+def test_header_reader_complete_and_strict():
+    import pytest
+    import subprocess
+    from streamingflow_amd import build, _header, _lib
+    path = build.build()
+    header = open(_header.HEADER_PATH, encoding="utf-8").read()
+    protos, consts, structs = _header.parse(header)
+    # completeness: one entry per prototype of the header, and per function the library exports
+    nm = subprocess.run(["nm", "-D", "--defined-only", path], check=True, capture_output=True, text=True).stdout
+    exported = {line.split()[2] for line in nm.splitlines() if line.split()[1] == "T" and line.split()[2].startswith("sf_")}
+    assert set(protos) == set(_lib.SIGNATURES) == exported, set(protos) ^ exported
+    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    assert len(protos) == len(re.findall(r"^(?:int|size_t|const char\*) +sf_\w+\(", code, flags=re.M))
+    assert [_lib.STRUCTS[s] for s in structs] == list(_lib.ABI_STRUCTS)      # the header defines them in SF_STRUCT_* order
+    # the drift this reader ended: the binding had four ints where the header and api.hip have five
+    assert _lib.SIGNATURES["sf_bottleblock_ws_bytes"] == (ctypes.c_size_t, [ctypes.c_int] * 5)
+    assert (_lib.SF_OK, _lib.SF_ERR_INVALID, _lib.SF_ERR_WORKSPACE, _lib.SF_ERR_LAUNCH, _lib.SF_ERR_UNSUPPORTED) == (0, -1, -2, -3, -4)
+    # strictness: anything outside the vocabulary raises and names the function
+    tail = "\n#ifdef __cplusplus\n}"
+    for bad in ("int sf_new_fwd(const float* x, short n, void* stream);", "int sf_new_fwd(float** x);", "float sf_new_fwd(int n);",
+                "int sf_new_fwd(const struct sf_conv_w* w);", "int sf_new_fwd(int (*cb)(int));", "int sf_new_fwd(unsigned n);",
+                "int sf_new_fwd(const int16_t x[4]);", "int sf_new_fwd(int n, ...);"):
+        assert tail in header
+        with pytest.raises(ValueError, match="sf_new_fwd"):
+            _header.parse(header.replace(tail, "\n" + bad + tail))
+    ok, _, _ = _header.parse(header.replace(tail, "\nint sf_new_fwd(const float lo[3], const int32_t dim[],\n  sf_gru_w * w);" + tail))
+    assert ok["sf_new_fwd"] == ("int", ["const float*", "const int32_t*", "sf_gru_w*"]) and len(ok) == len(protos) + 1
+
+
 def test_struct_sizes_match_abi7_header_layout():
     from streamingflow_amd import _lib
     assert _lib.SF_ABI_VERSION == 7      # the layout below is version 7's: a layout change bumps the version and this test with it

@@ -17,10 +17,10 @@ import torch
 import torch.nn.functional as F
 
 from util import hashfill, maxabs
+from streamingflow_amd._lib import SF_ERR_INVALID, SF_ERR_WORKSPACE
 
 pytestmark = pytest.mark.gpu
 
-SF_ERR_INVALID, SF_ERR_WORKSPACE = -1, -2      # include/sfnative.h
 U = 2.0 ** -24                                  # fp32 unit roundoff
 
 

@@ -21,9 +21,9 @@ from util import ROOT, cases, gold
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import gen_instance_labels_golden as GEN  # noqa: E402
+from streamingflow_amd._lib import SF_ERR_INVALID, SF_ERR_WORKSPACE  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-SF_ERR_INVALID, SF_ERR_WORKSPACE = -1, -2      # include/sfnative.h
 CENTER_TOL = 2.0 ** -22
 
 

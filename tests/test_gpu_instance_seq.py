@@ -18,9 +18,9 @@ from util import ROOT, gold
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import gen_instance_seq_golden as GEN  # noqa: E402
+from streamingflow_amd._lib import SF_ERR_INVALID, SF_ERR_WORKSPACE  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-SF_ERR_INVALID, SF_ERR_WORKSPACE = -1, -2      # include/sfnative.h
 THR = 0.1
 
 

@@ -12,9 +12,9 @@ import pytest
 import torch
 
 import track_util as TU
+from streamingflow_amd._lib import SF_OK, SF_ERR_INVALID, SF_ERR_WORKSPACE
 
 pytestmark = pytest.mark.gpu
-SF_OK, SF_ERR_INVALID, SF_ERR_WORKSPACE = 0, -1, -2      # include/sfnative.h
 POISON = -7
 
 

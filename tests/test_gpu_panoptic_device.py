@@ -16,9 +16,9 @@ import torch
 
 import panoptic_util as PU
 from util import cases, gold
+from streamingflow_amd._lib import SF_OK, SF_ERR_INVALID, SF_ERR_WORKSPACE
 
 pytestmark = pytest.mark.gpu
-SF_OK, SF_ERR_INVALID, SF_ERR_WORKSPACE = 0, -1, -2      # include/sfnative.h
 U = 2.0 ** -24
 
 

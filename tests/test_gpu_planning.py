@@ -8,9 +8,9 @@ import pytest
 import torch
 
 import planning_util as PU
+from streamingflow_amd._lib import SF_ERR_INVALID, SF_ERR_WORKSPACE
 
 pytestmark = pytest.mark.gpu
-SF_ERR_INVALID, SF_ERR_WORKSPACE = -1, -2      # include/sfnative.h
 
 
 @pytest.mark.parametrize("tag", PU.TAGS)

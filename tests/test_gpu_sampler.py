@@ -6,9 +6,9 @@ import pytest
 import torch
 
 import sampler_util as SU
+from streamingflow_amd._lib import SF_ERR_INVALID, SF_ERR_WORKSPACE, SF_ERR_UNSUPPORTED
 
 pytestmark = pytest.mark.gpu
-SF_ERR_INVALID, SF_ERR_WORKSPACE, SF_ERR_UNSUPPORTED = -1, -2, -4      # include/sfnative.h
 
 
 def test_fresnel_kernel_matches_scipy():

@@ -12,10 +12,9 @@ import torch
 
 import sparse_conv_util as SC
 from oracle import sparse_encoder_ref as SR
+from streamingflow_amd._lib import SF_ERR_INVALID, SF_ERR_WORKSPACE
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not torch.cuda.is_available(), reason="needs the MI355X")]
-
-SF_ERR_INVALID, SF_ERR_WORKSPACE = -1, -2      # include/sfnative.h
 
 
 def _check_values(case, got, what=""):
