@@ -569,6 +569,21 @@ int sf_sparse_to_dense_fwd(const float* feats, const int32_t* coords, int n, int
  *   + F.grid_sample(mode nearest | bilinear, padding zeros, align_corners=False) on NCHW maps x [B][C][H][W]. */
 int sf_warp_affine_fwd(const float* x, const float* theta, int B, int C, int H, int W, int bilinear, float* out,
                        void* stream);
+/* sf_flow_warp_fwd — warp_with_flow (mmdet3d/models/beverse/models/motion_modules.py:434-449) on NHWC maps: state [P][C], P = B*H*W,
+ *   resampled along a flow PER PIXEL (sf_warp_affine_fwd above resamples by one matrix per image), bilinear, zeros outside,
+ *   align_corners=True.  The flow (x first, then y, in pixels) is either given, flow_in [P][2], or computed here as the 2-channel 1x1
+ *   head of the motion module (offset_pred / flow_pred[1]): f = w_off [2][Cf] . feat [P][Cf] + b_off [2], feat the NHWC output of the
+ *   offset ConvBlock; exactly one of feat / flow_in is non-NULL (w_off, b_off, Cf are read with feat only).  Destination pixel (b, i, j)
+ *   samples image b at (i + fy, j + fx) (what the reference's normalise / un-normalise pair comes to, a few ulp apart): four taps at
+ *   floor and floor + 1, a tap outside [0, W) x [0, H) contributes zero and is never read, so no other image of the batch is.
+ *   The C channels of pixel p go to out[p*out_cs + out_co + c]: a channel slice of a wider tensor (the [P][C+L] input of the GRU cell).
+ *   flow_out [P][2] (may be NULL) receives the flow used.  One launch, no workspace; enqueues only.
+ *   SF_ERR_INVALID, nothing launched: a NULL state / out, both or neither of feat / flow_in, feat without w_off / b_off, B < 1, H < 2 or
+ *   W < 2 (the reference divides by W - 1), C, Cf, out_cs or out_co not a positive multiple of 4 (out_co may be 0), out_co + C > out_cs,
+ *   B*H*W >= 2^31, state / feat / w_off / out not 16-byte or flow_in / flow_out not 8-byte aligned, or the written slice of out
+ *   overlapping state, feat or flow_in (neighbouring pixels are read while others are written: in place is a race). */
+int sf_flow_warp_fwd(const float* state, const float* feat, const float* w_off, const float* b_off, const float* flow_in, float* out,
+                     float* flow_out, int B, int H, int W, int C, int Cf, int out_cs, int out_co, void* stream);
 int sf_confusion_fwd(const int64_t* a, const int64_t* b, long n, int K, int64_t* out, int32_t* bad, void* stream);
 size_t sf_instance_centers_ws_bytes(int H, int W);
 int sf_instance_centers_fwd(const float* center, int H, int W, float conf_threshold, int32_t* centers, int cap,
