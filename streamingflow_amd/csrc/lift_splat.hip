@@ -119,6 +119,9 @@ __global__ void lift_cell_start_kernel(const unsigned* __restrict__ keys, int n,
 // v_readlane and every lane gathers its channel of that point's feature row (one 256-B line per
 // wave).  Adds are sequential in list order: the sum is reproducible and bit-identical to a scalar
 // loop.  MODE 0: v = x[p][c].  MODE 1: v = depth[p] * feat[ray(p)][c], ray(p) = (p / (D*fHW))*fHW + p % fHW.
+// Every product and every sum in here is rounded on its own, as the reference's separate torch ops are (x = prob * feat, the kernel's
+// +=, bev * discount + pooled): the compiler's contraction is off and the operators are written out — __fmul_rn / __fadd_rn are plain
+// * and + in the toolchain's headers, compiled with contraction on, and came out as one v_fmac for the temporal blend.
 #ifndef LIFT_INFLIGHT
 #define LIFT_INFLIGHT 16
 #endif
@@ -127,6 +130,7 @@ __global__ __launch_bounds__(256) void lift_pool_kernel(const int* __restrict__ 
                                                         int C, const float* __restrict__ x, const float* __restrict__ depth,
                                                         const float* __restrict__ feat, int D, int fHW,
                                                         const float* __restrict__ prev, float discount, float* __restrict__ out) {
+#pragma clang fp contract(off)
   const int lane = threadIdx.x & 63;
   const int chunks = (C + 63) >> 6;
   const long wave = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -159,16 +163,16 @@ __global__ __launch_bounds__(256) void lift_pool_kernel(const int* __restrict__ 
         const int r = __builtin_amdgcn_readlane(row, jj);
         const float t = table[(size_t)r * C + cc];
         if (MODE == 0) v[i] = t;
-        else v[i] = __fmul_rn(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(dv), jj)), t);
+        else v[i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(dv), jj)) * t;
         if ((j + i) >= m) v[i] = 0.f;
       }
 #pragma unroll
-      for (int i = 0; i < LIFT_INFLIGHT; ++i) acc = __fadd_rn(acc, v[i]);
+      for (int i = 0; i < LIFT_INFLIGHT; ++i) acc = acc + v[i];
     }
   }
   if (!act) return;
   const size_t o = (size_t)cell * C + c;
-  if (prev) acc = __fadd_rn(__fmul_rn(prev[o], discount), acc);      // streamingflow.py:419
+  if (prev) acc = prev[o] * discount + acc;      // streamingflow.py:419: two roundings
   out[o] = acc;
 }
 

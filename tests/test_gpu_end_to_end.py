@@ -124,8 +124,9 @@ def test_shipped_sizes_chain_vs_oracles_on_a_reduced_cloud():
     """Config 3 after the image backbone at the SHIPPED grid sizes and channel widths, 3 camera + 5 LiDAR frames, 7 targets,
     with a reduced point cloud (3000 points per frame, where the numpy sparse oracle is feasible).  Every stage behind the
     lift-splat quantisation is compared through the chain of oracles; the camera BEV itself is taken from the product
-    (a frustum of 483 840 points per frame always has points within fp32 rounding of a cell boundary — DESIGN 6b; the
-    lift-splat kernels have their own full-size bit-exactness tests in test_gpu_lift.py)."""
+    (a frustum of 483 840 points per frame always has points within fp32 rounding of a cell boundary — DESIGN 6b; the full-size
+    bit-exactness test of test_gpu_lift.py covers the materialised path only — the fused path this model runs, lift_pool_kernel<1> behind
+    the rig quantiser, is held to its oracles at crowded cells and at the cell edges in test_gpu_lift_kernels.py)."""
     from oracle import decoder_ref as DR, ref_torch as R, sparse_encoder_ref as SR, temporal_model_ref as TR, voxelize as VZ
     from streamingflow_amd.models import streamingflow as SFM
     cfg, net, sd = _shipped_model()
