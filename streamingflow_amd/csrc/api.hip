@@ -63,7 +63,7 @@ struct CellBufs {
 // tile before it leaves the workgroup (conv_sp.hip, ConvProblem::fuse_*); ps[0]'s own output is then not stored.  Returns
 // whether the launch of ps carries q.
 bool fuse_following_1x1(ConvProblem* ps, int n, const ConvProblem& q, const sf_conv_w& w1, float* out) {
-  if (!tune().sp_fuse_1x1 || !sp_takes(ps, n, EPI_LNG) || !sp_takes(&q, 1, EPI_LNG)) return false;
+  if (!sp_takes(ps, n, EPI_LNG) || !sp_takes(&q, 1, EPI_LNG)) return false;
   if (w1.kh != 1 || w1.kw != 1 || w1.c1 != 0 || w1.cin_pad > 64 || w1.cout_pad > 64 || ps[0].cout_pad > 64 || !w1.scale || !w1.bias ||
       w1.c0 != ps[0].cout || q.add)
     return false;
@@ -162,7 +162,7 @@ bool carry_ok(const sf_dual_w& w, const sf_pmodel_w& pm, int B, int H, int W) {
   // One latent only.  (Measured with the blend mode / acc_in also in the large-tile AFFINE epilogues: per steady-state step 8 samples
   // 684 -> 669 us, one 200x200 latent 1200 -> 1200, 32 samples 2178 -> 2197 — and the two extra branches cost every AFFINE launch
   // of the batched forward 0.9 % (255.5 -> 257.8 ms): not worth the headline, reverted; profiles/README.md round-3 log.)
-  if (!(tune().pipe && B == 1 && P < tune().sp_max_p && tune().sp && pregate(P, w.cand1) && pregate(P, w.cand2))) return false;
+  if (!(tune().pipe && B == 1 && P < SP_MAX_P && tune().sp && pregate(P, w.cand1) && pregate(P, w.cand2))) return false;
   if (!pm.rb0.proj.w) return false;
   // The launch GROUPS the carried form issues must all be ones the small-P kernel takes (its AFFINE epilogue alone has the blend
   // mode and acc_in; run() refuses them elsewhere and the rollout would fail instead of falling back — ADVICE r3).  The groups above with
@@ -270,7 +270,7 @@ int infer_state(const sf_pmodel_w& w, const float* s, const float* eps, float* p
   ConvProblem c3 = problem(w.rb1.conv1, y1, nullptr, b, B, H, W);
   c3.se_sum = cs1; c3.se_fc0 = w.se0_fc0; c3.se_fc2 = w.se0_fc2; c3.se_out = sc1; c3.se_nt = nt1; c3.se_cr = C2 / 8;
   c3.se_inv_hw = 1.f / (float)HW;
-  const bool fuse_se = tiles && tune().sp_fuse_se && sp_takes(&c3, 1, EPI_AFFINE);
+  const bool fuse_se = tiles && sp_takes(&c3, 1, EPI_AFFINE);
   if (!fuse_se) {
     c3.se_sum = nullptr;
     SF_TRY(gate(y1, cs1, nt1, w.se0_fc0, w.se0_fc2, sc1));
@@ -368,7 +368,7 @@ int res_block(const sf_res_w& w, const float* x, float* out, float* t, float* pr
     // identity skip of an input that is upsampled on read: the Winograd epilogue reads the half-size tensor itself (one source pixel
     // per tile); anywhere else the caller has to materialise the upsampled input (SF_ERR_UNSUPPORTED before anything is launched)
     c2.add_up = 1;
-    if (!(tune().upsample_fused && wino_runs(c2, EPI_AFFINE))) return SF_ERR_UNSUPPORTED;
+    if (!wino_runs(c2, EPI_AFFINE)) return SF_ERR_UNSUPPORTED;
   }
   ConvProblem ps[2];
   ps[0] = problem(w.conv1, x, nullptr, t, n, Hin, Win, in_up);
@@ -378,7 +378,7 @@ int res_block(const sf_res_w& w, const float* x, float* out, float* t, float* pr
   if (pooled) {
     ConvProblem cp = c2;
     cp.pool2 = 1; cp.out = pooled;
-    if (tune().pool_fused && wino_runs(cp, EPI_AFFINE)) return run1(cp, EPI_AFFINE, st);
+    if (wino_runs(cp, EPI_AFFINE)) return run1(cp, EPI_AFFINE, st);
     SF_TRY(run1(c2, EPI_AFFINE, st));
     SF_HIP(launch_maxpool2(out, pooled, n, c2.Hout, c2.Wout, c2.cout, 0, st));
     return SF_OK;
@@ -731,7 +731,7 @@ int run_stages(const std::vector<Stage>& stages, const sf_pmodel_w& pm, const fl
   cb.g2 = A.take(2 * PC); cb.rs2 = A.take(PC); cb.h2 = A.take(PC); cb.g1s = A.take(2 * PC);
   cnow = cb;
   // one latent: the launch groups of the stages become phases of ONE persistent flow launch (conv_sp.hip: sp_flow_kernel)
-  FlowScope flow(rc.allow_flow && B == 1 && (long)B * H * W < tune().sp_max_p && tune().sp, A, st);      // for the duration of this function only
+  FlowScope flow(rc.allow_flow && B == 1 && (long)B * H * W < SP_MAX_P && tune().sp, A, st);      // for the duration of this function only
   if (!A.ok()) return SF_ERR_WORKSPACE;
   SF_TRY(flow.status);
   *flow_err = flow.err();
@@ -1054,9 +1054,9 @@ int sf_convnext_block_fwd(const sf_convnext_w* w, const float* x, float* out, in
   // never written (convnext_mlp.hip).  Exact fp32 only: the bf16x3 mode keeps its own K loop on the two-launch path
   const sf_conv_w &a = w->pw1, &b = w->pw2;
   const bool one_by_one = a.kh == 1 && a.kw == 1 && b.kh == 1 && b.kw == 1 && a.stride == 1 && b.stride == 1 && a.pad == 0 && b.pad == 0;
-  if (tune().mlp_fused && one_by_one && C == 64 && a.c0 == 64 && a.c1 == 0 && a.cin_pad == 64 && a.cout == 256 && a.cout_pad == 256 && a.act == ACT_GELU &&
+  if (one_by_one && C == 64 && a.c0 == 64 && a.c1 == 0 && a.cin_pad == 64 && a.cout == 256 && a.cout_pad == 256 && a.act == ACT_GELU &&
       b.c0 == 256 && b.c1 == 0 && b.cin_pad == 256 && b.cout == 64 && b.cout_pad == 64 && b.act == ACT_NONE && a.w && b.w &&
-      !(tune().b3 && a.w_bf16x3 && b.w_bf16x3)) {
+      !(a.w_bf16x3 && b.w_bf16x3)) {
     SF_TRY(seg_flush());
     auto cost = [&] {      // t and x once, out once, both weight matrices once
       return Cost{20 * 8 + EPI_AFFINE, 2.0 * (double)P * (64.0 * 256.0 + 256.0 * 64.0), 4.0 * ((double)P * 64.0 * 3.0 + 2.0 * 64.0 * 256.0)};

@@ -105,26 +105,7 @@ __device__ __forceinline__ void split_bf16x8(const f32x4 x0, const f32x4 x1, bf1
   lo = __builtin_bit_cast(bf16x8, l);
 }
 
-#ifndef SF_SETPRIO
-#define SF_SETPRIO 1
-#endif
-constexpr bool SETPRIO = SF_SETPRIO;
-// log2 of the XCD tile chunk of the LDS-DMA kernel's large launches (SF_XCD_CHUNK = 32 tiles; 0 switches the order off)
-static int xcd_chunk_log2() {
-  static const int v = [] {
-    const char* e = std::getenv("SF_XCD_CHUNK");
-    int c = e ? std::atoi(e) : 32, l = -1;
-    while (c > 0) { ++l; c >>= 1; }
-    return l;
-  }();
-  return v;
-}
-#ifndef SF_GDIAG
-#define SF_GDIAG 0  // same for the LDS-DMA kernel: 1 = weights only, 2 = pixels only, 3 = every chunk re-reads chunk 0, 4 = no DMA
-#endif
-#ifndef SF_DIAG
-#define SF_DIAG 0   // timing probes of the staged main loop (tools/experiments/diag_loop.sh); 0 = the product
-#endif
+constexpr int XCD_CHUNK_LOG2 = 5;      // log2 of the XCD tile chunk of the LDS-DMA kernel's large launches (32 tiles)
 constexpr int LDS_ROW = 36;   // floats per staged row: 32 K values + 4 pad
 constexpr int BK = 32;
 
@@ -648,7 +629,7 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void conv_igemm_kernel(const Con
         for (int n = 0; n < NT; ++n) fb[nxt][n] = lds_read_b64(b + n * 16 * ROW + koff(t4 + 1));
       }
       __builtin_amdgcn_sched_barrier(0);   // keep the prefetch reads above this group's MFMAs
-      if (SETPRIO) __builtin_amdgcn_s_setprio(1);
+      __builtin_amdgcn_s_setprio(1);
       // all tiles with the even k first, then the odd k: MT*NT independent accumulators between
       // two MFMAs on the same one (16x16x4 f32: 32-cycle issue, 40-cycle dependent latency)
 #pragma unroll
@@ -661,7 +642,7 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void conv_igemm_kernel(const Con
 #pragma unroll
         for (int n = 0; n < NT; ++n)
           acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[cur][m].y, fb[cur][n].y, acc[m][n], 0, 0, 0);
-      if (SETPRIO) __builtin_amdgcn_s_setprio(0);
+      __builtin_amdgcn_s_setprio(0);
       __builtin_amdgcn_sched_barrier(0);
     }
   };
@@ -675,29 +656,11 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void conv_igemm_kernel(const Con
   for (int it = 0; it < niter; ++it) {
     const int nxt = (it + 1) * KS + kg;
     const bool has_next = nxt < nchunks;
-#if SF_DIAG == 0
     if (has_next) load_chunk(cb + nxt);
     if (it * KS + kg < nchunks) compute(it & 1);
     if (has_next) store_chunk((it + 1) & 1);
     __syncthreads();
-#elif SF_DIAG == 1   // MFMA + fragment reads + barrier, no staging (results meaningless: timing probe only)
-    if (it * KS + kg < nchunks) compute(it & 1);
-    __syncthreads();
-#elif SF_DIAG == 2   // MFMA + fragment reads, no barrier
-    if (it * KS + kg < nchunks) compute(it & 1);
-#elif SF_DIAG == 4   // global loads issued, never written to LDS
-    if (has_next) load_chunk(cb + nxt);
-    if (it * KS + kg < nchunks) compute(it & 1);
-    __syncthreads();
-#elif SF_DIAG == 5   // LDS writes of stale registers, no global loads
-    if (it * KS + kg < nchunks) compute(it & 1);
-    if (has_next) store_chunk((it + 1) & 1);
-    __syncthreads();
-#endif
   }
-#if SF_DIAG == 4
-  if (niter < 0) store_chunk(0);   // keeps the staged registers alive
-#endif
 
   // ---- in-workgroup split-K reduction (fixed order) ----------------------------------------
   if constexpr (KS > 1) {
@@ -741,23 +704,14 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void conv_igemm_kernel(const Con
 // channels) or one input of any width, stride, dilation, nearest x2 upsampling on read, the neighbour table of a sparse
 // convolution, cross-workgroup split-K, and (SCALE instantiation) a per-(image, channel) SE scale applied to the pixel
 // fragments after the LDS read.  A reset-gate multiply is not: the GRU gates launch writes (1 - r) * s instead.
-// (tools/experiments/diag_loop.sh: without its staging the register-staged loop runs at 134 instead of 115 TFLOP/s on a
+// (timing probes, profiles/r01_v_diag_*: without its staging the register-staged loop runs at 134 instead of 115 TFLOP/s on a
 // 7-frame 128->128 layer — global loads cost 10 %, the LDS writes 6 %; this kernel reaches 126, 134 at 224 frames.)
-// bf16x3 staging depth.  SF_B3_DEEP=0 (shipped): two buffers and as many workgroups per CU as fit (2 for the 128 x 128 tiles, 3 for
-// 64 x 128).  -DSF_B3_DEEP=1 (experiment): as many 32-deep buffers as ~150 KB of LDS hold, one workgroup per CU, NB - 1 chunks in
-// flight — measured 186.5 ms per batch-32 forward against 137.3: the loop is not short of bytes in flight, it is short of other
-// workgroups to run while one waits at its per-chunk barrier.
-#ifndef SF_B3_DEEP
-#define SF_B3_DEEP 0
-#endif
-template <int MT, int NT, int WM, int WN>
-constexpr int b3_nb() {
-  if (!SF_B3_DEEP || WM * WN < 8) return 2;      // the 4-wave tiles keep two buffers and several workgroups per CU
-  const int per = 16 * (MT * WM + NT * WN) * 128, n = (150 * 1024) / per;
-  return n < 2 ? 2 : (n > 6 ? 6 : n);
-}
+// bf16x3 staging depth: two buffers, like the fp32 loop, and as many workgroups per CU as fit (2 for the 128 x 128 tiles, 3 for
+// 64 x 128).  As many 32-deep buffers as ~150 KB of LDS hold, one workgroup per CU, NB - 1 chunks in flight measured 186.5 ms per
+// batch-32 forward against 137.3: the loop is not short of bytes in flight, it is short of other workgroups to run while one waits at
+// its per-chunk barrier.
 template <int MT, int NT, int WM, int WN, int EPI, int NB, bool SCALE, bool B3 = false>
-__global__ __launch_bounds__(64 * WM * WN, (B3 && !SF_B3_DEEP && WM * WN >= 8 ? 4 : 1)) void conv_glds_kernel(const ConvLaunch L) {
+__global__ __launch_bounds__(64 * WM * WN, (B3 && WM * WN >= 8 ? 4 : 1)) void conv_glds_kernel(const ConvLaunch L) {
   constexpr int NWV = WM * WN;
   constexpr int BM = 16 * MT * WM, BN = 16 * NT * WN;
   constexpr int ROWS = BM + BN;
@@ -905,18 +859,6 @@ __global__ __launch_bounds__(64 * WM * WN, (B3 && !SF_B3_DEEP && WM * WN >= 8 ? 
   typedef __attribute__((address_space(3))) void lds_void;
   // one LDS-DMA of the chunk at the cursor: slot q of G (weights first); the last slot advances the cursor
   auto issue_one = [&](int chunk, int buf, int q) {
-#if SF_GDIAG == 3   // probe: every chunk re-reads the addresses of chunk 0
-    chunk = 0;
-#endif
-#if SF_GDIAG == 4
-    return;
-#endif
-#if SF_GDIAG == 2
-    if (q < GA) return;
-#endif
-#if SF_GDIAG == 1
-    if (q >= GA) return;
-#endif
     if (q < GA) {
       float* dst = smem + buf * BUF + (wave * GA + q) * 8 * 32;
 #if defined(__HIP_DEVICE_COMPILE__)     // the host pass must not see the target builtins (it silently drops the kernel stub)
@@ -958,7 +900,6 @@ __global__ __launch_bounds__(64 * WM * WN, (B3 && !SF_B3_DEEP && WM * WN >= 8 ? 
       (void)dst;
 #endif
     }
-#if SF_GDIAG != 3
     if (q == G - 1) {
       ++cur_kc;
       tap_fresh = false;
@@ -971,7 +912,6 @@ __global__ __launch_bounds__(64 * WM * WN, (B3 && !SF_B3_DEEP && WM * WN >= 8 ? 
         } else if (++cur_tx == KW) { cur_tx = 0; ++cur_ty; }
       }
     }
-#endif
   };
 
   const int sx = (j >> 1) & SWM;
@@ -1075,7 +1015,7 @@ __global__ __launch_bounds__(64 * WM * WN, (B3 && !SF_B3_DEEP && WM * WN >= 8 ? 
       for (int n = 0; n < NT; ++n) { fb[set][n].x *= fs[set][n].x; fb[set][n].y *= fs[set][n].y; }
     }
     __builtin_amdgcn_sched_barrier(0);
-    if (SETPRIO) __builtin_amdgcn_s_setprio(1);
+    __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int m = 0; m < MT; ++m)
 #pragma unroll
@@ -1086,7 +1026,7 @@ __global__ __launch_bounds__(64 * WM * WN, (B3 && !SF_B3_DEEP && WM * WN >= 8 ? 
 #pragma unroll
       for (int n = 0; n < NT; ++n)
         acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[set][m].y, fb[set][n].y, acc[m][n], 0, 0, 0);
-    if (SETPRIO) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
   };
   // prologue: LA = NB-1 chunks in flight, the first one retired and published
@@ -1179,24 +1119,23 @@ __global__ __launch_bounds__(64 * WM * WN, (B3 && !SF_B3_DEEP && WM * WN >= 8 ? 
 }
 
 // dynamic LDS of an LDS-DMA launch: NB staging buffers (+ the SE scale rows of up to 4 images x 256 channels)
-template <int MT, int NT, int WM, int WN, bool B3>
-constexpr int glds_nb() { return B3 ? b3_nb<MT, NT, WM, WN>() : 2; }
+constexpr int GLDS_NB = 2;
 template <int MT, int NT, int WM, int WN, bool SCALE, bool B3>
-constexpr int glds_lds() { return glds_nb<MT, NT, WM, WN, B3>() * 16 * (MT * WM + NT * WN) * 32 * 4 + (SCALE ? 4 * 256 * 4 : 0); }
+constexpr int glds_lds() { return GLDS_NB * 16 * (MT * WM + NT * WN) * 32 * 4 + (SCALE ? 4 * 256 * 4 : 0); }
 template <int MT, int NT, int WM, int WN, int EPI, bool SCALE, bool B3>
 static hipError_t launch_glds_tb(const ConvLaunch& L, hipStream_t stream) {
   constexpr int lds = glds_lds<MT, NT, WM, WN, SCALE, B3>();
-  constexpr auto kern = conv_glds_kernel<MT, NT, WM, WN, EPI, glds_nb<MT, NT, WM, WN, B3>(), SCALE, B3>;
+  constexpr auto kern = conv_glds_kernel<MT, NT, WM, WN, EPI, GLDS_NB, SCALE, B3>;
   const hipError_t e = set_max_dynamic_lds<kern>(lds);
   if (e != hipSuccess) return e;
   TileGrid g = tile_grid(L, 16 * MT * WM, 16 * NT * WN);
   if (g.maxblocks == 0) return hipSuccess;
   ConvLaunch LL = L;
   LL.xcd_shift = 0;
-  if (xcd_chunk_log2() >= 0 && g.maxblocks >= 4096 && g.zs == 1) {      // see the tile order in the kernel
-    const int span = 8 << xcd_chunk_log2();
+  if (g.maxblocks >= 4096 && g.zs == 1) {      // see the tile order in the kernel
+    const int span = 8 << XCD_CHUNK_LOG2;
     g.maxblocks = (g.maxblocks + span - 1) / span * span;
-    LL.xcd_shift = xcd_chunk_log2() + 1;
+    LL.xcd_shift = XCD_CHUNK_LOG2 + 1;
   }
   hipLaunchKernelGGL(kern, dim3(g.maxblocks, L.nprob, g.zs), dim3(64 * WM * WN), lds, stream, LL);
   return hipGetLastError();
@@ -1211,7 +1150,7 @@ template <TileId T, bool B3>
 static int glds_occupancy_of() {
   constexpr TileRow R = TILES[T];
   int n = -1;
-  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv_glds_kernel<R.MT, R.NT, R.WM, R.WN, EPI_AFFINE, glds_nb<R.MT, R.NT, R.WM, R.WN, B3>(), false, B3>,
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv_glds_kernel<R.MT, R.NT, R.WM, R.WN, EPI_AFFINE, GLDS_NB, false, B3>,
                                                                     64 * R.WM * R.WN, glds_lds<R.MT, R.NT, R.WM, R.WN, false, B3>());
   return e == hipSuccess ? n : -1;
 }

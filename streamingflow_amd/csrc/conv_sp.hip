@@ -45,9 +45,6 @@ constexpr int SP_BM = 64;                     // output channels per tile
 // n / d with the host's ceil(2^32 / d) (exact for n x d < 2^32, which the host checks); m == 0: d is 1, or no reciprocal was made
 __device__ __forceinline__ int sp_mdiv(const int n, const unsigned m, const int d) { return m ? (int)__umulhi((unsigned)n, m) : (d == 1 ? n : n / d); }
 
-#if !defined(SF_SP_PIN)
-#define SF_SP_PIN 1
-#endif
 constexpr int SP_NB = 3, SP_LA = SP_NB - 1;   // chunk buffers of the LDS ring / chunks in flight
 constexpr int SP_RED_PITCH = 68;              // reduction buffer [4 quarters][BN px][68] (inside the ring)
 constexpr int SP_SC_IMGS = 4;                 // SE scale rows kept in LDS: images a pixel tile can touch
@@ -63,13 +60,7 @@ struct SpGeo {
   static constexpr int BUFF = 2 * SUBF;       // floats per chunk buffer
   static constexpr int RING = SP_NB * BUFF;   // NT 2: 72 KB, NT 4: 96 KB
   static constexpr int NBI = BN / 32;         // pixel row blocks (8 rows) per loader and sub-chunk
-#if defined(SF_ABL_NO_PIXEL_DMA)      // timing-only ablation (results are garbage): the loaders issue the weight DMAs only — what a pixel operand
-  static constexpr int DPC = 2 * 2;           // that is LDS-resident could save at most (tools/r04/abl_pixel_dma.sh)
-#elif defined(SF_ABL_NO_WEIGHT_DMA)   // timing-only (garbage results): the pixel DMAs only — what weights that never had to be fetched per workgroup (one
-  static constexpr int DPC = 2 * NBI;         // copy per XCD L2, a weight-stationary slice) could save at most (tools/r05/abl_weight_dma.sh)
-#else
   static constexpr int DPC = 2 * (2 + NBI);   // DMA instructions per loader and chunk
-#endif
   static constexpr int NPX = BN / 32;         // epilogue items (pixel, channel quad) per consumer lane
   static_assert(4 * BN * SP_RED_PITCH + 512 <= RING, "reduction buffer + channel-sum scratch live in the ring");
 };
@@ -89,11 +80,6 @@ constexpr bool sp_has_wino() { return NT == 4 && !B3 && !PST; }
 template <int EPI, int NT, bool B3, bool PST>
 constexpr int sp_region() { return sp_has_wino<EPI, NT, B3, PST>() && SPW_REGION > SpGeo<NT>::RING ? SPW_REGION : SpGeo<NT>::RING; }
 
-#if defined(SF_ABL_NO_WEIGHT_DMA)
-#define SP_ABL_NO_W 1
-#else
-#define SP_ABL_NO_W 0
-#endif
 typedef __attribute__((address_space(3))) void sp_lds_void;
 
 
@@ -126,7 +112,7 @@ __device__ __forceinline__ float sp_reduce16(float v) { return spm_row16_sum(v);
 // (MI355X_MICROARCH.md, hand-off forms: every handed-off byte stored sc1, every storing wave drained before the signal).
 template <bool PST>
 __device__ __forceinline__ void sp_gst4(float* base, const size_t off, const float4 v) {      // base: block-uniform tensor pointer, off: this lane's element offset
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(SF_PST_PLAIN)
+#if defined(__HIP_DEVICE_COMPILE__)
   if constexpr (PST) {
     // a store the compiler knows (its hazard recognizer and wait counters see it; an inline-asm global_store_dwordx4 sc1 here
     // gave wrong tiles — tests/test_gpu_persistent.py): a volatile store to the GLOBAL address space is emitted as
@@ -145,7 +131,7 @@ __device__ __forceinline__ void sp_gst4(float* base, const size_t off, const flo
 }
 template <bool PST>
 __device__ __forceinline__ void sp_gst2(float* p, const float2 v) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(SF_PST_PLAIN) && !defined(SF_PST_PLAIN2)
+#if defined(__HIP_DEVICE_COMPILE__)
   if constexpr (PST) {
     typedef float f32x2v __attribute__((ext_vector_type(2)));
     const f32x2v t = {v.x, v.y};
@@ -159,7 +145,7 @@ __device__ __forceinline__ void sp_gst2(float* p, const float2 v) {
 }
 template <bool PST>
 __device__ __forceinline__ void sp_gst1(float* p, const float v) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(SF_PST_PLAIN) && !defined(SF_PST_PLAIN1)
+#if defined(__HIP_DEVICE_COMPILE__)
   if constexpr (PST) asm volatile("global_store_dword %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
   else *p = v;
 #else
@@ -167,15 +153,12 @@ __device__ __forceinline__ void sp_gst1(float* p, const float v) {
 #endif
 }
 
-// Flow mode, build flag SF_FLOW_SC1 (default 1): every load of bytes another workgroup of the same launch may have written — pixel
+// Flow mode: every load of bytes another workgroup of the same launch may have written — pixel
 // DMAs, epilogue operands, SE sums — bypasses this CU's L1 (sc0 sc1 / sc1: served by L2, which the hardware keeps coherent with the
 // write-through stores of the producers), so an item needs NO agent-scope acquire behind its dependency wait (the buffer_inv sc1
 // took 0.8-1.3 us of every item: profiles/r04_c_flow_stamps.txt).  MI355X_MICROARCH.md lists this form for global_/buffer_ loads to
 // registers (hand-off table, row 3); for LDS-DMA it is OBSERVED here — tests/test_gpu_persistent.py compares every rollout bit for
-// bit with the launch-per-layer path, with cache sweeps in between.  SF_FLOW_SC1=0 builds the acquire form (plain loads).
-#ifndef SF_FLOW_SC1
-#define SF_FLOW_SC1 1
-#endif
+// bit with the launch-per-layer path, with cache sweeps in between.
 template <bool VOL>
 __device__ __forceinline__ float4 sp_gld4(const float* p) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -445,7 +428,7 @@ struct SpDep {
 };
 // One wave waits for the counters, lane-parallel: lane 0 the phase-(q-2) total, lane 1 the phase-(q-1) total, lanes 2.. one tile
 // counter each — every counter on a line of its own, read with sc1 (L1-bypassing) loads until all have reached their counts.
-// The caller runs the workgroup barrier (and the acquire, in builds that need one).
+// The caller runs the workgroup barrier.
 __device__ __forceinline__ void sp_dep_wait(const SpDep& d, const int lane) {
   const bool l0 = lane == 0 && d.lag_expect > 0, l1 = lane == 1 && d.full_expect > 0, lt = lane >= 2 && lane - 2 < d.tile_n;
   const bool mine = l0 || l1 || lt;
@@ -470,14 +453,14 @@ __device__ __forceinline__ bool sp_body(const PT& P, const SpStamp L, int bx, in
                                         const SpDep dep = SpDep()) {
   typedef SpGeo<NT> G;
   constexpr int BN = G::BN;
-  constexpr bool VOL = PST && (SF_FLOW_SC1 != 0);      // flow mode: L1-bypassing loads of activations instead of an acquire
+  constexpr bool VOL = PST;                                 // flow mode: L1-bypassing loads of activations instead of an acquire
   constexpr bool WINO = sp_has_wino<EPI, NT, B3, PST>();
   constexpr int PX_AUX = VOL ? 16 : 0;                 // aux bits of the pixel DMAs (16 = sc1)
   // XOR mask of the 16-byte slot swizzle of the ring: 7 for the fp32 fragment reads (slots c + g), 5 for the bf16x3 loop
   // (slots 2g / 2g + 1: conflict-free for the ds_read_b128 lane groups, see conv_igemm.hip)
   constexpr int SWM = B3 ? 5 : 7;
   constexpr int NKR = B3 ? 2 : 4;      // in-workgroup K split: halves (one 32-deep sub-chunk each) or quarters
-#if SF_SP_PIN && defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__)
   // The fields of the problem record that the way to the first DMA reads, requested together and waited for once: left to itself
   // hipcc loads each field where a branch first needs it — some fifteen dependent scalar-load round trips between the entry of the
   // kernel and the first weight DMA, on a workgroup that lives for 15-20 us and has no partner on its CU to hide them (the items of
@@ -516,12 +499,7 @@ __device__ __forceinline__ bool sp_body(const PT& P, const SpStamp L, int bx, in
   const int nch_all = wn ? wgroups * kcpt : (nsub_all + 1) >> 1;
   const int cps = P.sp_cps > 0 ? P.sp_cps : (nch_all + nsplit - 1) / nsplit;     // chunks per K slice (host: every slice non-empty)
   const int cb = bz * cps;
-#if defined(SF_ABL_K49)      // timing-only ablation (results are garbage): the K loop of every 3x3 layer cut to 4/9 of its chunks — what the products
-  const int nchunks_full = (nch_all - cb) < cps ? (nch_all - cb) : cps;      // of a Winograd F(2x2, 3x3) form would cost at most
-  const int nchunks = (!wn && P.KH == 3 && P.KW == 3 && P.dil == 1) ? (nchunks_full * 4 + 8) / 9 : nchunks_full;
-#else
   const int nchunks = (nch_all - cb) < cps ? (nch_all - cb) : cps;
-#endif
 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lane = tid & 63;
@@ -727,9 +705,9 @@ __device__ __forceinline__ bool sp_body(const PT& P, const SpStamp L, int bx, in
 #endif
   // Flow mode: activations (and the epilogue operands, the SE sums) may be outputs of the phase before this one.  Each role first
   // does everything that depends on nothing — the loaders send the weight halves of the first chunks on their way and compute
-  // their pixel addresses, the consumers their fragment addresses — then wave 0 waits for the tile counters (+ the agent-scope
-  // acquire in SF_FLOW_SC1=0 builds: this CU's L1 may hold lines another CU has rewritten) and ONE workgroup barrier releases
-  // every wave's loads of activations.
+  // their pixel addresses, the consumers their fragment addresses — then wave 0 waits for the tile counters (no acquire
+  // behind it: the loads of activations bypass this CU's L1, which may hold lines another CU has rewritten) and ONE workgroup barrier
+  // releases every wave's loads of activations.
   constexpr int W_EARLY = PST ? SP_LA : 0;      // chunks whose weight halves are issued before the wait
   if constexpr (PST) SF_STAMP_AT(L, 7);
   float4 fuse_lw = spm_zero4(), fuse_lb = spm_zero4();
@@ -912,7 +890,6 @@ __device__ __forceinline__ bool sp_body(const PT& P, const SpStamp L, int bx, in
         // operands that depend on the channel only (scale / bias / LayerNorm and logit rows / SE scale of the residual): once per lane, now
         SpOps chan;
         sp_epi_load<EPI, VOL, 1>(P, 0, c_out, c_out < P.cout, HWout, chan, true);
-#if SF_SP_PIN
         {      // the problem-record fields that the operand loads, the hand-off and the epilogue read: requested together now, in the shadow of the
                // patch DMAs (left to itself hipcc loads each where the tail first needs it: a chain of dependent scalar-load round trips
                // between the last MFMA and the first operand load)
@@ -940,7 +917,6 @@ __device__ __forceinline__ bool sp_body(const PT& P, const SpStamp L, int bx, in
           }
 #undef SP_PIN
         }
-#endif
         if constexpr (SCALE) sp_barrier();
         SF_STAMP_AT(L, 1);
         for (int sidx = 0; sidx < nsc; ++sidx) {
@@ -951,21 +927,13 @@ __device__ __forceinline__ bool sp_body(const PT& P, const SpStamp L, int bx, in
 #endif
 #pragma unroll
           for (int pz = 0; pz < 4; ++pz) fb[pz] = sp_lds_read128(vbuf + pz * 512 + slot_h0);
-#if defined(SF_ABL_WSP_NO_A)      // timing-only ablation (garbage results): the loop without its A loads — what their latency costs at most
-          if (sidx < 0) load_a(1);
-#else
           load_a(1);
-#endif
           __builtin_amdgcn_sched_barrier(0);
           mfma_grp(0);
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
           for (int pz = 0; pz < 4; ++pz) fb[pz] = sp_lds_read128(vbuf + pz * 512 + slot_h1);
-#if defined(SF_ABL_WSP_NO_A)
-          if (sidx < 0) load_a(0);
-#else
           if (sidx + 1 < nsc) load_a(0);
-#endif
           __builtin_amdgcn_sched_barrier(0);
           mfma_grp(1);
           __builtin_amdgcn_sched_barrier(0);
@@ -1093,11 +1061,10 @@ __device__ __forceinline__ bool sp_body(const PT& P, const SpStamp L, int bx, in
         float* const blk = smem + buf * G::BUFF + s2 * G::SUBF;
 #if defined(__HIP_DEVICE_COMPILE__)
         if (live) {
-          if (with_w && !SP_ABL_NO_W) {
+          if (with_w) {
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w, (sp_lds_void*)(blk + (8 * lw) * 32), 16, a_voff[0], sc * 128, 0, 0);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w, (sp_lds_void*)(blk + (8 * (lw + 4)) * 32), 16, a_voff[1], sc * 128, 0, 0);
           }
-#if !defined(SF_ABL_NO_PIXEL_DMA)
 #pragma unroll
           for (int i = 0; i < G::NBI; ++i) {
             float* const dB = blk + (SP_BM + 8 * (lw + 4 * i)) * 32;
@@ -1109,17 +1076,14 @@ __device__ __forceinline__ bool sp_body(const PT& P, const SpStamp L, int bx, in
             if (from1) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc1, (sp_lds_void*)dB, 16, vob, 0, 0, PX_AUX);
             else __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc0, (sp_lds_void*)dB, 16, vob, 0, 0, PX_AUX);
           }
-#endif
         } else {      // offset -1 fails the buffer range check: the DMA writes zeros
-          if (with_w && !SP_ABL_NO_W) {
+          if (with_w) {
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w, (sp_lds_void*)(blk + (8 * lw) * 32), 16, minus1, 0, 0, 0);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w, (sp_lds_void*)(blk + (8 * (lw + 4)) * 32), 16, minus1, 0, 0, 0);
           }
-#if !defined(SF_ABL_NO_PIXEL_DMA)
 #pragma unroll
           for (int i = 0; i < G::NBI; ++i)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc0, (sp_lds_void*)(blk + (SP_BM + 8 * (lw + 4 * i)) * 32), 16, minus1, 0, 0, 0);
-#endif
         }
 #else
         (void)blk; (void)koff; (void)from1; (void)live; (void)whole_chunks; (void)minus1;
@@ -1261,10 +1225,6 @@ __device__ __forceinline__ bool sp_body(const PT& P, const SpStamp L, int bx, in
       if (wave == 0) {
         sp_dep_wait(dep, lane);
         SF_STAMP_AT(L, 9);
-        if constexpr (!VOL) {
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
       }
       sp_barrier();
       SF_STAMP_AT(L, 10);
@@ -1526,7 +1486,7 @@ __device__ __forceinline__ void sp_decode(const PT* ps, const IT* wg_base, const
     if (i < nprob && lg >= wg_base[i]) by = i;
   bx = lg - wg_base[by];
   const PT& P = ps[by];
-#if SF_SP_PIN && defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__)
   {      // ... and the fields of the problem this decode reads
     const int d0 = P.n_img, d1 = P.Hout, d2 = P.Wout, d3 = P.cout_pad, d4 = P.sp_bn;
     const unsigned d5 = P.sp_m_tiles, d6 = P.sp_m_npt;
@@ -1557,7 +1517,7 @@ __global__ __launch_bounds__(SP_THREADS) void conv_sp_kernel(const ConvLaunch L)
   int wb_[SF_MAX_GROUP + 1];
 #pragma unroll
   for (int i = 0; i <= SF_MAX_GROUP; ++i) wb_[i] = L.wg_base[i];
-#if SF_SP_PIN && defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__)
   asm volatile("" ::"s"(np_), "s"(xs_), "s"(wb_[0]), "s"(wb_[1]), "s"(wb_[2]), "s"(wb_[3]), "s"(wb_[4]));
 #endif
   int wtot_ = wb_[1];
@@ -1751,9 +1711,8 @@ static hipError_t launch_sp_tb(const ConvLaunch& L, hipStream_t stream) {
   if (g.maxblocks == 0) return hipSuccess;
   if (fused && EPI != EPI_LNG) return hipErrorInvalidValue;
   const int lds = sp_launch_lds<EPI, SCALE, NT, B3>(fused);      // + the fused 1x1 layer's chunk buffer
-  // compact 1-D grid where the host filled wg_base for this tile size
-  const dim3 grid = L.wg_base[L.nprob] > 0 ? dim3(L.wg_base[L.nprob], 1, 1) : dim3(g.maxblocks, L.nprob, g.zs);
-  hipLaunchKernelGGL(kern, grid, dim3(SP_THREADS), lds, stream, L);
+  // compact 1-D grid: the planner filled wg_base for this tile size (dispatch.hip: sp_plan)
+  hipLaunchKernelGGL(kern, dim3(L.wg_base[L.nprob], 1, 1), dim3(SP_THREADS), lds, stream, L);
   return hipGetLastError();
 }
 template <int EPI, bool SCALE, int NT>

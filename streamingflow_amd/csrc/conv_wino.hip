@@ -202,14 +202,6 @@ struct Wino5Geo {
   static_assert((TH_ == 2 ? 3 : 2) * LDS_FLOATS * 4 <= 160 * 1024, "two workgroups per CU (three of the 16-tile form)");
 };
 
-// timing-only ablations (tools/r05/ablate.sh; wrong results by construction): -DSF_W5_ABL=<bits>  1: no input transform in the loop,
-// 2: no patch DMAs in the loop, 4: no A loads in the loop, 8: no barriers in the loop, 16: no MFMAs, 32: minimal epilogue
-#if !defined(SF_W5_ABL)
-#define SF_W5_ABL 0
-#endif
-#if !defined(SF_W5_MAGIC)
-#define SF_W5_MAGIC 1
-#endif
 // GRP = 9 (round 6, EPI_LNG only): a 7x7 / pad-3 layer as nine 3x3 sub-kernels of its 9x9 zero frame (wino_weights_kernel) — tap group (a, b)
 // convolves the input shifted by (3a - 3, 3b - 3), all nine accumulate into the same Winograd-domain sums: the K loop runs over
 // 9 x cin/16 chunks, the patch offsets move when a chunk starts a new group, everything else is the 3x3 kernel
@@ -267,7 +259,6 @@ __device__ __forceinline__ void conv_wino5_body(const ConvLaunch& L) {
   const int lin = lin_, xcd = lin & 7, slot_ = lin >> 3;
   // the block decode divides by four launch constants: the host passes ceil(2^32 / d) (0 for d = 1) and the quotients are one
   // s_mul_hi each instead of a reciprocal sequence through the vector unit (exact: dividend x divisor < 2^32, checked by the host)
-#if SF_W5_MAGIC
   auto mdiv = [](const int nn, const unsigned m) { return m ? (int)__umulhi((unsigned)nn, m) : nn; };
   const unsigned m_ncb = L.wn_m[1], m_nbx = L.wn_m[2], m_nby = L.wn_m[3], m_tpi = L.wn_m[4];
   (void)m_tpi;
@@ -279,14 +270,6 @@ __device__ __forceinline__ void conv_wino5_body(const ConvLaunch& L) {
   const int bi_ = mdiv(b, m_nby);
   const int by = b - bi_ * nby;
   const int img = CAT ? mdiv(bx * TW, m_tpi) : bi_;
-#else
-  const int tb_ = slot_ / ncb;
-  int b = xcd * per_xcd + tb_;
-  if (b >= nblk) return;
-  const int bx = b % nbx; b /= nbx;
-  const int by = b % nby;
-  const int img = CAT ? (bx * TW) / tpi : b / nby;
-#endif
   const int ct0 = CAT ? bx * TW - img * tpi : 0;
   const int cn0 = CAT ? (tpi - ct0 < TW ? tpi - ct0 : TW) : TW;
   const int ty0 = L.wn_ty0 + by * TH, tx0 = CAT ? ct0 : bx * TW;
@@ -641,11 +624,10 @@ __device__ __forceinline__ void conv_wino5_body(const ConvLaunch& L) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const f32x4 cin = (first && e == 0) ? (f32x4){0.f, 0.f, 0.f, 0.f} : acc[p][mb][0];
-        if (SF_W5_ABL & 16) acc[p][mb][0] = (e == 0 && mb == 0) ? cin + A[slot][mb] * Bf : cin;
-        else acc[p][mb][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[slot][mb][e], Bf[e], cin, 0, 0, 0);
+        acc[p][mb][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[slot][mb][e], Bf[e], cin, 0, 0, 0);
       }
       __builtin_amdgcn_sched_barrier(0);
-      if (!(SF_W5_ABL & 4)) A[slot][mb] = load_A6(kc, p + 3, mb);                     // into the registers this half-step has released
+      A[slot][mb] = load_A6(kc, p + 3, mb);                     // into the registers this half-step has released
       __builtin_amdgcn_sched_barrier(0);
     }
   };
@@ -653,7 +635,7 @@ __device__ __forceinline__ void conv_wino5_body(const ConvLaunch& L) {
   // 64 -> 64 and gate layers — profiles/wino_tall_ablations.txt)
   auto chunk6 = [&](const int kc, auto first_c, auto more_c) {
     constexpr bool more = decltype(more_c)::value;
-    if (more && !(SF_W5_ABL & 2)) issue_patch(kc + 1);                              // behind barrier B: every wave is done with transform(kc)
+    if (more) issue_patch(kc + 1);                              // behind barrier B: every wave is done with transform(kc)
     step6(kc, std::integral_constant<int, 0>{}, first_c);
     step6(kc, std::integral_constant<int, 1>{}, first_c);
     step6(kc, std::integral_constant<int, 2>{}, first_c);
@@ -661,15 +643,15 @@ __device__ __forceinline__ void conv_wino5_body(const ConvLaunch& L) {
       wn_wait(6);                                               // younger than the patch: the A loads of steps 0 to 2
       scale_patch(kc + 1);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (!(SF_W5_ABL & 8)) wn_barrier();                                             // M: patch(kc + 1) complete
-      if (!(SF_W5_ABL & 1)) transform(kc + 1);
+      wn_barrier();                                             // M: patch(kc + 1) complete
+      transform(kc + 1);
     }
     step6(kc, std::integral_constant<int, 3>{}, first_c);
     step6(kc, std::integral_constant<int, 4>{}, first_c);
     step6(kc, std::integral_constant<int, 5>{}, first_c);
     if (more) {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (!(SF_W5_ABL & 8)) wn_barrier();                                             // B: V(kc + 1) published, patch buffer free
+      wn_barrier();                                             // B: V(kc + 1) published, patch buffer free
     }
   };
   (void)step6; (void)chunk6;
@@ -691,12 +673,11 @@ __device__ __forceinline__ void conv_wino5_body(const ConvLaunch& L) {
     for (int mb = 0; mb < 2; ++mb) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        if (SF_W5_ABL & 16) acc[yp][mb][0] = (e == 0 && mb == 0) ? acc[yp][mb][0] + A[slot][mb] * Bf : acc[yp][mb][0];
-        else acc[yp][mb][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[slot][mb][e], Bf[e], acc[yp][mb][0], 0, 0, 0);
+        acc[yp][mb][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[slot][mb][e], Bf[e], acc[yp][mb][0], 0, 0, 0);
       }
       __builtin_amdgcn_sched_barrier(0);
 #if defined(__HIP_DEVICE_COMPILE__)
-      if (!(SF_W5_ABL & 4)) A[slot][mb] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_u, u_voff + mb * 1024, so_next, 0));
+      A[slot][mb] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_u, u_voff + mb * 1024, so_next, 0));
 #endif
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -706,14 +687,14 @@ __device__ __forceinline__ void conv_wino5_body(const ConvLaunch& L) {
     if (more) {
       wn_wait(6);                                               // younger than the patch: the A loads of the chunk's first three steps
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (!(SF_W5_ABL & 8)) wn_barrier();                                             // M: patch(kc + 1) complete
-      if (!(SF_W5_ABL & 1)) transform(kc + 1);
+      wn_barrier();                                             // M: patch(kc + 1) complete
+      transform(kc + 1);
     }
   };
   auto end7 = [&](const bool more) {
     if (more) {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (!(SF_W5_ABL & 8)) wn_barrier();                                             // B: V(kc + 1) published, patch buffer free
+      wn_barrier();                                             // B: V(kc + 1) published, patch buffer free
     }
   };
   // chunk c of the triple that starts at chunk kc0: five steps, y-positions O .. O + 4 (O = 1: groups a = 0, O = 0: groups a = 2)
@@ -726,7 +707,7 @@ __device__ __forceinline__ void conv_wino5_body(const ConvLaunch& L) {
       if constexpr (s3 < 15) return u_so(kc0 + s3 / 5, s3 % 5 + O);
       else return u_so(kc0 + 3, s3 - 15 + o_next);
     };
-    if (more && !(SF_W5_ABL & 2)) issue_patch(kc + 1);                              // behind barrier B: every wave is done with transform(kc)
+    if (more) issue_patch(kc + 1);                              // behind barrier B: every wave is done with transform(kc)
     step7(kc, std::integral_constant<int, O>{}, std::integral_constant<int, (c * 5) % 3>{}, so_of(std::integral_constant<int, 0>{}));
     step7(kc, std::integral_constant<int, O + 1>{}, std::integral_constant<int, (c * 5 + 1) % 3>{}, so_of(std::integral_constant<int, 1>{}));
     step7(kc, std::integral_constant<int, O + 2>{}, std::integral_constant<int, (c * 5 + 2) % 3>{}, so_of(std::integral_constant<int, 2>{}));
@@ -743,7 +724,7 @@ __device__ __forceinline__ void conv_wino5_body(const ConvLaunch& L) {
   };
   // a chunk of the groups a = 1: all six y-positions; the chunk behind it (a = 1 or a = 2) starts at y-position 0
   auto chunk6g = [&](const auto kc) {      // (generic: instantiated by the tall tap-group kernel alone)
-    if (!(SF_W5_ABL & 2)) issue_patch(kc + 1);
+    issue_patch(kc + 1);
     step7(kc, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, u_so(kc, 3));
     step7(kc, std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{}, u_so(kc, 4));
     step7(kc, std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{}, u_so(kc, 5));
@@ -769,32 +750,31 @@ __device__ __forceinline__ void conv_wino5_body(const ConvLaunch& L) {
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) {
           const f32x4 cin = (first && e == 0) ? (f32x4){0.f, 0.f, 0.f, 0.f} : acc[p][mb][nb];
-          if (SF_W5_ABL & 16) acc[p][mb][nb] = (e == 0 && nb == 0 && mb == 0) ? cin + A[slot][mb] * Bf[nb] : cin;
-          else acc[p][mb][nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[slot][mb][e], Bf[nb][e], cin, 0, 0, 0);
+          acc[p][mb][nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[slot][mb][e], Bf[nb][e], cin, 0, 0, 0);
         }
       __builtin_amdgcn_sched_barrier(0);
-      if (!(SF_W5_ABL & 4)) A[slot][mb] = load_A(kc * 4 + p + 2, mb);                 // into the registers this half-step has released
+      A[slot][mb] = load_A(kc * 4 + p + 2, mb);                 // into the registers this half-step has released
       __builtin_amdgcn_sched_barrier(0);
     }
   };
   auto chunk = [&](const int kc, auto first_c, auto more_c) {
     constexpr bool more = decltype(more_c)::value;
-    if (MODE_A && more && !(SF_W5_ABL & 2)) issue_patch(kc + 1);                    // behind barrier B: every wave is done with transform(kc)
+    if (MODE_A && more) issue_patch(kc + 1);                    // behind barrier B: every wave is done with transform(kc)
     step(kc, std::integral_constant<int, 0>{}, first_c);
     step(kc, std::integral_constant<int, 1>{}, first_c);
     if (MODE_A && more) {
       wn_wait(4);                                               // younger than the patch: the A loads of steps 0 and 1
       scale_patch(kc + 1);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (!(SF_W5_ABL & 8)) wn_barrier();                                             // M: patch(kc + 1) complete
-      if (!(SF_W5_ABL & 1)) transform(kc + 1);
+      wn_barrier();                                             // M: patch(kc + 1) complete
+      transform(kc + 1);
     }
     step(kc, std::integral_constant<int, 2>{}, first_c);
     step(kc, std::integral_constant<int, 3>{}, first_c);
     if (more) {
       if constexpr (MODE_A) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (!(SF_W5_ABL & 8)) wn_barrier();                                           // B: V(kc + 1) published, patch buffer free
+        wn_barrier();                                           // B: V(kc + 1) published, patch buffer free
       } else {
         wn_wait(4);                                             // patch(kc + 1) is older than this chunk's A loads
         wn_barrier();                                           // E: every wave holds its last fragments of V(kc); patch(kc + 1) complete
@@ -832,17 +812,6 @@ __device__ __forceinline__ void conv_wino5_body(const ConvLaunch& L) {
 
   // ---- output transform, first half in registers: T[ih][b] = (M A)[ih][b] -------------------------------------------------------------------
   //   b = 0: (M0 + M1) + M2      b = 1: M1 - (M2 + M3)        (the orders of conv_wino_kernel)
-  if (SF_W5_ABL & 32) {
-    f32x4 sacc = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int p = 0; p < (TALL ? 6 : 4); ++p)
-#pragma unroll
-      for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-        for (int nb = 0; nb < (TALL ? 1 : NB); ++nb) sacc += acc[p][mb][nb];
-    if (sacc[0] + sacc[1] + sacc[2] + sacc[3] == 1.2345f) PX.out[tid] = sacc[0];
-    return;
-  }
   float* const Tb = Vbuf;                                      // [ih][b][tile][64 cout], 16-byte slot cq of a tile's row at cq ^ (tile & 15)
   wn_barrier();                                                 // every wave is done with V (and nothing is in flight into the patch)
   // 16-tile form (80 registers): what the exchange and the epilogue derive from the thread index is derived HERE — hipcc would compute it in

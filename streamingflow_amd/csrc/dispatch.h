@@ -28,12 +28,14 @@ struct Arena {
 };
 inline size_t al(size_t n) { return (n + 63) & ~size_t(63); }
 
-// Switches, read once per process from the environment (experiments and A/B aids only; defaults are the shipped choice).  geti (atoi) and
+// Switches, read once per process from the environment: the ones a test, bench.py, the package or a tools/*bench.py tool reads or sets, and
+// the printing aids (INTEGRATION.md has the table; tests/test_switches.py pins the set).  Measured thresholds nobody varies are constants
+// next to the planner that uses them (dispatch.hip).  geti (atoi) and
 // getl (atol) in dispatch.hip are the only readers of the conv dispatch; isset: a debugging aid that is on when its variable is set at all.
 // Three switches are LIVE — re-read at every Winograd plan (dispatch.hip: wino_live), because tests/test_gpu_wino_split.py and
 // tests/test_gpu_wino_tall.py flip them inside one process to compare both forms on the same tensors: SF_WINO_SPLIT_WGS (default 512),
 // SF_WINO_CAT_WIDE (default 1) and SF_WINO_TALL (0: F(2x2) everywhere, 1: the tall form wherever the kernel has it, unset: the measured rule); see wino_plan.
-// Two readers remain in kernel files: SF_XCD_CHUNK (conv_igemm.hip) and SF_DWCONV_PK (aux_kernels.hip).
+// One reader remains in a kernel file: SF_DWCONV_PK (aux_kernels.hip).
 int geti(const char* name, int dflt);
 long getl(const char* name, long dflt);
 inline bool isset(const char* name) { return geti(name, INT32_MIN) != INT32_MIN; }
@@ -46,66 +48,40 @@ struct Tune {
   int persist = geti("SF_PERSIST", 0);
   int b3_small_tiles = geti("SF_B3_SMALL_TILES", 0);   // experiment: bf16x3 layers with 128-multiple cout on 64 x 128 tiles (3 workgroups per CU) instead of 128 x 128 (2)
   int wide64 = geti("SF_WIDE64", 0);               // 1: 64-cout layers at >= 131072 pixels on 64 x 256 tiles (TILE_DMA64x256) instead of 64 x 128
-  int seg_maxph = geti("SF_SEG_MAXPH", 1 << 30);   // diagnostic: at most this many phases per persistent flow launch (1: every phase its own launch of the flow kernel)
   int wino = geti("SF_WINO", 1);                   // layers packed with Winograd weights run conv_wino.hip from wino_min_p pixels (0: direct form everywhere)
   int wino_min_p = geti("SF_WINO_MIN_P", 14000);   // measured (profiles/r04_zz_wino_min_p_sweep.txt, r04_zz_step_min_p_batched_latents.txt): 6 or more batched 50x50 latents
                                                    // and one 200x200 latent gain 6-11 % per ODE step, 5 latents / one 100x100 latent lose 4-7 %; 32 latents +1.6 % on the headline
   int wino_sp = geti("SF_WINO_SP", 1);             // one latent (small-P kernel, launch path): its 3x3 layers run in the Winograd form too (conv_sp.hip; 0: direct form — the round-5 step)
-  int wino_sp7 = geti("SF_WINO_SP7", 1);           // ... and the trusting gate's 7x7 as nine Winograd 3x3 sub-kernels (144 instead of 196 products per 2x2 outputs; 0: direct form)
-  int sp_short_tail = geti("SF_SP_SHORT_TAIL", 1); // ... short trailing problems of a group do not count against the 256-workgroup cap (see sp_plan)
-  int wsp_minsub = geti("SF_WSP_MINSUB", 1);       // ... a K slice of such a layer is at least this many 32-channel sub-chunks (measured: 1 -> 148.2 us per step, 2 -> 150.3)
   int flow_timeout = geti("SF_FLOW_TIMEOUT", 1 << 22);   // polls before a dependency wait of the flow kernel gives up (~1 us each: seconds); bring-up runs use a small value
   int fenced = geti("SF_HANDOFF_FENCED", 0);       // 1: split-K hand-offs also run the agent-scope release / acquire fences of round 1 (known-good reference for the fence-free sc1 form; gfx950 only either way)
-  int b3 = geti("SF_BF16X3", 1);                   // layers packed with split-bf16 weights (opt-in at pack time) run the bf16x3 K loop where a kernel has one (0: exact fp32 even then)
   int pipe = geti("SF_PIPE", 2);                   // one latent: branch 2 of the NEXT dual cell (gates2 -> cand2, functions of the state only) rides in the launches of infer_state, its conv_decoder_2 in the candidate launch (0: every cell on its own, 5 launches)
   int sp = geti("SF_SP", 1);                       // small pixel counts: the loader / consumer kernel of conv_sp.hip (0: the round-1 kernels)
-  int sp_xcd = geti("SF_SP_XCD", 1);               // ... bit 0: compact 1-D grid (no idle workgroups: step 198 -> 195 us); bit 1: XCD-contiguous logical ids (measured: fabric traffic 156 -> 144 MB per step but 195 -> 203 us; tile-major 133 MB and 218 us — the round-robin spread of a layer's workgroups over the XCDs is the fast one)
-  int sp_split_wgs = geti("SF_SP_SPLIT_WGS", 240); // ... K ranges are split across about this many workgroups per launch
-  int sp_bn = geti("SF_SP_BN", 0);                 // ... pixels per tile (0: by the amount of work, see sp_bn)
-  int sp_max_p = geti("SF_SP_MAX_P", 4096);        // ... used below this many pixels (one 50x50 latent; measured: from two samples on the round-1 kernels are as fast or faster)
-  int sp_fuse_se = geti("SF_SP_FUSE_SE", 1);       // ... SE gates computed in the consuming layer's prologue (one sample)
-  int sp_wide_work = geti("SF_SP_WIDE_WORK", 1000);// ... 64-pixel tiles + split K from this many (64x64 tile) x (64-deep chunk) units per launch
-  int sp_magic = geti("SF_SP_MAGIC", 1);           // ... its block / pixel decode divides by multiplication with host-made reciprocals (0: divides)
   int direct = geti("SF_DIRECT", 1);               // 0 disables the direct-fragment kernel
-  int mt = geti("SF_DIRECT_MT", 0);                // ... force its tile height
-  int ks = geti("SF_DIRECT_KS", 0);                // ... force its K-group count
-  int chunks_per_wave = std::max(1, geti("SF_DIRECT_CPW", 5));   // ... its target chunks per wave
   int split = geti("SF_SPLIT", 1);                 // cross-workgroup split-K on 64x64 tiles (small P)
-  int split_target = geti("SF_SPLIT_WGS", 1024);   // round 2 (sc1 hand-off): 512 -> 1024, batch-8 step 754 -> 701 us    // aim for this many workgroups per launch
-  int split_min_chunks = geti("SF_SPLIT_MINCH", 2);
-  int mid_tiles = geti("SF_MID_TILES", 1300);      // round 2: 640 -> 1300 (the 200x200 latent splits its 7x7 too: 1364 -> 1311 us)
   int glds = geti("SF_GLDS", 15);                  // LDS-DMA staging for large plain layers: bit 0 = 128-cout tiles, bit 1 = 64-cout tiles, bit 2 = LayerNorm-epilogue tiles, bit 3 = cross-workgroup split-K launches (0: register staging everywhere)
   int small_dma = geti("SF_SMALL_DMA", 1);         // >= 0: plain layers below LARGE_P run on the LDS-DMA kernel (32x32 tiles); bit 0: GRU candidates too (pre-gated state)
   int narrow = geti("SF_NARROW", 9);               // tile for layers with <= 32 output channels (dispatch.hip: narrow_tile — 9: TILE_DMA32x128, 32 cout x 128 px; 4 / 6 / 7 / 10: 64 x 64 / 64 x 128 / 64 x 128 on four waves / 64 x 256; -1: the 64-row tiles as planned)
-  int large_p = geti("SF_LARGE_P", 8192);          // measured: a 4-sample rollout (10000 px) is 18 % faster on the small-P kernels, 8 samples (20000 px) on the large tiles
-  int mid_minch_ln = geti("SF_MID_MINCH_LN", 1);   // LayerNorm-epilogue layers at mid P take the 64x64 tiles from this many K chunks (the 1x1 of the trusting gate: 4-sample step 415 -> 408 us; 8: the round-1 rule, 64x128 tiles for short K)
-  int sp_fuse_1x1 = geti("SF_SP_FUSE_1X1", 1);     // small-P kernel: the trusting gate's 1x1 layer runs inside the 7x7 layer's launch
-  int split_cfg = geti("SF_SPLIT_CFG", 4);         // tile config of the mid-P split-K launches without a LayerNorm epilogue (4 | 1)
-  int split_from = geti("SF_SPLIT_FROM", 100);     // only layers with at least this many K chunks (the 7x7)
   // ---- what wino_plan / wino_runs decide by (conv_wino.hip's wino_takes says what the kernel CAN address)
   int wino_ln7 = geti("SF_WINO_LN7", 1);           // the 7x7 + LayerNorm layer of the batched cells as nine 3x3 tap groups on the Winograd kernel (0: direct form) ...
   int wino_ln7_min_p = geti("SF_WINO_LN7_MIN_P", 65536);   // ... from this many pixels: one cout block and 9 x cin/16 chunks per workgroup, so the launch needs a full round of
                                                    // workgroups (2 x 256 blocks of 32 tiles = 65536 pixels) to pay — 8 latents of 50x50 are 175 workgroups of ~200 us each and
                                                    // LOSE to the direct form (batch-8 step 549 -> 563 us, profiles/r06_ln7_ab.txt)
   int wino_sample = geti("SF_WINO_SAMPLE", 1);     // the sampling layer of the batched infer_state on the Winograd kernel (0: direct form)
-  int wino_cat = geti("SF_WINO_CAT", 1);           // images concatenated along x where blocks of 8 tile columns fit one image badly (0: never) ...
-  int wino_cat_scaled = geti("SF_WINO_CAT_SCALED", 1);   // ... also layers with an SE input / residual scale (round 6: the SE scales of both images of a block; 0: plain form)
   // 16-tile blocks where 32-tile blocks would leave the launch below this many workgroups (two rounds of the chip's 512 slots; 0: never).  The
   // 16-tile form runs THREE workgroups per CU (80 registers, 46 KB of LDS), so a launch of nominally 313 / 626 32-tile workgroups (10 000 tiles / 32; as launched 328 / 656: 25 x 13
   // blocks rounded up to 8) becomes about twice as many of 768 slots.  Measured per threshold (profiles/r06_wino16_ab.txt, single-sample forward): BLEND launches 0.608 -> 0.514 ms, AFFINE 2.880 ->
   // 2.841, forward 7.44 -> 7.27 ms; at two samples per forward 13.18 -> 13.14; above ~1 400 workgroups the 32-tile form wins (every workgroup
   // loads the whole U of its 64 output channels whatever its tile count: 16 tiles double the load instructions per MFMA)
   long wino_small_wgs = getl("SF_WINO_SMALL_WGS", 1000);
-  int wino_group = geti("SF_WINO_GROUP", 1);       // Winograd layers of identical geometry (the two branches of a dual cell) share ONE launch: their tails merge
   bool wino_list = isset("SF_WINO_LIST");          // debugging aid (tools/r05/wino_layers.py): every Winograd launch timed by itself on stderr — SYNCHRONISES the stream
   bool wino_why = isset("SF_WINO_WHY");            // debugging aid: which large 3x3 launches keep the direct form
-  int upsample_fused = geti("SF_UPSAMPLE_FUSED", 1);   // the upsampled identity skip of a residual block is read by the Winograd epilogue (0: the caller materialises it)
-  int pool_fused = geti("SF_POOL_FUSED", 1);       // MaxPool2d(2) behind a residual block runs in the Winograd epilogue (0: a pooling launch)
-  int mlp_fused = geti("SF_MLP_FUSED", 1);         // the ConvNeXt pointwise MLP runs as one launch (convnext_mlp.hip; 0: two)
   bool prof_dump = isset("SF_PROF_DUMP");          // debugging aid: one line per profiled launch on stderr, in launch order
 };
 const Tune& tune();
-#define LARGE_P tune().large_p   // pixels from which the 64x64 / 64x128 tiles are used
+// pixels from which the 64x64 / 64x128 tiles are used.  Measured: a 4-sample rollout (10000 px) is 18 % faster on the small-P kernels, 8 samples (20000 px) on the large tiles
+constexpr int LARGE_P = 8192;
+// the small-P kernel (conv_sp.hip) is used below this many pixels (one 50x50 latent; measured: from two samples on the round-1 kernels are as fast or faster)
+constexpr int SP_MAX_P = 4096;
 
 // Fill a problem from a packed layer + geometry.  Output spatial size follows the conv formula.
 ConvProblem problem(const sf_conv_w& w, const float* in0, const float* in1, float* out, int n_img, int Hin, int Win, int in_up = 0);

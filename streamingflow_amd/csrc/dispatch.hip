@@ -175,7 +175,7 @@ static bool wino_wanted(const ConvProblem& q, int epi) {
 }
 // this problem runs on the Winograd kernel of the large launches (conv_wino.hip)
 bool wino_runs(const ConvProblem& q, int epi) {
-  return tune().wino && (double)pixels(q) >= tune().wino_min_p && wino_wanted(q, epi) && !(tune().b3 && q.w3);
+  return tune().wino && (double)pixels(q) >= tune().wino_min_p && wino_wanted(q, epi) && !q.w3;
 }
 
 // the split-K scratch of the running top-level call (SplitScope)
@@ -191,7 +191,7 @@ bool sp_takes(const ConvProblem* ps, int n, int epi) {
   int scaled = 0, unscalable = 0;
   for (int i = 0; i < n; ++i) {
     const ConvProblem& q = ps[i];
-    if (pixels(q) >= tune().sp_max_p || q.gather || q.gate || q.out_planar || !one_source_per_chunk(q)) return false;
+    if (pixels(q) >= SP_MAX_P || q.gather || q.gate || q.out_planar || !one_source_per_chunk(q)) return false;
     if ((epi == EPI_LNG || epi == EPI_TRUST) && q.cout_pad > 64) return false;
     if (q.in_scale || q.se_sum) {
       ++scaled;
@@ -213,13 +213,13 @@ bool sp_takes(const ConvProblem* ps, int n, int epi) {
 // dependencies are in linear pixels), not the LayerNorm layers (the 7x7 and its fused 1x1)
 static bool sp_wino_ok(const ConvProblem& q, int epi) {
   if (!tune().wino || !tune().wino_sp || g_seg || !q.w_wino) return false;
-  // 3x3, or the trusting gate's 7x7 as nine 3x3 sub-kernels (SF_WINO_SP7=0: the 7x7 keeps the direct form)
-  const bool k3 = q.KH == 3 && q.KW == 3 && q.pad == 1, k7 = q.KH == 7 && q.KW == 7 && q.pad == 3 && tune().wino_sp7 && epi == EPI_LNG;      // (the kernel carries the tap groups in its LayerNorm instantiation only)
+  // 3x3, or the trusting gate's 7x7 as nine 3x3 sub-kernels (144 instead of 196 products per 2x2 outputs)
+  const bool k3 = q.KH == 3 && q.KW == 3 && q.pad == 1, k7 = q.KH == 7 && q.KW == 7 && q.pad == 3 && epi == EPI_LNG;      // (the kernel carries the tap groups in its LayerNorm instantiation only)
   if (!(k3 || k7) || q.stride != 1 || q.dil != 1 || q.in_up || q.gather || q.gate || q.out_planar || q.pool2 || q.add_up) return false;
   if (q.fuse_w && epi != EPI_LNG) return false;
   if (q.n_img != 1 || (q.Hout & 1) || (q.Wout & 1) || q.Hin != q.Hout || q.Win != q.Wout || q.Wout < 4 || q.Hout < 4) return false;
   if ((q.c0 % 32) || (q.c1 % 32) || q.c0 + q.c1 != q.cin_pad || (q.cout_pad % 64)) return false;
-  if (tune().b3 && q.w3) return false;
+  if (q.w3) return false;
   return 4.0 * (k7 ? 9 : 1) * 16 * q.cout_pad * q.cin_pad < 2147483648.0;
 }
 // K units of a problem in the Winograd form: (tap group, 32-channel sub-chunk) pairs
@@ -227,14 +227,14 @@ static int sp_wino_units(const ConvProblem& q) { return (q.KH == 7 ? 9 : 1) * (q
 // pixels per tile of the small-P kernel.  Measured on the conv launches of an Euler step at 50x50 (profiles/r02_*):
 // 64-pixel tiles with the K range split across workgroups win where a launch has a lot of work (both gate / candidate
 // pairs, the 128 -> 128 layers of p_model, the 7x7), 32-pixel tiles without a hand-off elsewhere
+constexpr double SP_WIDE_WORK = 1000;      // 64-pixel tiles + split K from this many (64x64 tile) x (64-deep chunk) units per launch
 static int sp_bn(const ConvProblem* ps, int n, int epi) {
-  if (tune().sp_bn) return tune().sp_bn;
   for (int i = 0; i < n; ++i)
     if (sp_wino_ok(ps[i], epi)) return 64;      // the Winograd form lives on the 64-pixel tiles
   double work = 0;
   for (int i = 0; i < n; ++i)
     work += (double)tiles(ps[i], 64) * chunks64(ps[i]);
-  return work >= tune().sp_wide_work ? 64 : 32;
+  return work >= SP_WIDE_WORK ? 64 : 32;
 }
 // pixels per SE partial-sum row the producing conv's epilogue writes (the SE gate kernel sums ceil(P / this) rows)
 // (the producer's whole launch group decides its tile)
@@ -305,7 +305,7 @@ struct FlowBuilder {
     const bool all3 = launch_runs_bf16x3(L);
     const int cap = sp_flow_capacity(all3);
     if (L.wg_base[L.nprob] < 1 || L.wg_base[L.nprob] > cap || !sp_flow_has(epi, scaled, bn)) return SF_ERR_UNSUPPORTED;
-    if (!phases.empty() && (all3 != b3 || (int)phases.size() >= tune().seg_maxph)) SF_TRY(flush());
+    if (!phases.empty() && all3 != b3) SF_TRY(flush());
     if ((phases.size() + 1) * sizeof(FlowPhase) + (probs.size() + L.nprob) * sizeof(ConvProblem) + 64 > FLOW_TABLE_BYTES ||
         next_done + SP_FLOW_PHASE_DWORDS > FLOW_DONE_COUNTERS) {
       SF_TRY(flush());
@@ -452,7 +452,6 @@ static Cost wino_cost(const ConvProblem* ps, int n, int epi, WinoForm form, doub
 }
 // opt-in math mode: a launch runs the bf16x3 K loop only when every problem of it was packed with split-bf16 weights
 static void select_bf16x3(ConvLaunch& L) {
-  if (!tune().b3) return;
   bool all3 = true;
   for (int i = 0; i < L.nprob; ++i) all3 = all3 && L.p[i].w3 != nullptr;
   for (int i = 0; i < L.nprob; ++i) L.p[i].use_w3 = all3 ? 1 : 0;
@@ -495,11 +494,11 @@ struct WinoPlan {
   long wgs32 = 0;          // workgroups of the whole layer / group on 32-tile blocks: what SF_WINO_SMALL_WGS is compared with
   WinoSeg seg[2];
 };
-// Concatenated images pay where blocks of 8 tile columns fit the image badly and no epilogue operand is per image (SF_WINO_CAT=0: never)
+// Concatenated images pay where blocks of 8 tile columns fit the image badly and no epilogue operand but an SE scale is per image (round 6: the SE scales of both images of a block)
 static WinoForm wino_form(const ConvProblem& q, const WinoLive& live) {
   if (q.dil > 1) return WINO_DIL;
   const int tpi = (q.Wout + 1) / 2;
-  if (!tune().wino_cat || q.in_up || q.n_img < 2 || tpi < WN_TW || q.bias_per_img || ((q.in_scale || q.add_scale) && !tune().wino_cat_scaled)) return WINO_PLAIN;
+  if (q.in_up || q.n_img < 2 || tpi < WN_TW || q.bias_per_img) return WINO_PLAIN;
   const int plain = (tpi + WN_TW - 1) / WN_TW * WN_TW;
   // less than 10 % empty columns: the plain form, whose patch is two columns narrower — except at 128 or more output channels and at
   // least 4 % empty columns (100 tile columns run 104: the 200x200 gates and 128 -> 128 layers), where CAT measured 1.7 - 2.8 % faster and
@@ -681,7 +680,7 @@ static int run_wino(const ConvProblem* ps, int n, int P, int epi, hipStream_t st
     return timed([&] { return wino_issue(L, W, epi, st); }, [&] { return wino_cost(L.p, L.nprob, epi, W.form, wino_tall_frac(W)); }, st);
   };
   // layers of identical geometry (the two branches of a dual cell) share ONE launch: their tails merge
-  if (tune().wino_group && !tune().wino_list && n_wino >= 2) {
+  if (!tune().wino_list && n_wino >= 2) {
     ConvLaunch WG;
     std::memset(&WG, 0, sizeof(WG));
     for (int i = 0; i < n; ++i)
@@ -712,8 +711,9 @@ static int run_wino(const ConvProblem* ps, int n, int P, int epi, hipStream_t st
 
 // Small-P kernel, deciding: tile width (returned), which problems take the Winograd form, K slices with their slabs and tickets from
 // `scratch` (null: no split), the compact grid and the reciprocals — all into L.  K ranges are split across workgroups (sc1 slab hand-off)
-// so that the launch has about sp_split_wgs workgroups of equal length: a 2500-pixel layer has only 40 tiles of 64 pixels per 64 output
+// so that the launch has about SP_SPLIT_WGS workgroups of equal length: a 2500-pixel layer has only 40 tiles of 64 pixels per 64 output
 // channels
+constexpr int SP_SPLIT_WGS = 240, WSP_MINSUB = 1;      // ... and a slice of a Winograd-form layer is at least this many 32-channel sub-chunks (measured: 1 -> 148.2 us per step, 2 -> 150.3)
 static int sp_plan(ConvLaunch& L, int epi, const SplitCtx* scratch) {
   const int n = L.nprob, bn = sp_bn(L.p, n, epi);
   bool wn_of[SF_MAX_GROUP];
@@ -726,13 +726,13 @@ static int sp_plan(ConvLaunch& L, int epi, const SplitCtx* scratch) {
     nch_of[i] = wn_of[i] ? sp_wino_units(L.p[i]) : chunks64(L.p[i]);
     work_total += (double)tiles_of[i] * nch_of[i];
   }
-  const int wg_target = tune().sp_split_wgs, wg_cap = 256;
+  const int wg_target = SP_SPLIT_WGS, wg_cap = 256;
   const double per_wg = work_total / wg_target;      // chunks per workgroup at the target
   int wgs = 0;
   const bool may_split = scratch && tune().split && bn == 64;
   for (int i = 0; i < n; ++i) {
     int ns = (may_split && per_wg > 0) ? (int)(nch_of[i] / per_wg + 0.5) : 1;
-    const int min_per = wn_of[i] ? (tune().wsp_minsub > 0 ? tune().wsp_minsub : 1) : 3;      // at least 3 chunks (direct) / wsp_minsub sub-chunks (Winograd) per slice
+    const int min_per = wn_of[i] ? WSP_MINSUB : 3;      // at least 3 chunks (direct) / WSP_MINSUB sub-chunks (Winograd) per slice
     if (ns > nch_of[i] / min_per) ns = nch_of[i] / min_per;
     if (ns > 8) ns = 8;
     if (ns < 1) ns = 1;
@@ -741,11 +741,10 @@ static int sp_plan(ConvLaunch& L, int epi, const SplitCtx* scratch) {
   }
   // one workgroup owns a whole CU: a launch of more than 256 of them runs a second round for the few that are left
   // (measured: the 7x7 + projection launch at 280 workgroups took 54 us for 26 us of work per workgroup)
-  // ... unless the ones that are left are SHORT and come last (round 6, SF_SP_SHORT_TAIL): problems whose workgroups do less than a third of the
+  // ... unless the ones that are left are SHORT and come last (round 6): problems whose workgroups do less than a third of the
   // longest one's chunks — the trusting gate's 1x1 projection beside its 7x7 — are not counted against the cap when they are the last
   // problems of the group: the dispatcher hands them to the few free CUs while the long ones run
   auto long_wgs = [&]() {
-    if (!tune().sp_short_tail) return wgs;
     double cmax = 0;
     for (int i = 0; i < n; ++i) cmax = std::max(cmax, (double)nch_of[i] / ns_of[i]);
     int cnt = wgs;
@@ -780,17 +779,14 @@ static int sp_plan(ConvLaunch& L, int epi, const SplitCtx* scratch) {
     slab_off += (size_t)tiles_of[i] * ns * per;
     cnt_off += tiles_of[i];
   }
-  // compact 1-D grid: problem i owns logical workgroups [wg_base[i], wg_base[i + 1]); bit 0 of sp_xcd: compact grid,
-  // bit 1: XCD-contiguous logical ids
-  if (tune().sp_xcd & 1) {
-    int base = 0;
-    for (int i = 0; i < n; ++i) {
-      L.wg_base[i] = base;
-      base += tiles_of[i] * (L.p[i].nsplit > 1 ? L.p[i].nsplit : 1);
-    }
-    for (int i = n; i <= SF_MAX_GROUP; ++i) L.wg_base[i] = base;
-    L.xcd_shift = (tune().sp_xcd >> 1) & 1;
+  // compact 1-D grid (no idle workgroups: step 198 -> 195 us): problem i owns logical workgroups [wg_base[i], wg_base[i + 1]), ids in dispatch order (xcd_shift 0:
+  // XCD-contiguous ids measured 156 -> 144 MB of fabric traffic per step but 195 -> 203 us, tile-major 133 MB and 218 us — the round-robin spread over the XCDs is the fast one)
+  int base = 0;
+  for (int i = 0; i < n; ++i) {
+    L.wg_base[i] = base;
+    base += tiles_of[i] * (L.p[i].nsplit > 1 ? L.p[i].nsplit : 1);
   }
+  for (int i = n; i <= SF_MAX_GROUP; ++i) L.wg_base[i] = base;
   for (int i = 0; i < n; ++i) {
     ConvProblem& q = L.p[i];
     const int ns = q.nsplit > 1 ? q.nsplit : 1;
@@ -799,7 +795,7 @@ static int sp_plan(ConvLaunch& L, int epi, const SplitCtx* scratch) {
     // reciprocals of the divisors of the kernel's block decode and pixel decode (conv_sp.hip: sp_mdiv; exact while dividend x
     // divisor < 2^32: a launch has < 2^16 workgroups and < 2^13 pixels)
     const long Pi = pixels(q), n_pt = (Pi + bn - 1) / bn, kcpt = q.cin_pad >> 5;
-    if (!tune().sp_magic || (long)tiles_of[i] * ns * tiles_of[i] >= 0x100000000L || (Pi + 64) * q.Hout * q.Wout >= 0x100000000L) continue;
+    if ((long)tiles_of[i] * ns * tiles_of[i] >= 0x100000000L || (Pi + 64) * q.Hout * q.Wout >= 0x100000000L) continue;
     q.sp_m_tw = magic(q.Wout / 2);
     // d = 1 has no reciprocal (0 = "divide"): dividing by one is what the fallback does
     q.sp_m_tiles = magic(tiles_of[i]); q.sp_m_npt = magic(n_pt); q.sp_m_hw = magic((long)q.Hout * q.Wout); q.sp_m_w = magic(q.Wout);
@@ -828,7 +824,7 @@ static int run_sp(ConvLaunch& L, int epi, hipStream_t st) {
   bool scaled = false;
   for (int i = 0; i < n; ++i) scaled = scaled || (L.p[i].in_scale != nullptr) || (L.p[i].se_sum != nullptr);
   select_bf16x3(L);
-  if (g_seg && !prof_on() && (tune().sp_xcd & 1)) {      // inside a rollout: a phase of the persistent flow (diagnostic stamps: slot = phase index mod 64)
+  if (g_seg && !prof_on()) {      // inside a rollout: a phase of the persistent flow (diagnostic stamps: slot = phase index mod 64)
     const int rc = g_seg->add(L, epi, scaled, bn);
     if (rc == SF_OK) return SF_OK;
     if (rc != SF_ERR_UNSUPPORTED) return rc;
@@ -843,6 +839,7 @@ static int run_sp(ConvLaunch& L, int epi, hipStream_t st) {
 // Tiled / LDS-DMA kernels, deciding: the row of TILES (sf_launch.h) the launch runs on; mt / ks: the direct kernel's run-time tile
 struct TiledPlan { TileId tile = TILE_S16x64K4; int mt = 0, ks = 1; };
 // cross-workgroup split-K on 64x64 tiles: K slices, slabs and tickets into L, or L untouched where the scratch does not hold them
+constexpr int SPLIT_WGS = 1024, SPLIT_MINCH = 2;      // aim for this many workgroups per launch (round 2, sc1 hand-off: 512 -> 1024, batch-8 step 754 -> 701 us), slices of at least this many chunks
 static bool tiled_split(ConvLaunch& L, const SplitCtx& scratch) {
   // workgroup budget shared in proportion to each problem's work (tiles x chunks)
   double work_total = 0;
@@ -853,8 +850,8 @@ static bool tiled_split(ConvLaunch& L, const SplitCtx& scratch) {
   for (int i = 0; i < L.nprob; ++i) {
     ConvProblem& q = L.p[i];
     const int nt = tiles(q, 64), nc = chunks32(q);
-    int ns = (int)(tune().split_target * (double)nc / work_total + 0.5);
-    if (ns > nc / tune().split_min_chunks) ns = nc / tune().split_min_chunks;
+    int ns = (int)(SPLIT_WGS * (double)nc / work_total + 0.5);
+    if (ns > nc / SPLIT_MINCH) ns = nc / SPLIT_MINCH;
     if (ns > 16) ns = 16;
     if (ns < 1) ns = 1;
     const int cps = (nc + ns - 1) / ns;
@@ -925,6 +922,8 @@ static void tiled_glds(const ConvLaunch& L, int epi, TiledPlan& T) {
     if (ok) T.tile = TILE_DMA32x32;
   }
 }
+constexpr int DIRECT_CPW = 5, SPLIT_FROM = 100;      // direct kernel: target K chunks per wave; small P: split-K only for layers with at least this many K chunks (the 7x7)
+constexpr int MID_TILES = 1300;      // mid P: split-K below this many 64x64 tiles.  Round 2: 640 -> 1300 (the 200x200 latent splits its 7x7 too: 1364 -> 1311 us)
 static int tiled_plan(ConvLaunch& L, int P, int epi, const SplitCtx* scratch, TiledPlan& T) {
   const int n = L.nprob;
   T.tile = pick_tile(P, epi);
@@ -960,8 +959,8 @@ static int tiled_plan(ConvLaunch& L, int P, int epi, const SplitCtx* scratch, Ti
       cp_gcd = a;
     }
     if (ln) T.mt = (cp_max == 16 || cp_max == 32 || cp_max == 64) ? cp_max / 16 : 0;
-    else T.mt = tune().mt ? tune().mt : ((cp_gcd % 32 == 0) ? 2 : 1)   /* measured: 32-row tiles (twice the workgroups) beat 64-row ones */;
-    T.ks = tune().ks ? tune().ks : (chunks_max + tune().chunks_per_wave - 1) / tune().chunks_per_wave;
+    else T.mt = (cp_gcd % 32 == 0) ? 2 : 1   /* measured: 32-row tiles (twice the workgroups) beat 64-row ones */;
+    T.ks = (chunks_max + DIRECT_CPW - 1) / DIRECT_CPW;
     T.ks = T.ks < 1 ? 1 : (T.ks > 8 ? 8 : T.ks);
     if (ok && T.mt) T.tile = TILE_DIRECT16;
   }
@@ -969,12 +968,12 @@ static int tiled_plan(ConvLaunch& L, int P, int epi, const SplitCtx* scratch, Ti
   // re-reads than 16-pixel tiles, and enough workgroups for all 256 CUs)
   // measured (profiles/r01_d_sweep_convs.txt): the slab publish + ticket + acquire costs ~8 us, so
   // it only pays for the long-K layers (7x7: 196 chunks, 68 -> 44 us)
-  const bool split_small = (T.tile == TILE_S16x64K4 || T.tile == TILE_DIRECT16) && chunks_max >= tune().split_from;
+  const bool split_small = (T.tile == TILE_S16x64K4 || T.tile == TILE_DIRECT16) && chunks_max >= SPLIT_FROM;
   // a few batched samples (P = 8k..40k pixels): the large-tile kernels would have too few tiles,
-  // each walking the whole K range; split the K range instead (also keeps LayerNorm layers on 64x64)
-  const bool split_mid = (T.tile == TILE_L64x64 || T.tile == TILE_LN64x128) && tiles_total < tune().mid_tiles && chunks_max >= (T.tile == TILE_LN64x128 ? tune().mid_minch_ln : 8);
-  if ((split_small || split_mid) && tune().split && scratch && tiled_split(L, *scratch))
-    T.tile = (split_mid && tune().split_cfg == 1 && (epi == EPI_AFFINE || epi == EPI_BLEND || epi == EPI_SAMPLE)) ? TILE_L64x64 : TILE_SPLIT64x64;
+  // each walking the whole K range; split the K range instead (also keeps LayerNorm layers on 64x64).  LayerNorm-epilogue layers take the
+  // split from one K chunk (the 1x1 of the trusting gate: 4-sample step 415 -> 408 us; round 1 kept short K on 64x128 tiles), the others from 8
+  const bool split_mid = (T.tile == TILE_L64x64 || T.tile == TILE_LN64x128) && tiles_total < MID_TILES && chunks_max >= (T.tile == TILE_LN64x128 ? 1 : 8);
+  if ((split_small || split_mid) && tune().split && scratch && tiled_split(L, *scratch)) T.tile = TILE_SPLIT64x64;
   tiled_glds(L, epi, T);
   return T.tile == TILE_NONE ? SF_ERR_LAUNCH : SF_OK;      // (an SF_NARROW that names no tile: what the launcher's hipErrorInvalidValue became)
 }

@@ -6,8 +6,6 @@ Drop-in for the reference module (same constructor, ``forward`` signature, retur
 arithmetic runs on libsfnative (HIP, gfx950).  Internally everything is NHWC fp32; the NCHW
 reference layout exists only at ``forward``'s boundary.
 """
-import os
-
 import torch
 import torch.nn as nn
 
@@ -16,14 +14,9 @@ from ..layers.convolutions import Block, DeepLabHead
 from ..layers.temporal import SpatialGRU
 from ..layers.temporal_ode_bayes import NNFOwithBayesianJumps
 
-
-# SF_HEAD_PLANAR=0: the head writes [pixel][channel] frames and T strided transposes follow (the form before round 5; A/B aid)
-_HEAD_PLANAR = os.environ.get("SF_HEAD_PLANAR", "1") != "0"
-
-
-# SF_FOLD_DECODER=0: the last SpatialGRU runs its 1x1 conv_decoder on every frame (T launches) instead of handing its hidden states
-# to a DeepLabHead packed with the decoder folded into its input convolutions (A/B aid)
-_FOLD_DECODER = os.environ.get("SF_FOLD_DECODER", "1") != "0"
+# False (tests/test_gpu_ops.py sets it): the last SpatialGRU runs its 1x1 conv_decoder on every frame even where the decoder could be
+# folded into the DeepLabHead's input convolutions — the form every other (GRU, block) pair takes
+_FOLD_DECODER = True
 
 
 class _FoldedTail(runtime.PackedModule):
@@ -93,7 +86,8 @@ class FuturePredictionODE(nn.Module):
             gst = hst = None
             if (_FOLD_DECODER and i == last and isinstance(blk, DeepLabHead) and gru.conv_decoder.bias is None
                     and gru.input_size == blk.in_channels):
-                # the decoder of the last GRU is linear and only the head reads it: composed into the head's input weights
+                # the decoder of the last GRU is linear and only the head reads it: composed into the head's input weights (any other
+                # pair: the GRU runs its 1x1 conv_decoder on every frame)
                 tail = self.__dict__.get("_folded_tail")
                 if tail is None or tail._gru is not gru or tail._head is not blk:
                     tail = self.__dict__["_folded_tail"] = _FoldedTail(gru, blk)
@@ -155,8 +149,7 @@ class FuturePredictionODE(nn.Module):
         """x: [T, B, H, W, C] decoded predictions -> the head's output as [B, T, C, H, W].  whole: the B samples are the whole
         batch in order (the result is written in its final layout directly)."""
         B = x.shape[1]
-        if (whole and _HEAD_PLANAR and isinstance(self.res_blocks[-1], DeepLabHead)
-                and self.res_blocks[-1][4].out_channels == x.shape[-1]):
+        if whole and isinstance(self.res_blocks[-1], DeepLabHead) and self.res_blocks[-1][4].out_channels == x.shape[-1]:
             # the group is the whole batch, in order: the head's classifier writes [B, T, C, H, W] itself
             T, _, H, W, C = x.shape
             res = torch.empty((B, T, C, H, W), dtype=torch.float32, device=x.device)
