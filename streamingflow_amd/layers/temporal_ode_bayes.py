@@ -12,9 +12,6 @@ Differences a caller can observe (all documented in DESIGN.md):
   * ``solver='rk4'`` is accepted in addition to the reference's 'euler' / 'midpoint';
   * inference only (no autograd), batch 1 per call as in the reference.
 """
-import collections
-import ctypes
-
 import numpy as np
 import torch
 import torch.nn as nn
@@ -265,21 +262,26 @@ class NNFOwithBayesianJumps(nn.Module):
         # at most GRAPH_CACHE_MAX captured rollouts are kept, least recently used first out (a stream of variable timestamps produces a
         # new schedule structure per call: each entry pins its own buffers and a rollout workspace); when auto mode sees more than
         # GRAPH_AUTO_MAX_STRUCTURES distinct structures it stops capturing and runs eagerly
-        self._graphs = collections.OrderedDict()
+        self._graphs = runtime.GraphCache()
         self._graph_structures_seen = set()
         self._graph_gens = None
         self.apply(init_weights)
 
     # ---- noise --------------------------------------------------------------------------------
-    def _draw_eps(self, n_draws, B, h, w, device):
-        """[n_draws, B, h, w, C] fp32 on `device`, one row per infer_state call in reference order."""
+    def _draw_eps(self, noise, n_draws, B, h, w, device):
+        """[n_draws, B, h, w, C] fp32 on `device`, one row per infer_state call in reference order, from torch.randn or from the
+        injected source `noise` (this module's or a session's): a callable (shape, dtype, device) -> NCHW eps."""
         C = self.hidden_size
-        if self.noise is None:
+        if noise is None:
             return torch.randn((max(1, n_draws), B, h, w, C), dtype=torch.float32, device=device)
-        rows = [self.noise((B, C, h, w), torch.float32, "cpu") for _ in range(n_draws)]
+        rows = [noise((B, C, h, w), torch.float32, "cpu") for _ in range(n_draws)]
         if not rows:
             return torch.zeros((1, B, h, w, C), dtype=torch.float32, device=device)
-        return torch.stack(rows, 0).permute(0, 1, 3, 4, 2).contiguous().to(device)
+        return torch.stack(rows, 0).permute(0, 1, 3, 4, 2).contiguous().to(device=device, dtype=torch.float32)
+
+    def _in_kernel(self, noise):
+        """Whether an owner whose injected source is `noise` (this module, a session) draws inside the sampling epilogue."""
+        return noise is None and (True if self.in_kernel_noise is None else bool(self.in_kernel_noise))
 
     # ---- reference API on NCHW tensors ------------------------------------------------------------
     def srvp_encode(self, x):
@@ -297,7 +299,7 @@ class NNFOwithBayesianJumps(nn.Module):
         runtime.require_cuda(x)
         sn = runtime.to_nhwc(x)
         B, h, w, C = sn.shape
-        eps = self._draw_eps(1, B, h, w, x.device)
+        eps = self._draw_eps(self.noise, 1, B, h, w, x.device)
         p = torch.empty_like(sn)
         q = torch.empty((B, h, w, 2 * C), dtype=torch.float32, device=x.device)
         L = _lib.lib()
@@ -314,7 +316,7 @@ class NNFOwithBayesianJumps(nn.Module):
         B, h, w, C = sn.shape
         sc = sched.Schedule(dts=[float(delta_t)])
         coef = torch.from_numpy(sc.coef_array()).to(dev)
-        eps = self._draw_eps(sched.DRAWS_PER_STEP[self.solver], B, h, w, dev)
+        eps = self._draw_eps(self.noise, sched.DRAWS_PER_STEP[self.solver], B, h, w, dev)
         s_out, p_out = torch.empty_like(sn), torch.empty_like(pn)
         L = _lib.lib()
         ws = runtime.workspace(L.sf_ode_step_ws_bytes(C, B, h, w), dev)
@@ -327,22 +329,30 @@ class NNFOwithBayesianJumps(nn.Module):
                 torch.tensor([0], device=dev, dtype=torch.float64), torch.tensor([0], device=dev, dtype=torch.float32))
 
     # ---- the rollout ----------------------------------------------------------------------------
-    def _enqueue_rollout(self, s0, per_image, hx_obs, eps, coef, out, final, ws, B, h, w, philox=None):
-        ops = s0.ops_array()
-        sel = np.asarray(s0.sel_nops, dtype=np.int32)
+    def _enqueue(self, sc, hx, eps, philox, coef, per_image, out, final, B, h, w, ws, device, resume=None):
+        """The C call of a whole rollout (`resume` None) or of one segment of a session (`resume` = state_in, p_in, carry_in,
+        draw_base, p_out, carry_out: include/sfnative.h).  The noise is the `philox` record when there is one, else the `eps` rows."""
         L = _lib.lib()
-        if philox is not None:
-            _lib.check(L.sf_nnfo_rollout_philox_fwd(
-                self.gru_c.packed().struct, self.gru_obs.gru_d.packed().struct, self.p_model.packed().struct,
-                _lib.SOLVER[self.solver], int(bool(self.impute)), ops.ctypes.data_as(_lib.i32p), len(s0.ops),
-                ptr(hx_obs), ptr(philox), ptr(coef), int(per_image), sel.ctypes.data_as(_lib.i32p), len(sel), ptr(out),
-                ptr(final), B, h, w, ptr(ws), ws.numel() * 4, runtime.stream_ptr(hx_obs.device)), "nnfo_rollout_philox")
-            return
-        _lib.check(L.sf_nnfo_rollout_fwd(
-            self.gru_c.packed().struct, self.gru_obs.gru_d.packed().struct, self.p_model.packed().struct,
-            _lib.SOLVER[self.solver], int(bool(self.impute)), ops.ctypes.data_as(_lib.i32p), len(s0.ops),
-            ptr(hx_obs), ptr(eps), ptr(coef), int(per_image), sel.ctypes.data_as(_lib.i32p), len(sel), ptr(out),
-            ptr(final), B, h, w, ptr(ws), ws.numel() * 4, runtime.stream_ptr(hx_obs.device)), "nnfo_rollout")
+        if resume is None:
+            fn, block = (L.sf_nnfo_rollout_fwd if philox is None else L.sf_nnfo_rollout_philox_fwd), ()
+        else:
+            fn = L.sf_nnfo_rollout_resume_fwd if philox is None else L.sf_nnfo_rollout_resume_philox_fwd
+            state_in, p_in, carry_in, draw_base, p_out, carry_out = resume
+            block = (ptr(state_in), ptr(p_in), ptr(carry_in), int(draw_base), ptr(p_out), ptr(carry_out))
+        ops = sc.ops_array()
+        sel = np.asarray(sc.sel_nops, dtype=np.int32)
+        _lib.check(fn(self.gru_c.packed().struct, self.gru_obs.gru_d.packed().struct, self.p_model.packed().struct,
+                      _lib.SOLVER[self.solver], int(bool(self.impute)), ops.ctypes.data_as(_lib.i32p), len(sc.ops), ptr(hx),
+                      ptr(eps if philox is None else philox), ptr(coef), int(per_image), sel.ctypes.data_as(_lib.i32p), len(sel),
+                      ptr(out), ptr(final), *block, B, h, w, ptr(ws), ws.numel() * 4, runtime.stream_ptr(device)), fn.__name__[3:-4])
+
+    def _pack_generations(self):
+        """The packed copies a captured graph holds raw pointers into: a graph is stale once any of the three was rebuilt."""
+        return (self.gru_c.pack_generation(), self.p_model.pack_generation(), self.gru_obs.gru_d.pack_generation())
+
+    def _graph_key_tail(self, device, philox):
+        # (a graph keeps the form, launch per layer / persistent flow, it was captured in)
+        return (str(device), self.solver, bool(self.impute), bool(philox), packing._FLOW[0])
 
     GRAPH_CACHE_MAX = 4
     GRAPH_AUTO_MAX_STRUCTURES = 16
@@ -364,7 +374,7 @@ class NNFOwithBayesianJumps(nn.Module):
     def __getstate__(self):
         # captured graphs (hipGraphExec handles + their static buffers) belong to this object alone: a copy starts without them
         d = runtime.strip_runtime_state(self.__dict__)
-        d["_graphs"] = collections.OrderedDict()
+        d["_graphs"] = runtime.GraphCache()
         d["_graph_structures_seen"] = set()
         d["_graph_gens"] = None
         # a copy (copy.deepcopy, an EMA twin, torch.save / load) draws its OWN Philox stream: new instance serial, seed derived again on
@@ -378,12 +388,89 @@ class NNFOwithBayesianJumps(nn.Module):
 
     def drop_graphs(self):
         """Destroy every captured rollout graph of this module and release its static buffers."""
-        L = _lib.lib()
-        for g in self._graphs.values():
-            if g.get("exec") is not None:
-                L.sf_graph_destroy(g["exec"])
-        self._graphs.clear()
+        self._graphs.drop()
         self._graph_structures_seen.clear()
+
+    def _rollout_noise(self, eps, need, B, h, w, device):
+        """(eps, philox) of one rollout: the in-kernel record {seed, call} beside an empty eps, or `need` rows, fed or drawn."""
+        C = self.hidden_size
+        if eps is None and self._in_kernel(self.noise):
+            self._noise_calls += 1
+            philox = torch.tensor([self._philox_seed(), self._noise_calls], dtype=torch.int64, device=device)
+            return torch.empty((0, B, h, w, C), dtype=torch.float32, device=device), philox      # placeholder (shape key of the graph cache)
+        if eps is None:
+            eps = self._draw_eps(self.noise, need, B, h, w, device)
+        elif eps.dim() == 4:
+            eps = eps[:, None]
+        if eps.shape[0] < need or tuple(eps.shape[1:]) != (B, h, w, C):
+            raise ValueError(f"eps must be [{need}, {B}, {h}, {w}, {C}] for solver {self.solver!r}, got {tuple(eps.shape)}")
+        return eps, None
+
+    def _auto_graph(self, structure, pixels):
+        """`use_graph` None: graphs for the launch-bound single-latent kernels, but not from inside somebody else's capture
+        (warm-up, synchronize and a nested capture would break it) and not for an endless variety of schedule structures: the
+        set stops growing at the cap, a stream of ever new timestamp structures then runs eagerly, while structures whose graph
+        is still cached keep replaying it."""
+        if self.use_graph is not None or pixels >= 4096:
+            return False
+        seen = self._graph_structures_seen
+        if len(seen) <= self.GRAPH_AUTO_MAX_STRUCTURES:
+            seen.add(structure)
+        if torch.cuda.is_current_stream_capturing():
+            return False
+        return len(seen) <= self.GRAPH_AUTO_MAX_STRUCTURES or any(k[0] == structure for k in self._graphs)
+
+    def _run_eager(self, s0, per_image, hx_obs, eps, philox, coef):
+        _, B, h, w, C = hx_obs.shape
+        dev = hx_obs.device
+        out = torch.empty((len(s0.sel_nops), B, h, w, C), dtype=torch.float32, device=dev)
+        final = torch.empty((B, h, w, C), dtype=torch.float32, device=dev)
+        ws = runtime.workspace(_lib.lib().sf_nnfo_rollout_ws_bytes(C, B, h, w), dev)
+        self._enqueue(s0, hx_obs, eps, philox, coef, per_image, out, final, B, h, w, ws, dev)
+        return out, final
+
+    def _run_graph(self, s0, per_image, hx_obs, eps, philox, coef):
+        """Replay the rollout from the graph of its (structure, shapes); the first call of one warms up eagerly on the static
+        buffers and captures, then replays like every later one.  Returns the static buffers (valid until the next replay)."""
+        _, B, h, w, C = hx_obs.shape
+        dev = hx_obs.device
+        # when any of the three packs was rebuilt (load_state_dict, .to(), in-place update) every cached graph is stale
+        gens = self._pack_generations()
+        if self._graph_gens != gens:
+            self.drop_graphs()
+            self._graph_gens = gens
+        feeds = {"hx": hx_obs, "eps": eps, "coef": coef, "philox": philox}
+        key = (s0.key(), per_image, tuple(hx_obs.shape), tuple(eps.shape)) + self._graph_key_tail(dev, philox is not None)
+        g = self._graphs.get(key)
+        if g is None:
+            g = {k: v.clone() if v is not None else None for k, v in feeds.items()}
+            g["out"] = torch.empty((len(s0.sel_nops), B, h, w, C), dtype=torch.float32, device=dev)
+            g["final"] = torch.empty((B, h, w, C), dtype=torch.float32, device=dev)
+            g["ws"] = runtime.static_workspace(_lib.lib().sf_nnfo_rollout_ws_bytes(C, B, h, w), dev)
+            self._graphs.capture(key, g, lambda: self._enqueue(s0, g["hx"], g["eps"], g["philox"], g["coef"], per_image, g["out"],
+                                                               g["final"], B, h, w, g["ws"], dev), dev, self.GRAPH_CACHE_MAX)
+        for k, v in feeds.items():
+            if v is not None:
+                g[k].copy_(v)
+        self._graphs.replay(g, dev)
+        return g["out"], g["final"]
+
+    def _flow_checked(self, result, s0, per_image, hx_obs, eps, philox, coef):
+        """Persistent flow kernel: a dependency wait that gave up (device shared with another stream / process) must cost time, not
+        a result — the same rollout again on the launch-per-layer path, in this process, counted.  Whether it gave up is read from
+        THIS rollout's own output (the poison kernel turns every element into NaN), not from sf_flow_errors, whose "most recent
+        rollout of the thread" is the most recent one ENQUEUED, not the graph that was just replayed."""
+        if not (packing.flow_active() and packing.flow_checked()) or torch.cuda.is_current_stream_capturing():
+            return result
+        if not bool(torch.isnan(result[1].reshape(-1)[:1]).item()):
+            return result
+        packing.FLOW_FALLBACKS[0] += 1
+        L = _lib.lib()
+        was = L.sf_set_flow_mode(0)
+        try:
+            return self._run_eager(s0, per_image, hx_obs.contiguous(), eps.contiguous(), philox, coef)
+        finally:
+            L.sf_set_flow_mode(int(bool(was)) if packing._FLOW[0] is not None else -1)
 
     def rollout_nhwc(self, hx_obs, sc, eps=None):
         """hx_obs: [n_obs, B, h, w, C] (or [n_obs, h, w, C] for one sample) encoded observations in
@@ -403,108 +490,20 @@ class NNFOwithBayesianJumps(nn.Module):
         if len(scs) not in (1, B) or any(x.key() != s0.key() for x in scs):
             raise ValueError("batched rollout needs one schedule, or one per sample with identical structure")
         per_image = len(scs) > 1 and any(x.dts != s0.dts for x in scs)
+        auto_graph = self._auto_graph(s0.key(), B * h * w)
         # draws the kernels will read: one per jump, DRAWS_PER_STEP[solver] per step (a schedule built for another solver
         # would make them read past the end of eps)
-        need = s0.n_jumps + sched.DRAWS_PER_STEP[self.solver] * s0.n_steps
-        philox = None
-        in_kernel = self.noise is None if self.in_kernel_noise is None else bool(self.in_kernel_noise)
-        auto_graph = self.use_graph is None and B * h * w < 4096
-        if auto_graph:
-            # not from inside somebody else's capture (warm-up, synchronize and a nested capture would break it), and not for an
-            # endless variety of schedule structures
-            # (the set stops growing at the cap: a stream of ever new timestamp structures then runs eagerly, while structures whose graph is
-            # still cached keep replaying it)
-            if len(self._graph_structures_seen) <= self.GRAPH_AUTO_MAX_STRUCTURES:
-                self._graph_structures_seen.add(s0.key())
-            cached = any(k[0] == s0.key() for k in self._graphs)
-            if torch.cuda.is_current_stream_capturing() or (len(self._graph_structures_seen) > self.GRAPH_AUTO_MAX_STRUCTURES and not cached):
-                auto_graph = False
-        if eps is None and in_kernel and self.noise is None:
-            self._noise_calls += 1
-            philox = torch.tensor([self._philox_seed(), self._noise_calls], dtype=torch.int64, device=dev)
-            eps = torch.empty((0, B, h, w, C), dtype=torch.float32, device=dev)      # placeholder (shape key of the graph cache)
-        elif eps is None:
-            eps = self._draw_eps(need, B, h, w, dev)
-        elif eps.dim() == 4:
-            eps = eps[:, None]
-        if philox is None and (eps.shape[0] < need or tuple(eps.shape[1:]) != (B, h, w, C)):
-            raise ValueError(f"eps must be [{need}, {B}, {h}, {w}, {C}] for solver {self.solver!r}, got {tuple(eps.shape)}")
+        eps, philox = self._rollout_noise(eps, s0.n_jumps + sched.DRAWS_PER_STEP[self.solver] * s0.n_steps, B, h, w, dev)
         coef_np = np.stack([x.coef_array() for x in scs], axis=1) if per_image else s0.coef_array()
         coef = torch.from_numpy(np.ascontiguousarray(coef_np)).to(dev)
-        L = _lib.lib()
-        nbytes = L.sf_nnfo_rollout_ws_bytes(C, B, h, w)
-        if not (self.use_graph or auto_graph):
-            out = torch.empty((len(s0.sel_nops), B, h, w, C), dtype=torch.float32, device=dev)
-            final = torch.empty((B, h, w, C), dtype=torch.float32, device=dev)
-            ws = runtime.workspace(nbytes, dev)
-            self._enqueue_rollout(s0, per_image, hx_obs, eps, coef, out, final, ws, B, h, w, philox)
-        else:
-            # a captured graph holds raw pointers into the packed weights: when any of the three packs was rebuilt
-            # (load_state_dict, .to(), in-place update) every cached graph is stale — destroy them and their buffers
-            gens = (self.gru_c.pack_generation(), self.p_model.pack_generation(), self.gru_obs.gru_d.pack_generation())
-            if self._graph_gens != gens:
-                self.drop_graphs()
-                self._graph_gens = gens
-            from .. import packing
-            key = (s0.key(), per_image, tuple(hx_obs.shape), tuple(eps.shape), str(dev), self.solver, bool(self.impute), philox is not None,
-                   packing._FLOW[0])      # a graph keeps the form (launch per layer / persistent flow) it was captured in
-            g = self._graphs.get(key)
-            if g is None:
-                g = {"hx": torch.empty_like(hx_obs), "eps": torch.empty_like(eps), "coef": torch.empty_like(coef),
-                     "out": torch.empty((len(s0.sel_nops), B, h, w, C), dtype=torch.float32, device=dev),
-                     "final": torch.empty((B, h, w, C), dtype=torch.float32, device=dev),
-                     "ws": torch.empty(nbytes // 4 + 1024, dtype=torch.float32, device=dev),
-                     "philox": torch.empty_like(philox) if philox is not None else None}
-                g["hx"].copy_(hx_obs); g["eps"].copy_(eps); g["coef"].copy_(coef)
-                if philox is not None:
-                    g["philox"].copy_(philox)
-                # eager warm-up (sets kernel attributes, packs weights), then capture on a side stream
-                self._enqueue_rollout(s0, per_image, g["hx"], g["eps"], g["coef"], g["out"], g["final"], g["ws"], B, h, w, g["philox"])
-                torch.cuda.synchronize(dev)
-                side = torch.cuda.Stream(device=dev)
-                with torch.cuda.stream(side):
-                    sp = runtime.stream_ptr(dev)
-                    _lib.check(L.sf_graph_begin(sp), "graph_begin")
-                    try:
-                        self._enqueue_rollout(s0, per_image, g["hx"], g["eps"], g["coef"], g["out"], g["final"], g["ws"], B, h, w, g["philox"])
-                    finally:
-                        ex = ctypes.c_void_p()
-                        _lib.check(L.sf_graph_end(sp, ctypes.byref(ex)), "graph_end")
-                g["exec"] = ex
-                self._graphs[key] = g
-                while len(self._graphs) > self.GRAPH_CACHE_MAX:      # least recently used out: its graph is destroyed, its buffers released
-                    _, old_g = self._graphs.popitem(last=False)
-                    if old_g.get("exec") is not None:
-                        L.sf_graph_destroy(old_g["exec"])
-            else:
-                self._graphs.move_to_end(key)
-            g["hx"].copy_(hx_obs); g["eps"].copy_(eps); g["coef"].copy_(coef)
-            if philox is not None:
-                g["philox"].copy_(philox)
-            _lib.check(L.sf_graph_launch(g["exec"], runtime.stream_ptr(dev)), "graph_launch")
-            out, final = g["out"], g["final"]      # valid until the next replay of this graph
+        args = (s0, per_image, hx_obs, eps, philox, coef)
+        if self.use_graph or auto_graph:
+            out, final = self._run_graph(*args)
             if auto_graph:                          # nobody asked for the zero-copy form: hand out fresh tensors
                 out, final = out.clone(), final.clone()
-        from .. import packing as _pk
-        if _pk.flow_active() and _pk.flow_checked() and not torch.cuda.is_current_stream_capturing():
-            # persistent flow kernel: a dependency wait that gave up (device shared with another stream / process) must cost time, not a
-            # result — the same rollout again on the launch-per-layer path, in this process, counted
-            # (read from THIS rollout's own output — the poison kernel turns every element into NaN — not from sf_flow_errors, whose
-            # "most recent rollout of the thread" is the most recent one ENQUEUED, not the graph that was just replayed)
-            if bool(torch.isnan(final.reshape(-1)[:1]).item()):
-                _pk.FLOW_FALLBACKS[0] += 1
-                was = L.sf_set_flow_mode(0)
-                try:
-                    if philox is None:
-                        eps_c, hx_c = eps.contiguous(), hx_obs.contiguous()
-                    else:
-                        eps_c, hx_c = eps, hx_obs.contiguous()
-                    out = torch.empty((len(s0.sel_nops), B, h, w, C), dtype=torch.float32, device=dev)
-                    final = torch.empty((B, h, w, C), dtype=torch.float32, device=dev)
-                    ws2 = runtime.workspace(nbytes, dev)
-                    self._enqueue_rollout(s0, per_image, hx_c, eps_c, coef, out, final, ws2, B, h, w, philox)
-                finally:
-                    L.sf_set_flow_mode(int(bool(was)) if _pk._FLOW[0] is not None else -1)
+        else:
+            out, final = self._run_eager(*args)
+        out, final = self._flow_checked((out, final), *args)
         return (out[:, 0], final[0]) if one else (out, final)
 
     def stream(self, delta_t, history=16, **kw):

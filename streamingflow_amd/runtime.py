@@ -1,5 +1,6 @@
 """Device plumbing shared by the modules: current HIP stream handle, a grow-only workspace per
 device, NCHW<->NHWC conversion through the library, cached packed weights."""
+import collections
 import ctypes
 
 import torch
@@ -28,6 +29,10 @@ def workspace(nbytes, device):
     if cur is None or cur.numel() < need:
         _WORKSPACES[key] = cur = torch.empty(need, dtype=torch.float32, device=torch.device("cuda", dev))
     return cur
+
+
+def static_workspace(nbytes, device):      # of a captured graph, which keeps the pointer (`workspace` may move when it grows)
+    return torch.empty(int(nbytes) // 4 + 1024, dtype=torch.float32, device=device)
 
 
 def ptr(t):
@@ -119,3 +124,43 @@ class PackedModule(torch.nn.Module):
 
     def __getstate__(self):
         return strip_runtime_state(self.__dict__)
+
+
+class GraphCache(collections.OrderedDict):
+    """Captured hipGraphs of one owner, least recently used first: key -> entry, a dict of the static buffers the graph reads and
+    writes plus ``"exec"``, its hipGraphExec handle.  The owner decides the keys, the limit and when the entries are stale.  No
+    finalizer: handles are destroyed by eviction and by ``drop()`` only."""
+
+    def capture(self, key, entry, enqueue, device, limit):
+        """Run ``enqueue()`` eagerly (the real run; it also sets kernel attributes and packs weights), record the same calls on a
+        side stream into a graph, and insert the entry.  Nothing is replayed."""
+        L = _lib.lib()
+        enqueue()
+        torch.cuda.synchronize(device)
+        with torch.cuda.stream(torch.cuda.Stream(device=device)):
+            sp = stream_ptr(device)
+            _lib.check(L.sf_graph_begin(sp), "graph_begin")
+            try:
+                enqueue()
+            finally:
+                ex = ctypes.c_void_p()
+                _lib.check(L.sf_graph_end(sp, ctypes.byref(ex)), "graph_end")
+        entry["exec"] = ex
+        self.insert(key, entry, limit)
+
+    def insert(self, key, entry, limit):
+        entry["key"] = key
+        self[key] = entry
+        self.drop(limit)
+
+    def replay(self, entry, device):
+        """Launch the entry's graph on the current stream; the entry becomes the most recently used."""
+        self.move_to_end(entry["key"])
+        _lib.check(_lib.lib().sf_graph_launch(entry["exec"], stream_ptr(device)), "graph_launch")
+
+    def drop(self, keep=0):
+        """All entries but the ``keep`` most recently used leave: their graphs are destroyed, their buffers released."""
+        while len(self) > keep:
+            entry = self.popitem(last=False)[1]
+            if entry.get("exec") is not None:
+                _lib.lib().sf_graph_destroy(entry["exec"])

@@ -11,13 +11,10 @@ reproduces the one-shot call on the same observations (bitwise at the latent lev
 ``FutureStreamSession``  model level (``FuturePredictionODE.stream``): BEV frames in, ``forward(...)[0]``-shaped predictions out.
 """
 import collections
-import ctypes
 
-import numpy as np
 import torch
 
-from . import _lib, packing, runtime, schedule as sched
-from .runtime import ptr
+from . import _lib, runtime, schedule as sched
 
 _MODULE_NOISE = object()
 
@@ -59,7 +56,7 @@ class StreamSession:
         self.noise = ode.noise if noise is _MODULE_NOISE else noise
         self.use_graph = use_graph
         self._sched = sched.StreamSchedule(delta_t, ode.use_variable_ode_step, ode.solver, history)
-        self._graphs = collections.OrderedDict()
+        self._graphs = runtime.GraphCache()
         self._bufs = None            # (state, p, carry): the trunk's static device buffers, updated in place
         self._hist = collections.deque()
         self._gens = None
@@ -96,11 +93,7 @@ class StreamSession:
         raise TypeError("a StreamSession holds device buffers and captured graphs of this process: open a new one instead of copying")
 
     def drop_graphs(self):
-        L = _lib.lib()
-        for g in self._graphs.values():
-            if g.get("exec") is not None:
-                L.sf_graph_destroy(g["exec"])
-        self._graphs.clear()
+        self._graphs.drop()
 
     def reset(self):
         """State and imputed input to zeros, draw counter to 0, path emptied, new noise epoch."""
@@ -118,14 +111,10 @@ class StreamSession:
         if self._bufs is not None:
             for t in self._bufs:
                 t.zero_()
-        gens = self._generations() if self._gens is not None else None
+        gens = self.ode._pack_generations() if self._gens is not None else None
         if gens != self._gens:
             self.drop_graphs()
             self._gens = None
-
-    def _generations(self):
-        o = self.ode
-        return (o.gru_c.pack_generation(), o.p_model.pack_generation(), o.gru_obs.gru_d.pack_generation())
 
     def _check(self, *tensors):
         if self.ode.training:
@@ -135,7 +124,7 @@ class StreamSession:
                                "state may be partly written — call reset() and feed the stream again")
         runtime.require_cuda(*tensors)
         runtime.require_no_grad(*tensors)
-        gens = self._generations()
+        gens = self.ode._pack_generations()
         if self._gens is None:
             self.drop_graphs()
             self._gens = gens
@@ -144,17 +133,9 @@ class StreamSession:
                                "state was computed: call reset() and feed the stream again")
 
     def _in_kernel(self):
-        o = self.ode
-        return self.noise is None and (True if o.in_kernel_noise is None else bool(o.in_kernel_noise))
+        return self.ode._in_kernel(self.noise)
 
     # ---- noise ------------------------------------------------------------------------------------
-    def _row(self, shape, dev):
-        h, w, C = shape
-        if self.noise is None:
-            return torch.randn((1, h, w, C), dtype=torch.float32, device=dev)
-        e = self.noise((1, C, h, w), torch.float32, "cpu")
-        return e.permute(0, 2, 3, 1).contiguous().to(device=dev, dtype=torch.float32)
-
     def _eps(self, base, n, shape, dev, fresh=False):
         """[max(n, 1), 1, h, w, C]: the draws numbered base .. base + n - 1 (cached: a branch and the trunk segment after it read
         the same rows)."""
@@ -165,49 +146,42 @@ class StreamSession:
                 raise ValueError("fresh_noise with an injected noise source: the source defines the draws (inject another one)")
             return torch.randn((n, 1) + tuple(shape), dtype=torch.float32, device=dev)
         while self._pulled < base + n:
-            self._rows[self._pulled] = self._row(shape, dev)
+            self._rows[self._pulled] = (torch.randn((1,) + tuple(shape), dtype=torch.float32, device=dev) if self.noise is None
+                                        else self.ode._draw_eps(self.noise, 1, 1, *shape[:2], dev)[0])
             self._pulled += 1
         return torch.stack([self._rows[k] for k in range(base, base + n)], 0)
 
     # ---- one segment ------------------------------------------------------------------------------
     def _enqueue(self, seg, trunk, hx, eps, philox, coef, out, ws, base, shape):
+        """One segment from the carried (state, p, carry): the trunk writes all three back in place, a branch only reads them."""
         h, w, C = shape
-        o, L = self.ode, _lib.lib()
         state, p, carry = self._bufs
-        ops = seg.ops_array()
-        sel = np.asarray(seg.sel_nops, dtype=np.int32)
-        head = (o.gru_c.packed().struct, o.gru_obs.gru_d.packed().struct, o.p_model.packed().struct, _lib.SOLVER[o.solver],
-                int(bool(o.impute)), ops.ctypes.data_as(_lib.i32p), len(seg.ops), ptr(hx))
-        tail = (ptr(coef), 0, sel.ctypes.data_as(_lib.i32p) if len(sel) else None, len(sel), ptr(out),
-                ptr(state) if trunk else None, ptr(state), ptr(p), ptr(carry), int(base),
-                ptr(p) if trunk else None, ptr(carry) if trunk else None, 1, h, w, ptr(ws), ws.numel() * 4, runtime.stream_ptr(state.device))
-        if philox is not None:
-            _lib.check(L.sf_nnfo_rollout_resume_philox_fwd(*head, ptr(philox), *tail), "nnfo_rollout_resume_philox")
-        else:
-            _lib.check(L.sf_nnfo_rollout_resume_fwd(*head, ptr(eps), *tail), "nnfo_rollout_resume")
+        state_out, p_out, carry_out = (state, p, carry) if trunk else (None, None, None)
+        self.ode._enqueue(seg, hx, eps, philox, coef, 0, out, state_out, 1, h, w, ws, state.device,
+                          resume=(state, p, carry, base, p_out, carry_out))
+
+    def _segment_noise(self, seg, base, shape, dev, fresh):
+        """(eps, philox) of one segment: the {seed, call} record of this epoch (of its own for a fresh branch), or the fed rows."""
+        if not self._in_kernel():
+            return self._eps(base, seg.n_draws, shape, dev, fresh), None
+        o = self.ode
+        call = self._call
+        if call is None or fresh:
+            call = o._noise_calls = o._noise_calls + 1
+            if not fresh:
+                self._call = call
+        return None, torch.tensor([o._philox_seed(), call], dtype=torch.int64, device=dev)
 
     def _run(self, seg, trunk, hx, base, shape, dev, fresh=False):
         """Enqueue one segment from the carried (state, p, carry).  trunk: they are updated in place and nothing is returned;
         branch: they are only read and the selected states [n_sel, 1, h, w, C] are returned (None when the branch selects none)."""
         h, w, C = shape
-        o, L = self.ode, _lib.lib()
         n_sel = len(seg.sel_nops)
         if not seg.ops:
             return None
-        philox = eps = None
-        if self._in_kernel():
-            if self._call is None or fresh:
-                o._noise_calls += 1
-                call = o._noise_calls
-                if not fresh:
-                    self._call = call
-            else:
-                call = self._call
-            philox = torch.tensor([o._philox_seed(), call], dtype=torch.int64, device=dev)
-        else:
-            eps = self._eps(base, seg.n_draws, shape, dev, fresh)
+        eps, philox = self._segment_noise(seg, base, shape, dev, fresh)
         coef = torch.from_numpy(seg.coef_array()).to(dev)
-        nbytes = L.sf_nnfo_rollout_ws_bytes(C, 1, h, w)
+        nbytes = _lib.lib().sf_nnfo_rollout_ws_bytes(C, 1, h, w)
         graph = self.use_graph
         if graph is None:
             graph = h * w < 4096 and philox is None and not torch.cuda.is_current_stream_capturing()
@@ -216,44 +190,22 @@ class StreamSession:
             self._enqueue(seg, trunk, hx, eps, philox, coef, out, runtime.workspace(nbytes, dev), base, shape)
             return out
         # (the key says whether p_out is produced — trunk — and, for the Philox form, which draw numbers the kernels were captured with)
-        key = (bool(trunk), seg.key(), int(base) if philox is not None else None, shape, str(dev), o.solver, bool(o.impute),
-               philox is not None, packing._FLOW[0])
+        key = (bool(trunk), seg.key(), int(base) if philox is not None else None, shape) + self.ode._graph_key_tail(dev, philox is not None)
+        feeds = {"hx": hx.reshape(1, 1, h, w, C) if trunk else None, "eps": eps, "philox": philox, "coef": coef}
         g = self._graphs.get(key)
         if g is not None:
-            self._graphs.move_to_end(key)
-            g["coef"].copy_(coef)
-            if trunk:
-                g["hx"].copy_(hx.reshape(g["hx"].shape))
-            if eps is not None:
-                g["eps"].copy_(eps)
-            else:
-                g["philox"].copy_(philox)
-            _lib.check(L.sf_graph_launch(g["exec"], runtime.stream_ptr(dev)), "graph_launch")
+            for k, v in feeds.items():
+                if v is not None:
+                    g[k].copy_(v)
+            self._graphs.replay(g, dev)
         else:
-            g = {"hx": hx.reshape(1, 1, h, w, C).clone() if trunk else None, "coef": coef.clone(),
-                 "eps": eps.clone() if eps is not None else None, "philox": philox.clone() if philox is not None else None,
-                 "out": torch.empty((n_sel, 1, h, w, C), dtype=torch.float32, device=dev) if n_sel else None,
-                 "ws": torch.empty(nbytes // 4 + 1024, dtype=torch.float32, device=dev)}
-            args = (seg, trunk, g["hx"], g["eps"], g["philox"], g["coef"], g["out"], g["ws"], base, shape)
-            # The first run of a structure is the real one, eager (it also sets kernel attributes); the capture that follows records
-            # the same calls without running them — a trunk segment updates the carried state in place and must run exactly once.
-            self._enqueue(*args)
-            torch.cuda.synchronize(dev)
-            side = torch.cuda.Stream(device=dev)
-            with torch.cuda.stream(side):
-                sp = runtime.stream_ptr(dev)
-                _lib.check(L.sf_graph_begin(sp), "graph_begin")
-                try:
-                    self._enqueue(*args)
-                finally:
-                    ex = ctypes.c_void_p()
-                    _lib.check(L.sf_graph_end(sp, ctypes.byref(ex)), "graph_end")
-            g["exec"] = ex
-            self._graphs[key] = g
-            while len(self._graphs) > self.GRAPH_CACHE_MAX:
-                _, old = self._graphs.popitem(last=False)
-                if old.get("exec") is not None:
-                    L.sf_graph_destroy(old["exec"])
+            g = {k: v.clone() if v is not None else None for k, v in feeds.items()}
+            g["out"] = torch.empty((n_sel, 1, h, w, C), dtype=torch.float32, device=dev) if n_sel else None
+            g["ws"] = runtime.static_workspace(nbytes, dev)
+            # The first run of a structure is the real one, eager; the capture that follows only records the same calls — a trunk
+            # segment updates the carried state in place and must run exactly once, so nothing is replayed here.
+            self._graphs.capture(key, g, lambda: self._enqueue(seg, trunk, g["hx"], g["eps"], g["philox"], g["coef"], g["out"], g["ws"],
+                                                               base, shape), dev, self.GRAPH_CACHE_MAX)
         return g["out"]      # the graph's static buffer (valid until its next replay): predict() copies the rows it returns out of it
 
     # ---- public -----------------------------------------------------------------------------------
