@@ -12,6 +12,7 @@ Only outputs (data) are stored; weights / inputs / eps are regenerated from thei
   big_stats.json  G7: statistics of the C=64, 200x200 forward (tensors are 72 MB)
   voxelize.npz    N2: mmdet3d Voxelization (hard voxelisation) outputs from the reference's C++ CPU kernel
   voxelize_live.npz  N2: the raw hard / dynamic calls of that kernel on 4000 random points (with the points)
+  voxelize_edges.npz N2: the same calls on the edge clouds of tests/voxel_util.py the kernel can run (--only voxel_edges)
   unused_cells.npz a16: Dual_GRU / BiGRU (layers/temporal.py:59-249) and the dual cells with several present frames
   lift_splat.npz  N1: streamingflow.bev_pool / projection_to_birds_eye_view / get_geometry /
                   create_frustum / pose_vec2mat / mmdet3d bev_pool (+ QuickCumsum) outputs
@@ -408,6 +409,39 @@ def gen_voxel_live():
     np.savez_compressed(os.path.join(OUT, "voxelize_live.npz"), **out)
 
 
+def run_voxel_reference(ext, points, vs, rng, mp, mv):
+    """the raw hard and dynamic calls of the compiled reference kernel on one cloud (numpy [n, F]) ->
+    (voxels [m, mp, F], coors [m, 3], num [m], per-point coors [n, 3])"""
+    pts = torch.from_numpy(np.ascontiguousarray(points, dtype=np.float32))
+    voxels = pts.new_zeros((mv, mp, pts.shape[1]))
+    coors = pts.new_zeros((mv, 3), dtype=torch.int)
+    num = pts.new_zeros((mv,), dtype=torch.int)
+    m = ext.hard_voxelize(pts, voxels, coors, num, list(vs), list(rng), mp, mv, 3, True)
+    dyn = pts.new_zeros((pts.shape[0], 3), dtype=torch.int)
+    ext.dynamic_voxelize(pts, dyn, list(vs), list(rng), 3)
+    return _np(voxels[:m]), coors[:m].numpy().astype(np.int32), num[:m].numpy().astype(np.int32), dyn.numpy().astype(np.int32)
+
+
+def gen_voxel_edges():
+    """the compiled reference kernel on the edge clouds of tests/voxel_util.py that it can run (REFERENCE_IDS: cubic grids, finite
+    coordinates) — half-way grid ratios, a power-of-two and a one-cell grid, descending arrival order at six caps, a 3000-point cell,
+    an empty result.  Results only: the clouds are regenerated from their names (tests/test_voxel_oracle.py)."""
+    from . import build_ref
+    sys.path.insert(0, os.path.dirname(OUT))
+    import voxel_util as VU
+    ext = build_ref.load_voxel_layer()
+    assert ext is not None, "oracle/_ref/voxel_layer is not built (python -m oracle.build_ref)"
+    out = {}
+    for cid in VU.REFERENCE_IDS:
+        pts, vs, rng, mp, mv = VU.case(cid)
+        key = cid.replace(":", "_")
+        out["voxels_" + key], out["coors_" + key], out["num_" + key], out["dyn_coors_" + key] = run_voxel_reference(ext, pts, vs, rng, mp, mv)
+        print("voxel_edges", cid, "V =", VU.occupied(pts, vs, rng), "caps", (mp, mv), "->", out["num_" + key].shape[0], "voxels,",
+              int(out["num_" + key].sum()), "points kept of", pts.shape[0])
+    np.savez_compressed(os.path.join(OUT, "voxelize_edges.npz"), **out)
+    print("voxelize_edges.npz", os.path.getsize(os.path.join(OUT, "voxelize_edges.npz")), "bytes")
+
+
 def gen_decoder():
     """N3 (Decoder): the reference's Decoder class on the oracle's restatement of torchvision's resnet18 trunk."""
     from . import decoder_ref as DR
@@ -560,6 +594,8 @@ def main():
         gen_voxel()
     if "voxel_live" in todo:
         gen_voxel_live()
+    if "voxel_edges" in todo:
+        gen_voxel_edges()
     if "decoder" in todo:
         gen_decoder()
     if "temporal" in todo:
@@ -568,7 +604,7 @@ def main():
         gen_eval()
     if "labels" in todo:
         gen_labels()
-    if not set(todo) - {"lift", "voxel", "voxel_live", "decoder", "temporal", "eval", "labels"} and not a.big:
+    if not set(todo) - {"lift", "voxel", "voxel_live", "voxel_edges", "decoder", "temporal", "eval", "labels"} and not a.big:
         return
     m = refimport.modules()
     if "ops" in todo:

@@ -18,10 +18,13 @@ import torch
 
 
 def grid_size(voxel_size, coors_range):
-    """voxelization_cuda.cu:283-285: round((max - min) / size) per axis, fp32."""
+    """voxelization_cuda.cu:256-258, :403-405 and voxelization_cpu.cpp:123, :159: C round() — half AWAY from zero — of the fp32
+    quotient (max - min) / size per axis.  np.round is half to even (2.5 -> 2 where the reference forms 3 cells), so the quotient is
+    rounded as sign(q) * floor(|q| + 0.5) in float64: q has at most 24 significant bits, so |q| + 0.5 is exact below 2^52."""
     vs = np.asarray(voxel_size, dtype=np.float32)
     cr = np.asarray(coors_range, dtype=np.float32)
-    return [int(np.round((cr[3 + i] - cr[i]) / vs[i])) for i in range(3)]
+    q = [np.float64((cr[3 + i] - cr[i]) / vs[i]) for i in range(3)]
+    return [int(np.copysign(np.floor(abs(v) + 0.5), v)) for v in q]
 
 
 def point_coors(points, voxel_size, coors_range):

@@ -52,7 +52,8 @@ __global__ void vox_key_kernel(const float* __restrict__ points, int n, int F, V
     ok = ok && (f >= 0.f) && (f < (float)G.g[a]);
     c[a] = ok ? (int)f : 0;
   }
-  key[i] = ok ? (unsigned)((c[2] * G.g[1] + c[1]) * G.g[0] + c[0]) : sentinel;
+  // unsigned arithmetic: the upper half of a grid of more than 2^31 cells has keys that do not fit an int
+  key[i] = ok ? ((unsigned)c[2] * (unsigned)G.g[1] + (unsigned)c[1]) * (unsigned)G.g[0] + (unsigned)c[0] : sentinel;
   val[i] = (unsigned)i;
 }
 
@@ -164,9 +165,9 @@ size_t sf_hard_voxelize_ws_bytes(int num_points) {
 
 int sf_dynamic_voxelize_fwd(const float* points, int num_points, int num_features, const float* voxel_size, const float* coors_range,
                             int32_t* coors, void* stream) {
-  if (!voxel_size || !coors_range || !coors || num_points < 0 || num_features < 3) return SF_ERR_INVALID;
-  if (num_points == 0) return SF_OK;
-  if (!points) return SF_ERR_INVALID;
+  if (!voxel_size || !coors_range || num_points < 0 || num_features < 3) return SF_ERR_INVALID;
+  if (num_points == 0) return SF_OK;                 // an empty cloud has an empty [0][3] output: its pointer may be NULL
+  if (!points || !coors) return SF_ERR_INVALID;
   VoxGrid G;
   for (int a = 0; a < 3; ++a) {
     G.vs[a] = voxel_size[a];
@@ -193,12 +194,23 @@ int sf_hard_voxelize_fwd(const float* points, int num_points, int num_features, 
     G.vs[a] = voxel_size[a];
     G.lo[a] = coors_range[a];
     if (!(voxel_size[a] > 0.f)) return SF_ERR_INVALID;
-    G.g[a] = (int)roundf((coors_range[3 + a] - coors_range[a]) / voxel_size[a]);       // voxelization_cuda.cu:283-285
+    G.g[a] = (int)roundf((coors_range[3 + a] - coors_range[a]) / voxel_size[a]);       // voxelization_cuda.cu:256-258
     if (G.g[a] < 1) return SF_ERR_INVALID;
     cells *= G.g[a];
   }
   if (cells >= 4294967295.0) return SF_ERR_UNSUPPORTED;
   const unsigned sentinel = (unsigned)cells;
+  // every refusal comes before the first write: a refused call leaves the outputs as they were
+  const int n = num_points;
+  const int bits = bits_for(sentinel);
+  const size_t a = a256((size_t)n * 4);
+  size_t tb_sort = 0, tb_scan = 0;
+  if (n > 0) {
+    if (!points) return SF_ERR_INVALID;
+    tb_sort = vox_sort_tmp(n, bits, st);
+    tb_scan = vox_scan_tmp(n, st);
+    if (!ws || ws_bytes < 6 * a + a256(tb_sort) + a256(tb_scan)) return SF_ERR_WORKSPACE;
+  }
   // the reference hands back zero-initialised outputs (voxelize.py:52-54)
   if (voxels && hipMemsetAsync(voxels, 0, (size_t)max_voxels * max_points * num_features * sizeof(float), st) != hipSuccess)
     return SF_ERR_LAUNCH;
@@ -210,12 +222,6 @@ int sf_hard_voxelize_fwd(const float* points, int num_points, int num_features, 
     if (voxel_num && hipMemsetAsync(voxel_num, 0, sizeof(int), st) != hipSuccess) return SF_ERR_LAUNCH;
     return SF_OK;
   }
-  if (!points) return SF_ERR_INVALID;
-  const int n = num_points;
-  const int bits = bits_for(sentinel);
-  const size_t a = a256((size_t)n * 4);
-  const size_t tb_sort = vox_sort_tmp(n, bits, st), tb_scan = vox_scan_tmp(n, st);
-  if (!ws || ws_bytes < 6 * a + a256(tb_sort) + a256(tb_scan)) return SF_ERR_WORKSPACE;
   char* p = static_cast<char*>(ws);
   unsigned* key = reinterpret_cast<unsigned*>(p);
   unsigned* val = reinterpret_cast<unsigned*>(p + a);
