@@ -1094,10 +1094,34 @@ static int deeplab_head(const sf_deeplab_w* w, const float* x, float* out, int n
     ps[i] = problem(w->branch[i], x, nullptr, cat, n, H, W);
     ps[i].out_cs = 4 * hid; ps[i].out_co = i * hid;
   }
-  SF_TRY(run(ps, 4, EPI_AFFINE, st));
   ConvProblem pj = problem(w->project, cat, nullptr, y, n, H, W);
   pj.bias = bimg; pj.bias_per_img = 1;
-  SF_TRY(run1(pj, EPI_AFFINE, st));
+  // The 1x1 branch's slice of `cat` is read by the projection alone: where the projection runs on the 128 x 128 LDS-DMA tile in exact fp32
+  // with one cout tile, its workgroups compute that slice for their own pixels (conv_igemm.hip: the producer form) and neither the branch's
+  // launch nor the slice's trip through memory happens (slice 0 of `cat` stays unwritten and unread).  Same chunk and k order in both GEMMs:
+  // bitwise the two launches' result.  SF_GLDS bit 4 (live) = 0 restores the two launches; bit 5 is a test's: the branch and the projection on
+  // that tile at any pixel count, so that both forms meet on a few tiles
+  const int live = glds_live();
+  const sf_conv_w& b0 = w->branch[0];
+  const bool forced = (live & 32) && hid % 128 == 0 && b0.kh == 1 && b0.kw == 1 && b0.stride == 1 && b0.pad == 0;
+  const bool on_tile = forced || plans_dma128(pj, EPI_AFFINE);
+  const bool fused = (live & 16) && on_tile && hid == 128 && pj.cout_pad == 128 && pj.c0 == 4 * hid && pj.cin_pad == 4 * hid && !pj.w3 && pj.w &&
+                     C % 32 == 0 && b0.c0 == C && b0.c1 == 0 && b0.cin_pad == C && b0.cout == hid && b0.cout_pad == hid && b0.kh == 1 && b0.kw == 1 &&
+                     b0.stride == 1 && b0.pad == 0 && b0.act == ACT_RELU && b0.w && b0.scale && b0.bias && !b0.w_bf16x3;
+  if (fused) {
+    SF_TRY(run(ps + 1, 3, EPI_AFFINE, st));
+    pj.e0 = x; pj.e0_cs = C;
+    pj.fuse_w = b0.w; pj.fuse_scale = b0.scale; pj.fuse_bias = b0.bias;
+    pj.fuse_cout = hid; pj.fuse_cout_pad = b0.cout_pad; pj.fuse_kpad = b0.cin_pad;
+    SF_TRY(run_dma128(pj, true, st));
+  } else if (forced) {
+    SF_TRY(run_dma128(ps[0], false, st));
+    SF_TRY(run(ps + 1, 3, EPI_AFFINE, st));
+    SF_TRY(run_dma128(pj, false, st));
+  } else {
+    SF_TRY(run(ps, 4, EPI_AFFINE, st));
+    SF_TRY(run1(pj, EPI_AFFINE, st));
+  }
   SF_TRY(run1(problem(w->conv3, y, nullptr, z, n, H, W), EPI_AFFINE, st));
   ConvProblem pc = problem(w->cls, z, nullptr, out, n, H, W);
   if (planar_group > 0) { pc.out_planar = 1; pc.pl_div = planar_group; pc.pl_sa = stride_major; pc.pl_sb = stride_minor; }

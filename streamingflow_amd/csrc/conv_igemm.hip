@@ -710,8 +710,20 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void conv_igemm_kernel(const Con
 // 64 x 128).  As many 32-deep buffers as ~150 KB of LDS hold, one workgroup per CU, NB - 1 chunks in flight measured 186.5 ms per
 // batch-32 forward against 137.3: the loop is not short of bytes in flight, it is short of other workgroups to run while one waits at
 // its per-chunk barrier.
-template <int MT, int NT, int WM, int WN, int EPI, int NB, bool SCALE, bool B3 = false>
-__global__ __launch_bounds__(64 * WM * WN, (B3 && WM * WN >= 8 ? 4 : 1)) void conv_glds_kernel(const ConvLaunch L) {
+//
+// PROD, the producer form (the ASPP head, api.hip: deeplab_head): the first fuse_cout input channels of this layer are not in memory.  They are
+// relu(fuse_scale * (fuse_w . x) + fuse_bias), a 1x1 layer over x = e0 ([pixel][e0_cs], fuse_kpad channels), and the workgroup computes them
+// for its own pixels first: the same K loop over the chunks of x and fuse_w, staged through the same ring, into the same accumulators — the
+// launch that layer would have been, chunk for chunk and k for k.  Its affine + ReLU epilogue leaves the tile in registers (a wave: 64 of
+// the 128 produced channels x its 32 pixels).  The pixel half of the layer's first fuse_cout / 32 = 4 K chunks is then written from those
+// registers, in the slot order a DMA would have produced (a lane holds four consecutive channels of a pixel: one 16-byte slot), where the
+// plain form starts DMAs; the weight half and every later chunk go as ever.  One cout tile (cout_pad == 128), fuse_cout == 128, no split-K.
+// It is the instantiation with GLDS_PRODUCER set in NBF (a flag beside the buffer count: the names of the plain instantiations stay what they were).
+constexpr int GLDS_PRODUCER = 16;
+template <int MT, int NT, int WM, int WN, int EPI, int NBF, bool SCALE, bool B3 = false>
+__global__ __launch_bounds__(64 * WM * WN, ((B3 && WM * WN >= 8) || (NBF & GLDS_PRODUCER) ? 4 : 1)) void conv_glds_kernel(const ConvLaunch L) {
+  constexpr int NB = NBF & (GLDS_PRODUCER - 1);      // staging buffers
+  constexpr bool PROD = (NBF & GLDS_PRODUCER) != 0;
   constexpr int NWV = WM * WN;
   constexpr int BM = 16 * MT * WM, BN = 16 * NT * WN;
   constexpr int ROWS = BM + BN;
@@ -869,7 +881,7 @@ __global__ __launch_bounds__(64 * WM * WN, (B3 && WM * WN >= 8 ? 4 : 1)) void co
 #endif
     } else {
       const int qb = q - GA;
-      if (tap_fresh && qb == 0) {
+      if (!PROD && tap_fresh && qb == 0) {      // (producer form: a 1x1 layer over one tensor of whole chunks, tap_off0 is set once)
         if (gather) {      // block-uniform: sparse convolution, the neighbour table replaces the pixel arithmetic
 #pragma unroll
           for (int i = 0; i < GB; ++i) {
@@ -891,9 +903,9 @@ __global__ __launch_bounds__(64 * WM * WN, (B3 && WM * WN >= 8 ? 4 : 1)) void co
       }
       float* dst = smem + buf * BUF + (BM + (wave * GB + qb) * 8) * 32;
 #if defined(__HIP_DEVICE_COMPILE__)
-      const bool from1 = cur_kc * BK >= c0;                               // wave-uniform: the whole chunk reads in1
+      const bool from1 = !PROD && cur_kc * BK >= c0;                      // wave-uniform: the whole chunk reads in1
       int voff = from1 ? tap_off1[qb] : tap_off0[qb];
-      if (!whole_chunks) voff = (cur_kc * BK + b_c4[qb] < c01) ? voff : (int)0x80000000;      // channels past cin inside the chunk: zero
+      if (!PROD && !whole_chunks) voff = (cur_kc * BK + b_c4[qb] < c01) ? voff : (int)0x80000000;      // channels past cin inside the chunk: zero
       if (from1) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc1, (lds_void*)dst, 16, voff, (cur_kc * BK - c0) * 4, 0, 0);      // the vector offset alone is range-checked: it must not go negative
       else __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc0, (lds_void*)dst, 16, voff, cur_kc * (BK * 4), 0, 0);
 #else
@@ -1029,14 +1041,130 @@ __global__ __launch_bounds__(64 * WM * WN, (B3 && WM * WN >= 8 ? 4 : 1)) void co
     __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
   };
+  // ---- producer form: the produced tile, and the chunks of the K loop whose pixel half comes from it.  The weight rows of the 1x1 layer are
+  // staged in an order that gives EVERY wave a part of every produced chunk: 16-row tile m of wave row wm holds channels 32 m + 16 wm .. + 15,
+  // half of chunk m.  (Which wave multiplies a channel does not touch its sum: the k order is the chunk and k-group order.)  Chunks 0 and 1 then
+  // leave the registers for the two free buffers before the K loop starts, and only tiles 2 and 3 (16 registers) stay live into it
+  constexpr int NPROD = 4;      // produced chunks: 128 channels
+  f32x4 tp[PROD ? MT : 1][PROD ? NT : 1];
+  // pixel half of produced chunk M into buffer BUF: lane (j, g) holds channels 16 wm + 4 g .. + 3 of the chunk for pixel row pr: one 16-byte slot
+  auto put_produced = [&](auto M, auto BUFC) {
+    if constexpr (PROD) {
+      constexpr int m = decltype(M)::value, buf = decltype(BUFC)::value;
+      typedef __attribute__((address_space(3))) f32x4 lds_f4w;
+      asm volatile("" ::: "memory");      // the stores stay behind the barrier that freed the buffer
+#pragma unroll
+      for (int n = 0; n < NT; ++n) {
+        const int pr = (wn * NT + n) * 16 + j;      // ((BM + pr) >> 1) & SWM == sx: BM and the tile rows are multiples of 16
+        *(lds_f4w*)(smem + buf * BUF + (BM + pr) * 32 + 4 * ((wm * 4 + g) ^ sx)) = tp[m][n];
+      }
+    }
+  };
+  // chunk `chunk` of the layer's own K loop on its way into buffer BUF (cb == 0: a chunk's parity is its buffer's)
+  auto issue_chunk_prod = [&](int chunk, auto BUFC) {
+    constexpr int buf = decltype(BUFC)::value;
+    if (chunk < NPROD) {      // block-uniform: chunk 1 (its pixel half is in place), 2 or 3
+#pragma unroll
+      for (int q = 0; q < GA; ++q) issue_one(chunk, buf, q);
+      if (chunk >= 2) put_produced(std::integral_constant<int, 2 + buf>(), BUFC);
+      ++cur_kc;      // the cursor of the pixel DMAs: their first chunk is NPROD (tap_fresh is still set then)
+    } else {
+#pragma unroll
+      for (int q = 0; q < G; ++q) issue_one(chunk, buf, q);
+    }
+  };
+  if constexpr (PROD) {
+    static_assert(!SCALE && !B3 && NB == 2 && MT == 4 && WM == 2 && EPI == EPI_AFFINE, "producer form: the 128 x 128 AFFINE tile, exact fp32");
+    const int kx = P.fuse_kpad / BK;
+    int pa_voff[GA], pb_voff[GB];
+#pragma unroll
+    for (int q = 0; q < GA; ++q) {
+      const int r = (wave * GA + q) * 8 + (lane >> 3);
+      const int k4 = (lane & 7) ^ ((r >> 1) & SWM);
+      const int grow = 32 * ((r >> 4) & 3) + 16 * (r >> 6) + (r & 15);      // tile m = (r >> 4) & 3 of wave row r >> 6
+      pa_voff[q] = (grow * P.fuse_kpad + k4 * 4) * (int)sizeof(float);
+    }
+#pragma unroll
+    for (int q = 0; q < GB; ++q) {      // both 1x1 layers read pixel gp itself (past the last one: beyond the buffer, zero-filled)
+      const int gp = p_tile * BN + (wave * GB + q) * 8 + (lane >> 3);
+      pb_voff[q] = gp < Ptot ? ((gp - img0 * HWout) * P.e0_cs + b_c4[q]) * (int)sizeof(float) : (int)0x80000000;
+      tap_off0[q] = gp < Ptot ? ((gp - img0 * HWout) * in0_cs + b_c4[q]) * (int)sizeof(float) : (int)0x80000000;
+    }
+#if defined(__HIP_DEVICE_COMPILE__)
+    const __amdgpu_buffer_rsrc_t rsrc_pw = make_rsrc(P.fuse_w, (size_t)P.fuse_cout_pad * P.fuse_kpad * sizeof(float));
+    const __amdgpu_buffer_rsrc_t rsrc_px = make_rsrc(P.e0 + img0_px * P.e0_cs, imgs_left * P.Hin * P.Win * P.e0_cs * sizeof(float));
+#endif
+    auto issue_x = [&](int c, int buf) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+      for (int q = 0; q < GA; ++q)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_pw, (lds_void*)(smem + buf * BUF + (wave * GA + q) * 8 * 32), 16, pa_voff[q], c * (BK * 4), 0, 0);
+#pragma unroll
+      for (int q = 0; q < GB; ++q)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_px, (lds_void*)(smem + buf * BUF + (BM + (wave * GB + q) * 8) * 32), 16, pb_voff[q], c * (BK * 4), 0, 0);
+#else
+      (void)c; (void)buf;
+#endif
+    };
+    issue_x(0, 0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    // the K loop below, over the kx chunks of x: the same k-groups in the same order into the same accumulators
+    auto prod_step = [&](const int c, auto BUFC) {
+      constexpr int buf = decltype(BUFC)::value, ibuf = buf ^ 1;
+      read_frags(buf, 0, 0);
+      if (c > 0) mfmas((NG - 1) & 1);
+      if (c + 1 < kx) issue_x(c + 1, ibuf);
+#pragma unroll
+      for (int t4 = 0; t4 < NG - 1; ++t4) {
+        read_frags(buf, t4 + 1, (t4 + 1) & 1);
+        mfmas(t4 & 1);
+      }
+      if (c + 1 < kx) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+      }
+    };
+    for (int c = 0; c < kx; c += 2) {
+      prod_step(c, std::integral_constant<int, 0>());
+      if (c + 1 < kx) prod_step(c + 1, std::integral_constant<int, 1>());
+    }
+    mfmas((NG - 1) & 1);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();      // every wave has read its last fragments of x: both buffers are free
+#pragma unroll
+    for (int q = 0; q < GA; ++q) issue_one(0, 0, q);      // the layer's first weight chunk lands under the epilogue
+    // the 1x1 layer's AFFINE epilogue (run_epilogue: acc * scale + bias, ReLU) into registers; pixels past the last one feed columns nobody stores
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+      const int c = 32 * m + 16 * wm + 4 * g;
+      const float4 sc = ld4(P.fuse_scale + c), bi = ld4(P.fuse_bias + c);
+#pragma unroll
+      for (int n = 0; n < NT; ++n) {
+        float4 v;
+        v.x = acc[m][n][0] * sc.x + bi.x; v.y = acc[m][n][1] * sc.y + bi.y;
+        v.z = acc[m][n][2] * sc.z + bi.z; v.w = acc[m][n][3] * sc.w + bi.w;
+        tp[m][n] = (f32x4){act_apply(v.x, ACT_RELU), act_apply(v.y, ACT_RELU), act_apply(v.z, ACT_RELU), act_apply(v.w, ACT_RELU)};
+        acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      }
+    }
+  }
   // prologue: LA = NB-1 chunks in flight, the first one retired and published
   SF_STAMP_AT(L, 1);
+  if constexpr (PROD) {      // (the weight half of chunk 0 is in flight)
+    put_produced(std::integral_constant<int, 0>(), std::integral_constant<int, 0>());
+    put_produced(std::integral_constant<int, 1>(), std::integral_constant<int, 1>());
+    ++cur_kc;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  } else {
 #pragma unroll
-  for (int c = 0; c < LA; ++c)
-    if (c < nchunks) {      // block-uniform
+    for (int c = 0; c < LA; ++c)
+      if (c < nchunks) {      // block-uniform
 #pragma unroll
-      for (int q = 0; q < G; ++q) issue_one(cb + c, c, q);
-    }
+        for (int q = 0; q < G; ++q) issue_one(cb + c, c, q);
+      }
+  }
   if (LA > 1 && nchunks >= LA) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G * (LA - 1)) : "memory");
   else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
@@ -1063,8 +1191,12 @@ __global__ __launch_bounds__(64 * WM * WN, (B3 && WM * WN >= 8 ? 4 : 1)) void co
     const unsigned long long ti0 = __builtin_amdgcn_s_memtime();
 #endif
     if (more) {
+      if constexpr (PROD) {
+        issue_chunk_prod(c + LA, std::integral_constant<int, ibuf>());
+      } else {
 #pragma unroll
-      for (int q = 0; q < G; ++q) issue_one(cb + c + LA, ibuf, q);
+        for (int q = 0; q < G; ++q) issue_one(cb + c + LA, ibuf, q);
+      }
     }
 #ifdef SF_STAMP
     cyc_issue += __builtin_amdgcn_s_memtime() - ti0;
@@ -1122,10 +1254,10 @@ __global__ __launch_bounds__(64 * WM * WN, (B3 && WM * WN >= 8 ? 4 : 1)) void co
 constexpr int GLDS_NB = 2;
 template <int MT, int NT, int WM, int WN, bool SCALE, bool B3>
 constexpr int glds_lds() { return GLDS_NB * 16 * (MT * WM + NT * WN) * 32 * 4 + (SCALE ? 4 * 256 * 4 : 0); }
-template <int MT, int NT, int WM, int WN, int EPI, bool SCALE, bool B3>
+template <int MT, int NT, int WM, int WN, int EPI, bool SCALE, bool B3, bool PROD = false>
 static hipError_t launch_glds_tb(const ConvLaunch& L, hipStream_t stream) {
   constexpr int lds = glds_lds<MT, NT, WM, WN, SCALE, B3>();
-  constexpr auto kern = conv_glds_kernel<MT, NT, WM, WN, EPI, GLDS_NB, SCALE, B3>;
+  constexpr auto kern = conv_glds_kernel<MT, NT, WM, WN, EPI, GLDS_NB | (PROD ? GLDS_PRODUCER : 0), SCALE, B3>;
   const hipError_t e = set_max_dynamic_lds<kern>(lds);
   if (e != hipSuccess) return e;
   TileGrid g = tile_grid(L, 16 * MT * WM, 16 * NT * WN);
@@ -1406,6 +1538,13 @@ hipError_t launch_conv_glds(const ConvLaunch& L, int epi, TileId tile, hipStream
   for (int i = 0; i < L.nprob; ++i) scaled = scaled || (L.p[i].in_scale != nullptr);
   if (scaled && tile >= 0 && tile < TILE_COUNT) tile = TILES[tile].scaled_as;
   return launch_tile(AllTiles{}, L, epi, tile, TILE_DMA, scaled, 0, 0, stream);
+}
+// the producer form of the 128 x 128 AFFINE tile (conv_glds_kernel: GLDS_PRODUCER): one exact-fp32 problem of one cout tile whose first fuse_cout input
+// channels are the 1x1 layer (fuse_w, fuse_scale, fuse_bias) over e0.  dispatch.hip (run_dma128) checks what the kernel assumes
+hipError_t launch_conv_glds_producer(const ConvLaunch& L, hipStream_t stream) {
+  constexpr TileRow R = TILES[TILE_DMA128x128];
+  if (L.nprob != 1 || L.p[0].cout_pad != 16 * R.MT * R.WM || L.p[0].nsplit > 1 || launch_runs_bf16x3(L)) return hipErrorInvalidValue;
+  return launch_glds_tb<R.MT, R.NT, R.WM, R.WN, EPI_AFFINE, false, false, true>(L, stream);
 }
 
 }  // namespace sf

@@ -58,7 +58,8 @@ struct Tune {
   int sp = geti("SF_SP", 1);                       // small pixel counts: the loader / consumer kernel of conv_sp.hip (0: the round-1 kernels)
   int direct = geti("SF_DIRECT", 1);               // 0 disables the direct-fragment kernel
   int split = geti("SF_SPLIT", 1);                 // cross-workgroup split-K on 64x64 tiles (small P)
-  int glds = geti("SF_GLDS", 15);                  // LDS-DMA staging for large plain layers: bit 0 = 128-cout tiles, bit 1 = 64-cout tiles, bit 2 = LayerNorm-epilogue tiles, bit 3 = cross-workgroup split-K launches (0: register staging everywhere)
+  int glds = geti("SF_GLDS", 31);                  // LDS-DMA staging for large plain layers: bit 0 = 128-cout tiles, bit 1 = 64-cout tiles, bit 2 = LayerNorm-epilogue tiles, bit 3 = cross-workgroup split-K launches (0: register staging everywhere)
+                                                   // bits 4 and 5 are LIVE (glds_live, dispatch.hip): the ASPP head's 1x1 branch inside its projection launch / a test's forced 128 x 128 tile
   int small_dma = geti("SF_SMALL_DMA", 1);         // >= 0: plain layers below LARGE_P run on the LDS-DMA kernel (32x32 tiles); bit 0: GRU candidates too (pre-gated state)
   int narrow = geti("SF_NARROW", 9);               // tile for layers with <= 32 output channels (dispatch.hip: narrow_tile — 9: TILE_DMA32x128, 32 cout x 128 px; 4 / 6 / 7 / 10: 64 x 64 / 64 x 128 / 64 x 128 on four waves / 64 x 256; -1: the 64-row tiles as planned)
   // ---- what wino_plan / wino_runs decide by (conv_wino.hip's wino_takes says what the kernel CAN address)
@@ -93,6 +94,10 @@ bool wino_runs(const ConvProblem& q, int epi);                        // this pr
 bool sp_takes(const ConvProblem* ps, int n, int epi);                 // this group runs on the small-P kernel
 int chansum_tile_px(const ConvProblem* group, int n, int epi);
 bool pregate(long P, const sf_conv_w& cand);
+// the ASPP head's 128 x 128 LDS-DMA launches (dispatch.hip)
+int glds_live();                                                      // SF_GLDS now: bit 4 (16) the producer form, bit 5 (32) a test's forced tile
+bool plans_dma128(const ConvProblem& p, int epi);                     // run() would put this layer, alone, on TILE_DMA128x128
+int run_dma128(const ConvProblem& p, bool producer, hipStream_t st);  // one plain AFFINE layer on that tile; producer: its first fuse_cout input channels computed in the launch
 // zero fill / device-to-device copy as kernels (graph nodes like everything around them)
 hipError_t zero_fill(void* p, size_t bytes, hipStream_t st);
 hipError_t copy_floats(const float* src, float* dst, size_t n, hipStream_t st);

@@ -1071,6 +1071,58 @@ int run(const ConvProblem* ps, int n, int epi, hipStream_t st) {
   return rc;
 }
 
+// ---- the ASPP head's 128 x 128 LDS-DMA launches (api.hip: deeplab_head).  SF_GLDS bits 4 and 5 are LIVE, re-read at every head
+// (tests/test_gpu_aspp_producer.py flips them inside one process): bit 4: the 1x1 branch is computed inside the projection launch (the
+// producer form of conv_glds_kernel) where the head qualifies; bit 5, a test's setting: the 1x1 branch and the projection of a head run on
+// that tile whatever their pixel count, so that both forms can be compared on shapes of a few tiles
+int glds_live() { return geti("SF_GLDS", 31); }
+// run() would put this layer, alone, on TILE_DMA128x128
+bool plans_dma128(const ConvProblem& p, int epi) {
+  const int P = (int)pixels(p);
+  if (P <= 0 || (wino_considers(P, epi) && wino_runs(p, epi)) || sp_takes(&p, 1, epi)) return false;
+  ConvLaunch L;
+  std::memset(&L, 0, sizeof(L));
+  L.p[0] = p;
+  L.nprob = 1;
+  TiledPlan T;
+  return tiled_plan(L, P, epi, g_split, T) == SF_OK && T.tile == TILE_DMA128x128;
+}
+// One plain AFFINE layer on TILE_DMA128x128, planner or not.  producer: the first fuse_cout input channels of p are
+// relu(fuse_scale * (fuse_w . e0) + fuse_bias) and are not read from in0 (conv_igemm.hip: the producer form).  The record's cost counts both
+// GEMMs and the bytes the launch moves: x, the input channels it does read, both weight matrices, the output
+int run_dma128(const ConvProblem& p, bool producer, hipStream_t st) {
+  ConvLaunch L;
+  std::memset(&L, 0, sizeof(L));
+  L.p[0] = p;
+  L.p[0].fenced = tune().fenced;
+  L.nprob = 1;
+  const ConvProblem& q = L.p[0];
+  if (pixels(q) <= 0) return SF_OK;
+  if (q.gate || q.gather || q.in_scale || q.acc_in || q.pool2 || q.add_up || q.cout_pad % 128 || !one_source_per_chunk(q) || !offsets_fit32(q, 256.0)) return SF_ERR_UNSUPPORTED;
+  if (producer) {
+    ConvProblem x = q;      // the producer's own reads, by the same 32-bit rule
+    x.in0_cs = q.e0_cs; x.in1_cs = 0; x.cout_pad = q.fuse_cout_pad; x.ktot = q.fuse_kpad;
+    const bool ok = q.e0 && q.fuse_w && q.fuse_scale && q.fuse_bias && !q.w3 && q.cout_pad == 128 && q.c1 == 0 && q.KH == 1 && q.KW == 1 && q.stride == 1 &&
+                    q.pad == 0 && !q.in_up && q.fuse_cout == 128 && q.fuse_cout_pad == 128 && q.fuse_kpad >= 32 && q.fuse_kpad % 32 == 0 &&
+                    q.e0_cs == q.fuse_kpad && q.cin_pad > q.fuse_cout && q.cin_pad == q.c0 && q.Hin == q.Hout && q.Win == q.Wout && offsets_fit32(x, 256.0);
+    if (!ok) return SF_ERR_UNSUPPORTED;
+  }
+  SF_TRY(seg_flush());
+  L.stamp_slot = next_stamp_slot();
+  select_bf16x3(L);
+  auto cost = [&] {
+    Cost c = direct_cost(TILES[TILE_DMA128x128].key * 8 + EPI_AFFINE, L.p, 1);
+    if (producer) {
+      const double Pi = (double)pixels(q);
+      c.flops += 2.0 * Pi * q.fuse_cout * q.fuse_kpad;
+      c.bytes += 4.0 * (Pi * q.fuse_kpad + (double)q.fuse_cout * q.fuse_kpad - Pi * q.fuse_cout);
+    }
+    return c;
+  };
+  SF_HIP(timed([&] { return producer ? launch_conv_glds_producer(L, st) : launch_conv_glds(L, EPI_AFFINE, TILE_DMA128x128, st); }, cost, st));
+  return SF_OK;
+}
+
 // RAII: carve + zero the split-K scratch for the duration of one top-level call
 SplitScope::SplitScope(Arena& A, hipStream_t st) : prev(g_split) {
   if (!tune().split) return;

@@ -67,6 +67,7 @@ constexpr TileRow TILES[TILE_COUNT] = {
 hipError_t launch_conv(const ConvLaunch& L, int epi, TileId tile, hipStream_t stream);
 hipError_t launch_conv_direct(const ConvLaunch& L, int epi, int mt, int ks, hipStream_t stream);      // TILE_DIRECT16; mt: 16-row cout tiles per wave (1, 2, 4); ks: K-groups per workgroup (1..8)
 hipError_t launch_conv_glds(const ConvLaunch& L, int epi, TileId tile, hipStream_t stream);
+hipError_t launch_conv_glds_producer(const ConvLaunch& L, hipStream_t stream);      // TILE_DMA128x128, AFFINE: the first input channels computed in the workgroup (conv_igemm.hip: PROD)
 hipError_t set_stamp_buffer(unsigned long long* p);
 int glds_occupancy(int which);
 
