@@ -5,7 +5,9 @@
     run on the CPU, the reference's rollouts move by at most 3.7e-5 for a 1e-5 input perturbation, so the device path's
     summation-order differences (1e-6 .. 1e-5 a layer) land well inside it;
   * GRUCell alone to 1e-4, as test_single_branch_cells_gpu;
-  * a forward captured with torch.cuda.graph on one stream replays bitwise."""
+  * a forward captured with torch.cuda.graph on one stream replays bitwise.
+The fixtures stay under 1,000 pixels.  Sizes above them — every kernel family the cells' dispatch reaches, up to the Winograd launches of
+the benchmarked 200 x 200 rollout, against a float64 cell on all channels — are in tests/test_gpu_beverse_cells.py."""
 import os
 import sys
 
