@@ -448,6 +448,28 @@ int sf_lift_pool_fused_fwd(const float* feat, const float* depth_prob, int D, in
                            float* out, void* stream);
 /* depth.softmax(dim=1) of streamingflow.py:304 on [rows][D][fHW] */
 int sf_depth_softmax_fwd(const float* logits, float* prob, int rows, int D, int fHW, void* stream);
+/* The same softmax for logits that are still NHWC — rows * fHW pixels of cs floats each, the D logits of a pixel contiguous from channel
+ * co (a channel slice of a wider tensor; cs, co multiples of 4, the pointer 16-byte aligned) — written out planar in the same pass:
+ * out_logits [rows][D][fHW] (bitwise the input, transposed) and out_prob [rows][D][fHW] = expf(x - max) / sum.  What follows the depth
+ * branch of the camera neck: the model returns the planar logits (depth_prediction) and the lift reads the planar probabilities.
+ * SF_ERR_UNSUPPORTED, before anything is written: D not a multiple of 4 or D > 128. */
+int sf_depth_softmax_planar_fwd(const float* logits_nhwc, int cs, int co, float* out_logits, float* out_prob, int rows, int D, int fHW,
+                                void* stream);
+
+/* ---- N7: camera encoder neck (streamingflow/models/encoder.py:107-112, layers/convolutions.py:183-201) --------------------------------
+ * Both DeepLabHead + UpsamplingConcat branches (features, depth) of Encoder.get_features_depth after its endpoint selection, on one stream:
+ *   head   ONE sf_deeplab_w for both heads, which read the same input: hid = 2 * 64, the branch and pooling weights of the two heads
+ *          stacked on cout, projection / 3x3 / classifier block-diagonal, cls.cout = 2 * c_hi = [feature | depth]
+ *          (streamingflow_amd/models/encoder.py packs it; the zero blocks contribute exact zeros)
+ *   convs  [4] = feature conv1, feature conv2, depth conv1, depth conv2 of the two UpsamplingConcat: 3x3, pad 1, BN + ReLU folded;
+ *          conv1 has c0 = c_lo (the /8 endpoint) and c1 = c_hi (its half of the upsampled head output) — cat[x, upsampled], never written
+ *   hi [n][H][W][c_hi], lo [n][2H][2W][c_lo]  ->  rays [n * 4HW][C] (NHWC features, the rows the lift gathers), depth_logits and
+ *   depth_prob [n][D][4HW] (planar, as sf_depth_softmax_planar_fwd writes them).
+ * SF_ERR_INVALID: a NULL pointer or structs that are not such a neck; SF_ERR_UNSUPPORTED (nothing written): D % 4 != 0 or D > 128;
+ * SF_ERR_WORKSPACE: ws_bytes < sf_camera_neck_ws_bytes(c_hi, c_lo, C, D, hid, n, H, W) (hid = head->hid; 0 for invalid sizes). */
+size_t sf_camera_neck_ws_bytes(int c_hi, int c_lo, int C, int D, int hid, int n, int H, int W);
+int sf_camera_neck_fwd(const sf_deeplab_w* head, const sf_conv_w* convs, const float* hi, const float* lo, float* rays,
+                       float* depth_logits, float* depth_prob, int n, int H, int W, float* ws, size_t ws_bytes, void* stream);
 
 /* ---- N2 (first half): LiDAR hard voxelisation ------------------------------------------------------
  * hard_voxelize — mmdet3d/ops/voxel/src/voxelization.h:63-85, deterministic GPU path

@@ -278,3 +278,28 @@ class DeepLabHead(nn.Sequential, PackedModule):
 
     def forward(self, x):
         return runtime.to_nchw(self.forward_nhwc(runtime.to_nhwc(x)))
+
+
+class UpsamplingConcat(nn.Module):
+    """Parameter container for convolutions.py:183-201 (bilinear x2 of the first argument, cat[x, upsampled], two 3x3 conv + BN +
+    ReLU; keys ``conv.0/1/3/4.*``).  It runs inside the camera neck's single entry point (models/encoder.py: sf_camera_neck_fwd),
+    where the concatenation is never written: ``pack`` gives the two packed convolutions for a given channel split."""
+
+    def __init__(self, in_channels, out_channels, scale_factor=2):
+        super().__init__()
+        if scale_factor != 2:
+            raise NotImplementedError("UpsamplingConcat: the x2 bilinear kernel only")
+        self.upsample = nn.Upsample(scale_factor=scale_factor, mode='bilinear', align_corners=False)
+        self.conv = _seq(nn.Conv2d(in_channels, out_channels, kernel_size=3, padding=1, bias=False), nn.BatchNorm2d(out_channels),
+                         nn.ReLU(inplace=True),
+                         nn.Conv2d(out_channels, out_channels, kernel_size=3, padding=1, bias=False), nn.BatchNorm2d(out_channels),
+                         nn.ReLU(inplace=True))
+        self.in_channels, self.out_channels = in_channels, out_channels
+
+    def pack(self, pk, c_skip):
+        """(conv1, conv2) as _lib.ConvW owned by ``pk``; conv1 reads c_skip channels of x, then in_channels - c_skip upsampled ones."""
+        sc, bi = packing.bn_fold(self.conv[1])
+        c1 = packing.conv_w(pk, self.conv[0].weight, c_skip, self.in_channels - c_skip, scale=sc, bias=bi, act="relu", pad=1)
+        sc, bi = packing.bn_fold(self.conv[4])
+        c2 = packing.conv_w(pk, self.conv[3].weight, self.out_channels, scale=sc, bias=bi, act="relu", pad=1)
+        return c1, c2

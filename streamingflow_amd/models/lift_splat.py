@@ -179,26 +179,40 @@ class LiftSplat(nn.Module):
             A[:, :t + 1] = ego[:, t].view(b, 1, 1, 4, 4).matmul(A[:, :t + 1])
         return A[..., :3, :].reshape(b, s, n, 12).float().contiguous()
 
-    def lift_splat(self, feat, depth_logits, intrinsics, extrinsics, future_egomotion, nhwc=False):
+    def lift_splat(self, feat, depth_logits, intrinsics, extrinsics, future_egomotion, nhwc=False, rays_nhwc=None, depth_prob=None):
         """get_geometry + depth softmax (x) features + projection_to_birds_eye_view in one pass.
-        feat [b,s,n,C,fH,fW] image features, depth_logits [b,s,n,D,fH,fW] -> [b, s, C, X, Y]."""
-        runtime.require_cuda(feat, depth_logits, intrinsics, extrinsics, future_egomotion)
-        b, s, n, C, fH, fW = feat.shape
-        D = depth_logits.shape[3]
+        feat [b,s,n,C,fH,fW] image features, depth_logits [b,s,n,D,fH,fW] -> [b, s, C, X, Y].
+        ``rays_nhwc`` [b*s*n*fH*fW, C] (the features already in the gather layout; ``feat`` may then be None) and ``depth_prob``
+        [b*s*n, D, fH*fW] (the softmax already taken) replace the transpose and the softmax launch: what the camera neck hands over."""
+        runtime.require_cuda(feat, depth_logits, intrinsics, extrinsics, future_egomotion, rays_nhwc, depth_prob)
+        b, s, n, D, fH, fW = depth_logits.shape
+        C = feat.shape[3] if rays_nhwc is None else rays_nhwc.shape[-1]
         (X, Y, Z), _, _ = self._grid
         if Z != 1:
             raise RuntimeError("lift_splat collapses the height axis: Z_BOUND must give one slice")
         if (D, fH, fW) != tuple(self.frustum.shape[:3]):
             raise RuntimeError("feature / depth shape does not match the frustum %s" % (tuple(self.frustum.shape[:3]),))
-        dev = feat.device
+        dev = depth_logits.device
         L = _lib.lib()
         st = runtime.stream_ptr(dev)
         fHW = fH * fW
         rows = b * s * n
-        logits = runtime.f32c(depth_logits).view(rows, D, fHW)
-        prob = torch.empty_like(logits)
-        _lib.check(L.sf_depth_softmax_fwd(ptr(logits), ptr(prob), rows, D, fHW, st), "depth_softmax")
-        rays = runtime.to_nhwc(feat.reshape(rows, C, fH, fW)).view(rows * fHW, C)
+        if depth_prob is None:
+            logits = runtime.f32c(depth_logits).view(rows, D, fHW)
+            prob = torch.empty_like(logits)
+            _lib.check(L.sf_depth_softmax_fwd(ptr(logits), ptr(prob), rows, D, fHW, st), "depth_softmax")
+        else:
+            prob = runtime.f32c(depth_prob)
+            if prob.numel() != rows * D * fHW:
+                raise RuntimeError("depth_prob %s does not match depth_logits %s" % (tuple(depth_prob.shape), tuple(depth_logits.shape)))
+        if rays_nhwc is None:
+            if tuple(feat.shape) != (b, s, n, C, fH, fW):
+                raise RuntimeError("feat %s does not match depth_logits %s" % (tuple(feat.shape), tuple(depth_logits.shape)))
+            rays = runtime.to_nhwc(feat.reshape(rows, C, fH, fW)).view(rows * fHW, C)
+        else:
+            rays = runtime.f32c(rays_nhwc)
+            if tuple(rays.shape) != (rows * fHW, C):
+                raise RuntimeError("rays_nhwc %s: expected [%d, C]" % (tuple(rays.shape), rows * fHW))
         aff = self.rig_affines(intrinsics, extrinsics, future_egomotion).view(rows, 12)
         fr = self.frustum
         us, vs, ds = fr[0, 0, :, 0].contiguous(), fr[0, :, 0, 1].contiguous(), fr[:, 0, 0, 2].contiguous()

@@ -4,10 +4,11 @@ Mirrors ``streamingflow.forward`` (streamingflow/models/streamingflow.py:208-269
 attribute names (``temporal_model``, ``encoders.lidar.{voxelize,backbone}``, ``temporal_model_lidar``,
 ``future_prediction_ode``, ``decoder``, ``bev_resolution`` / ``bev_start_position`` / ``bev_dimension``,
 ``frustum``), so a released ``model.*`` checkpoint slice loads with ``strict=False``.  The one part that
-is NOT here is the EfficientNet image ``Encoder`` (streamingflow/models/encoder.py; needs
-``efficientnet_pytorch``, out of scope — SURVEY.md §8): assign any module returning
-``(features [b*n, C, fH, fW], depth_logits [b*n, D, fH, fW])`` to ``self.encoder``, or pass that pair in
-place of ``image``.
+is NOT here is the EfficientNet trunk of the image ``Encoder`` (streamingflow/models/encoder.py; needs
+``efficientnet_pytorch``, out of scope — SURVEY.md §8).  The encoder's neck is (models/encoder.py): pass
+``encoder=Encoder(cfg.MODEL.ENCODER, D, backbone=EfficientNetEndpoints(trunk, ...))`` or assign it to ``self.encoder`` — its
+outputs then reach the lift in the layouts the lift reads — or assign any module returning
+``(features [b*n, C, fH, fW], depth_logits [b*n, D, fH, fW])``, or pass that pair in place of ``image``.
 
 Camera:  (features, depth logits, rig) -> LiftSplat.lift_splat -> + ego-pose channels -> TemporalModel
 LiDAR:   point clouds -> hard voxelisation + mean -> SparseEncoder -> TemporalModel
@@ -61,7 +62,7 @@ def default_cfg(**over):
 
 
 class streamingflow(nn.Module):
-    def __init__(self, cfg):
+    def __init__(self, cfg, encoder=None):
         super().__init__()
         self.cfg = cfg
         self.lift = LiftSplat.from_cfg(cfg)
@@ -74,7 +75,9 @@ class streamingflow(nn.Module):
         self.latent_dim = cfg.MODEL.DISTRIBUTION.LATENT_DIM
         self.planning_enabled = bool(getattr(getattr(cfg, "PLANNING", None), "ENABLED", False))
         self.bev_size = (int(self.bev_dimension[0]), int(self.bev_dimension[1]))
-        self.encoder = None                       # image backbone: not part of this build (see module docstring)
+        # image encoder: None unless given (or assigned later).  models/encoder.py has the reference's neck on the device; the
+        # EfficientNet trunk in front of it is not part of this build (see module docstring)
+        self.encoder = encoder
         tm = cfg.MODEL.TEMPORAL_MODEL
         if tm.NAME != "temporal_block":
             raise NotImplementedError("TEMPORAL_MODEL.NAME == 'temporal_block' only")
@@ -133,7 +136,19 @@ class streamingflow(nn.Module):
             if self.encoder is None:
                 raise RuntimeError("no image backbone: set `.encoder` or pass (features, depth_logits) instead of images")
             b, s, n = image.shape[:3]
-            feat, depth = self.encoder(image.reshape(b * s * n, *image.shape[3:]))
+            flat = image.reshape(b * s * n, *image.shape[3:])
+            if hasattr(self.encoder, "neck_nhwc"):
+                # the neck's own layouts go straight to the lift: NHWC rays and planar probabilities, no transpose, no softmax launch
+                rays, logits, prob = self.encoder.forward_nhwc(flat)
+                D, (fH, fW) = logits.shape[1], self.frustum.shape[1:3]
+                depth = logits.view(b, s, n, D, fH, fW)
+                x = self.lift.lift_splat(None, depth, intrinsics, extrinsics, future_egomotion, rays_nhwc=rays, depth_prob=prob)
+                cam_front = None
+                if self.planning_enabled:      # only the front camera of the present frame goes back to NCHW
+                    from .. import runtime
+                    cam_front = runtime.to_nchw(rays.view(b, s, n, fH, fW, -1)[:, -1, 1].contiguous())
+                return x, depth, cam_front
+            feat, depth = self.encoder(flat)
             feat, depth = feat.view(b, s, n, *feat.shape[1:]), depth.view(b, s, n, *depth.shape[1:])
         x = self.lift.lift_splat(feat, depth, intrinsics, extrinsics, future_egomotion)
         cam_front = feat[:, -1, 1].contiguous() if self.planning_enabled else None
