@@ -46,17 +46,24 @@ int gru_cell(const sf_gru_w& w, const float* x, const float* s, float* out, floa
   return run1(b, EPI_BLEND, st);
 }
 
-size_t dual_ws_floats(int C, int P) { return 2 * al((size_t)P * 2 * C) + 8 * al((size_t)P * C); }
-
+// ---- workspace layouts (dispatch.h: Arena).  One struct per module: take() is the carve of the forward AND, through a measuring arena,
+// the module's sf_*_ws_bytes.  It sees what the size query is given (and the flow mode), never a weight or a launch plan: where a call can
+// need less than that tells (a tile width, an absent projection), the bound is carved.  P: pixels of all images.
+// gates [P][2C] and the pre-gated state [P][C] of one conv-GRU cell; SpatialGRU: + the two states it alternates between
+struct GruBufs { float *g, *rs; void take(Arena& A, int C, size_t P) { g = A.take(P * 2 * C); rs = A.take(P * C); } };
+struct SpatialGruBufs { float *g, *sa, *sb, *rs; void take(Arena& A, int C, size_t P) { g = A.take(P * 2 * C); sa = A.take(P * C); sb = A.take(P * C); rs = A.take(P * C); } };
+template <class Bufs>
+struct WithSplit {      // a module's buffers behind the split-K scratch of its convolutions
+  SplitBufs split;
+  Bufs bufs;
+  template <class... Dims> void take(Arena& A, Dims... dims) { split.take(A); bufs.take(A, dims...); }
+};
 // scratch of one dual cell (temporal_ode_bayes.py:92-131 / :239-275)
 struct CellBufs {
   float *g1, *g2, *h1, *h2, *r2, *t1, *sk, *t2, *rs1, *rs2;
-  bool take(Arena& A, int C, int P) {
-    g1 = A.take((size_t)P * 2 * C); g2 = A.take((size_t)P * 2 * C);
-    h1 = A.take((size_t)P * C); h2 = A.take((size_t)P * C); r2 = A.take((size_t)P * C);
-    t1 = A.take((size_t)P * C); sk = A.take((size_t)P * C); t2 = A.take((size_t)P * C);
-    rs1 = A.take((size_t)P * C); rs2 = A.take((size_t)P * C);
-    return A.ok();
+  void take(Arena& A, int C, size_t P) {
+    g1 = A.take(P * 2 * C); g2 = A.take(P * 2 * C); h1 = A.take(P * C); h2 = A.take(P * C); r2 = A.take(P * C);
+    t1 = A.take(P * C); sk = A.take(P * C); t2 = A.take(P * C); rs1 = A.take(P * C); rs2 = A.take(P * C);
   }
 };
 // Small-P kernel: a 1x1 + LayerNorm + GELU layer `q` (weights w1) that follows the LayerNorm layer ps[0] is applied to ps[0]'s
@@ -185,11 +192,9 @@ bool carry_ok(const sf_dual_w& w, const sf_pmodel_w& pm, int B, int H, int W) {
 // coefficient records of consecutive images (0: one record shared by all).  `carry`: gates2 / cand2 of this cell were
 // computed beside the previous infer_state (see Carry).
 int dual_cell(const sf_dual_w& w, const float* x, const float* s, float* out, int derivative, const float* base,
-              const float* coef, int coef_stride, float* out2, int acc2, int B, int H, int W, Arena& A, hipStream_t st,
+              const float* coef, int coef_stride, float* out2, int acc2, int B, int H, int W, const CellBufs& b, hipStream_t st,
               const Carry* carry = nullptr) {
   const int C = w.C, P = B * H * W;
-  CellBufs b;
-  if (!b.take(A, C, P)) return SF_ERR_WORKSPACE;
   const bool pre = pregate(P, w.cand1) && pregate(P, w.cand2);
   ConvProblem ps[2];
   if (carry) {
@@ -211,17 +216,22 @@ int dual_cell(const sf_dual_w& w, const float* x, const float* s, float* out, in
 }
 
 constexpr int SE_SLABS = 64;
-size_t infer_ws_floats(int C, int P) {
-  int nt = (P + 15) / 16;
-  if (nt < SE_SLABS * 64) nt = SE_SLABS * 64;   // room for [B<=64][SE_SLABS] slab sums as well
-  return al((size_t)P * C) + 4 * al((size_t)P * 2 * C) + 2 * al((size_t)nt * 2 * C) + 3 * al((size_t)64 * 2 * C);
-}
+// scratch of infer_state.  cs1 / cs2: the SE producers' channel sums, [rows][2C] — one image: a row per pixel tile of the producing launch,
+// whose kernel (16, 32 or 64 pixels a tile) the plan decides: carved for 16; several images: SE_SLABS slab sums per image
+struct InferBufs {
+  float *a, *pr, *y1, *b, *y2, *cs1, *cs2, *sc1, *sc2, *slabs;
+  void take(Arena& A, int C, int B, size_t HW) {
+    const size_t P = B * HW, C2 = 2 * (size_t)C, rows = B == 1 ? (P + 15) / 16 : (size_t)B * SE_SLABS;
+    a = A.take(P * C); pr = A.take(P * C2); y1 = A.take(P * C2); b = A.take(P * C2); y2 = A.take(P * C2);
+    cs1 = A.take(rows * C2); cs2 = A.take(rows * C2); sc1 = A.take(B * C2); sc2 = A.take(B * C2); slabs = A.take(SE_SLABS * C2);
+  }
+};
 
 // temporal_ode_bayes.py:463-477 on B images.  SE channel means: B == 1 uses the per-16-pixel sums
 // the producing conv's epilogue writes; B > 1 (16-pixel tiles straddle images) sums per-image
 // slabs with one extra small launch.  Both are fixed-order.
 int infer_state(const sf_pmodel_w& w, const float* s, const float* eps, float* p_out, float* q_out, int B, int H, int W,
-                Arena& A, hipStream_t st, const unsigned long long* philox = nullptr, int draw = 0, const Side* side = nullptr) {
+                const InferBufs& ib, hipStream_t st, const unsigned long long* philox = nullptr, int draw = 0, const Side* side = nullptr) {
   if (!eps && !philox) return SF_ERR_INVALID;
   const int C = w.C, C2 = 2 * C, HW = H * W, P = B * HW;
   if (B < 1 || B > 64) return SF_ERR_UNSUPPORTED;
@@ -237,17 +247,8 @@ int infer_state(const sf_pmodel_w& w, const float* s, const float* eps, float* p
   const int n2 = infer_group2(w, side, B, H, W, l2);
   const int tpx1 = chansum_tile_px(l2, n2, EPI_AFFINE), tpx2 = chansum_tile_px(&c4, 1, EPI_AFFINE);
   const int nt1 = tiles ? (P + tpx1 - 1) / tpx1 : SE_SLABS, nt2 = tiles ? (P + tpx2 - 1) / tpx2 : SE_SLABS;
-  float* a = A.take((size_t)P * C);
-  float* pr = A.take((size_t)P * C2);
-  float* y1 = A.take((size_t)P * C2);
-  float* b = A.take((size_t)P * C2);
-  float* y2 = A.take((size_t)P * C2);
-  float* cs1 = A.take(tiles ? (size_t)nt1 * C2 : (size_t)B * SE_SLABS * C2);
-  float* cs2 = A.take(tiles ? (size_t)nt2 * C2 : (size_t)B * SE_SLABS * C2);
-  float* sc1 = A.take((size_t)B * C2);
-  float* sc2 = A.take((size_t)B * C2);
-  float* slabs = A.take((size_t)SE_SLABS * C2);
-  if (!A.ok()) return SF_ERR_WORKSPACE;
+  if (tpx1 < 16 || tpx2 < 16) return SF_ERR_UNSUPPORTED;      // InferBufs carves a row of sums per 16 pixels
+  float *a = ib.a, *pr = ib.pr, *y1 = ib.y1, *b = ib.b, *y2 = ib.y2, *cs1 = ib.cs1, *cs2 = ib.cs2, *sc1 = ib.sc1, *sc2 = ib.sc2, *slabs = ib.slabs;
   if (!w.rb0.proj.w || w.rb1.proj.w) return SF_ERR_INVALID;
   auto gate = [&](const float* y, const float* rows, int nrows, const float* fc0, const float* fc2, float* scale) -> int {
     SF_TRY(seg_flush());
@@ -302,7 +303,8 @@ struct Stage {              // (the defaults: an inner stage of an ODE step)
   bool infer_after = true; int draw = 0; float* p_out = nullptr;
   int op_end = -1;      // index of the op this stage completes (-1: an inner solver stage)
 };
-struct StageBufs { float *k, *pk, *acc, *s3; };      // [P][C] each; Euler uses none
+// [P][C] each; midpoint uses three, Euler none: the size query is not told the solver
+struct StageBufs { float *k, *pk, *acc, *s3; void take(Arena& A, size_t PC) { k = A.take(PC); pk = A.take(PC); acc = A.take(PC); s3 = A.take(PC); } };
 
 // One ODE step (temporal_ode_bayes.py:436-461, + build-defined RK4) of cell `w` as 1, 2 or 4 stages appended to `out`: input x (the
 // imputed input, or zeros with IMPUTE off), state s -> s2, and infer_state(s2) -> p2 where need_p.  cf: the step's coefficient record
@@ -331,30 +333,30 @@ int step_stages(int solver, const sf_dual_w* w, const float* x, const float* s, 
 }
 
 // One stand-alone step: its stages one after the other, every cell and every infer_state on its own (no carried branch, no persistent flow).
-// `zeros`: [P][C] zero tensor (IMPUTE=False).  Scratch: k, pk, acc, s3 (P*C each; Euler: none) + cell/infer workspaces.
-int ode_step(const sf_dual_w& gc, const sf_pmodel_w& pm, int solver, int impute, const float* s_in, const float* p_in, const float* coef,
-             int coef_stride, const float* eps, float* s_out, float* p_out, const float* zeros, int B, int H, int W, Arena& A0, hipStream_t st) {
-  if (solver != SF_SOLVER_EULER && solver != SF_SOLVER_MIDPOINT && solver != SF_SOLVER_RK4) return SF_ERR_INVALID;
-  const size_t PC = (size_t)B * H * W * gc.C;
-  StageBufs sb = {};
-  if (solver != SF_SOLVER_EULER) {
-    sb.k = A0.take(PC); sb.pk = A0.take(PC); sb.acc = A0.take(PC);
-    if (solver == SF_SOLVER_RK4) sb.s3 = A0.take(PC);
-    if (!A0.ok()) return SF_ERR_WORKSPACE;
+// `zeros`: [P][C] zero tensor (IMPUTE=False); the solver stages; a cell's scratch overlays the infer_state's behind it.
+struct StepLayout {
+  SplitBufs split;
+  float* zeros;
+  StageBufs sb;
+  CellBufs cell;
+  InferBufs inf;
+  void take(Arena& A, int C, int B, size_t HW) {
+    split.take(A);
+    zeros = A.take(B * HW * C);
+    sb.take(A, B * HW * C);
+    A.larger_of([&] { cell.take(A, C, B * HW); }, [&] { inf.take(A, C, B, HW); });
   }
+};
+int ode_step(const sf_dual_w& gc, const sf_pmodel_w& pm, int solver, int impute, const float* s_in, const float* p_in, const float* coef,
+             int coef_stride, const float* eps, float* s_out, float* p_out, const StepLayout& L, int B, int H, int W, hipStream_t st) {
+  const size_t PC = (size_t)B * H * W * gc.C;
   std::vector<Stage> stages;
-  step_stages(solver, &gc, impute ? p_in : zeros, s_in, s_out, p_out, true, coef, 0, 0, sb, stages);
+  step_stages(solver, &gc, impute ? p_in : L.zeros, s_in, s_out, p_out, true, coef, 0, 0, L.sb, stages);
   for (const Stage& g : stages) {
-    Arena Ac = A0, Ai = A0;
-    SF_TRY(dual_cell(*g.w, g.x, g.s, g.out, g.derivative, g.base, g.coef, coef_stride, g.out2, g.acc2, B, H, W, Ac, st));
-    if (g.infer_after) SF_TRY(infer_state(pm, g.out, eps + (size_t)g.draw * PC, g.p_out, nullptr, B, H, W, Ai, st));
+    SF_TRY(dual_cell(*g.w, g.x, g.s, g.out, g.derivative, g.base, g.coef, coef_stride, g.out2, g.acc2, B, H, W, L.cell, st));
+    if (g.infer_after) SF_TRY(infer_state(pm, g.out, eps + (size_t)g.draw * PC, g.p_out, nullptr, B, H, W, L.inf, st));
   }
   return SF_OK;
-}
-
-size_t ode_step_ws_floats(int C, int P) {
-  size_t cellw = dual_ws_floats(C, P), inf = infer_ws_floats(C, P);
-  return 4 * al((size_t)P * C) + (cellw > inf ? cellw : inf);
 }
 
 // ResBlock (res_models.py:74-79) on n images; t: [P][cin] scratch, pr: [P][cout] scratch (if proj)
@@ -471,8 +473,9 @@ int sf_conv2d_ex_fwd(const sf_conv_w* w, const float* in0, int in0_cs, const flo
   if (in0_cs < w->c0 || (w->c1 > 0 && in1_cs < w->c1) || out_cs < out_co + w->cout || (in0_cs % 4) || (out_cs % 4) || (out_co % 4) ||
       (add && (add_cs < w->cout || (add_cs % 4))))
     return SF_ERR_INVALID;
-  Arena A(ws, ws_bytes);
-  SplitScope sp(A, (hipStream_t)stream);
+  SplitBufs split;
+  carve(split, ws, ws_bytes);      // optional scratch: what does not fit stays null, and the call runs without split-K
+  SplitScope sp(split, (hipStream_t)stream);
   ConvProblem p = problem(*w, in0, in1, out, n_img, Hin, Win, in_up);
   p.in0_cs = in0_cs;
   if (w->c1 > 0) p.in1_cs = in1_cs;
@@ -483,7 +486,7 @@ int sf_conv2d_ex_fwd(const sf_conv_w* w, const float* in0, int in0_cs, const flo
   if (act_after_add) p.mode |= 2;
   return run1(p, EPI_AFFINE, (hipStream_t)stream);
 }
-size_t sf_conv2d_ex_ws_bytes(void) { return SPLIT_WS_FLOATS * sizeof(float); }
+size_t sf_conv2d_ex_ws_bytes(void) { return layout_bytes<SplitBufs>(); }
 
 /* UpsamplingAdd tail — convolutions.py:208,215: out = bilinear_x2(in) + skip (skip may be NULL) */
 int sf_upsample_bilinear2_add_fwd(const float* in, const float* skip, float* out, int n, int Hin, int Win, int C, void* stream) {
@@ -500,8 +503,9 @@ int sf_sparse_conv_masked_fwd(const sf_conv_w* w, const float* feats, int feats_
       (feats_cs % 4))
     return SF_ERR_INVALID;
   if (n_out == 0) return SF_OK;
-  Arena A(ws, ws_bytes);
-  SplitScope sp(A, (hipStream_t)stream);
+  SplitBufs split;
+  carve(split, ws, ws_bytes);      // optional scratch: what does not fit stays null, and the call runs without split-K
+  SplitScope sp(split, (hipStream_t)stream);
   ConvProblem p = problem(*w, feats, nullptr, out, 1, 1, n_in, 0);   // the input "image" is the n_in feature rows
   p.in0_cs = feats_cs;
   p.Hout = 1; p.Wout = n_out;
@@ -517,14 +521,14 @@ int sf_sparse_conv_fwd(const sf_conv_w* w, const float* feats, int feats_cs, int
 }
 
 /* per-image channel means of an NHWC tensor (fixed-order two-level sum: reproducible) */
-size_t sf_channel_mean_ws_bytes(int C, int n) { return al((size_t)n * 64 * C) * sizeof(float); }
+struct MeanBufs { float* part; void take(Arena& A, int C, int n) { part = A.take((size_t)n * 64 * C); } };      // 64 slab sums per image
+size_t sf_channel_mean_ws_bytes(int C, int n) { return layout_bytes<MeanBufs>(C, n); }
 int sf_channel_mean_fwd(const float* x, float* out, int n, int HW, int C, float* ws, size_t ws_bytes, void* stream) {
   if (!x || !out || n < 1 || HW < 1 || C < 4 || (C % 4) || C > 1024) return SF_ERR_INVALID;
-  Arena A(ws, ws_bytes);
-  float* part = A.take((size_t)n * 64 * C);
-  if (!A.ok() || !part) return SF_ERR_WORKSPACE;
-  SF_HIP(launch_chan_partial(x, part, n, HW, C, 64, (hipStream_t)stream));
-  SF_HIP(launch_mean_from_partials(part, out, n, 64, C, HW, (hipStream_t)stream));
+  MeanBufs b;
+  if (!carve(b, ws, ws_bytes, C, n)) return SF_ERR_WORKSPACE;
+  SF_HIP(launch_chan_partial(x, b.part, n, HW, C, 64, (hipStream_t)stream));
+  SF_HIP(launch_mean_from_partials(b.part, out, n, 64, C, HW, (hipStream_t)stream));
   return SF_OK;
 }
 /* elementwise LogSigmoid (DistributionModule(method='BERNOULLI'), streamingflow/models/distributions.py:33, :47) */
@@ -546,25 +550,22 @@ int sf_broadcast_channels_fwd(const float* vec, float* out, int n, int HW, int k
 int sf_conv2d_repeat(const sf_conv_w* w, const float* in0, const float* in1, const float* add, float* out, int n_img,
                      int Hin, int Win, int in_up, int reps, float* ws, size_t ws_bytes, void* stream) {
   if (!w || !valid_w(*w) || !in0 || !out || (w->c1 > 0 && !in1)) return SF_ERR_INVALID;
-  Arena A(ws, ws_bytes);
-  SplitScope sp(A, (hipStream_t)stream);
+  SplitBufs split;
+  carve(split, ws, ws_bytes);      // optional scratch: what does not fit stays null, and the call runs without split-K
+  SplitScope sp(split, (hipStream_t)stream);
   ConvProblem p = problem(*w, in0, in1, out, n_img, Hin, Win, in_up);
   p.add = add;
   for (int i = 0; i < reps; ++i) SF_TRY(run1(p, EPI_AFFINE, (hipStream_t)stream));
   return SF_OK;
 }
 
-size_t sf_gru_cell_ws_bytes(int C, int n_img, int H, int W) {
-  return (al((size_t)n_img * H * W * 2 * C) + al((size_t)n_img * H * W * C)) * sizeof(float);
-}
+size_t sf_gru_cell_ws_bytes(int C, int n_img, int H, int W) { return layout_bytes<GruBufs>(C, (size_t)n_img * H * W); }
 static int gru_cell_entry(const sf_gru_w* w, const float* x, const float* s, float* out, int n_img, int H, int W, float* ws, size_t ws_bytes,
                           void* stream, int ode_derivative) {
   if (!w || !x || !s || !out || !valid_w(w->gates) || !valid_w(w->cand)) return SF_ERR_INVALID;
-  Arena A(ws, ws_bytes);
-  float* g = A.take((size_t)n_img * H * W * 2 * w->cand.cout);
-  float* rs = A.take((size_t)n_img * H * W * w->cand.cout);
-  if (!A.ok()) return SF_ERR_WORKSPACE;
-  return gru_cell(*w, x, s, out, g, rs, n_img, H, W, (hipStream_t)stream, ode_derivative);
+  GruBufs b;
+  if (!carve(b, ws, ws_bytes, w->cand.cout, (size_t)n_img * H * W)) return SF_ERR_WORKSPACE;
+  return gru_cell(*w, x, s, out, b.g, b.rs, n_img, H, W, (hipStream_t)stream, ode_derivative);
 }
 int sf_gru_cell_fwd(const sf_gru_w* w, const float* x, const float* s, float* out, int n_img, int H, int W, float* ws,
                     size_t ws_bytes, void* stream) {
@@ -576,9 +577,7 @@ int sf_gru_ode_cell_fwd(const sf_gru_w* w, const float* x, const float* s, float
   return gru_cell_entry(w, x, s, out, n_img, H, W, ws, ws_bytes, stream, 1);
 }
 
-size_t sf_spatial_gru_ws_bytes(int C, int n_img, int H, int W) {
-  return (al((size_t)n_img * H * W * 2 * C) + 3 * al((size_t)n_img * H * W * C)) * sizeof(float);
-}
+size_t sf_spatial_gru_ws_bytes(int C, int n_img, int H, int W) { return layout_bytes<SpatialGruBufs>(C, (size_t)n_img * H * W); }
 int sf_spatial_gru_fwd(const sf_gru_w* w, const float* x, const float* state0, float* out, int T, int n_img, int H,
                        int W, float* ws, size_t ws_bytes, void* stream) {
   if (!w || !x || !state0 || !out || !valid_w(w->gates) || !valid_w(w->cand)) return SF_ERR_INVALID;
@@ -586,18 +585,14 @@ int sf_spatial_gru_fwd(const sf_gru_w* w, const float* x, const float* state0, f
   if (has_dec && !valid_w(w->decoder)) return SF_ERR_INVALID;
   const int C = w->cand.cout, Cx = w->gates.c0;
   const size_t P = (size_t)n_img * H * W;
-  Arena A(ws, ws_bytes);
-  float* g = A.take(P * 2 * C);
-  float* sa = A.take(P * C);
-  float* sb = A.take(P * C);
-  float* rs = A.take(P * C);
-  if (!A.ok()) return SF_ERR_WORKSPACE;
+  SpatialGruBufs b;
+  if (!carve(b, ws, ws_bytes, C, P)) return SF_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   const float* cur = state0;
   for (int t = 0; t < T; ++t) {   // temporal.py:35-39
     // without a decoder (BEVerse SpatialGRU, basic_modules.py:225-284) the states ARE the output
-    float* nxt = has_dec ? ((t & 1) ? sb : sa) : out + t * P * C;
-    SF_TRY(gru_cell(*w, x + t * P * Cx, cur, nxt, g, rs, n_img, H, W, st));
+    float* nxt = has_dec ? ((t & 1) ? b.sb : b.sa) : out + t * P * C;
+    SF_TRY(gru_cell(*w, x + t * P * Cx, cur, nxt, b.g, b.rs, n_img, H, W, st));
     if (has_dec)
       SF_TRY(run1(problem(w->decoder, nxt, nullptr, out + t * P * w->decoder.cout, n_img, H, W), EPI_AFFINE, st));
     cur = nxt;
@@ -605,17 +600,16 @@ int sf_spatial_gru_fwd(const sf_gru_w* w, const float* x, const float* state0, f
   return SF_OK;
 }
 
-size_t sf_dual_cell_ws_bytes(int C, int n_img, int H, int W) {
-  return (dual_ws_floats(C, n_img * H * W) + SPLIT_WS_FLOATS) * sizeof(float);
-}
+size_t sf_dual_cell_ws_bytes(int C, int n_img, int H, int W) { return layout_bytes<WithSplit<CellBufs>>(C, (size_t)n_img * H * W); }
 int sf_dual_cell_fwd(const sf_dual_w* w, const float* x, const float* s, float* out, int derivative, const float* base,
                      const float* coef, float* out2, int acc2, int n_img, int H, int W, float* ws, size_t ws_bytes,
                      void* stream) {
   if (!w || !x || !s || !out || w->C <= 0 || (w->C % 8) || n_img < 1) return SF_ERR_INVALID;
   if (w->C > 128) return SF_ERR_UNSUPPORTED;
-  Arena A(ws, ws_bytes);
-  SplitScope sp(A, (hipStream_t)stream);
-  return dual_cell(*w, x, s, out, derivative, base, coef, 0, out2, acc2, n_img, H, W, A, (hipStream_t)stream);
+  WithSplit<CellBufs> L;
+  if (!carve(L, ws, ws_bytes, w->C, (size_t)n_img * H * W)) return SF_ERR_WORKSPACE;
+  SplitScope sp(L.split, (hipStream_t)stream);
+  return dual_cell(*w, x, s, out, derivative, base, coef, 0, out2, acc2, n_img, H, W, L.bufs, (hipStream_t)stream);
 }
 
 // trusting gate + mix of two given branch states (the tail of both dual cells; the recurrent Dual_GRU calls it per step)
@@ -624,34 +618,38 @@ int sf_trust_mix_fwd(const sf_dual_w* w, const float* r1, const float* r2, const
   if (!w || !r1 || !r2 || !out || w->C <= 0 || (w->C % 8) || n_img < 1) return SF_ERR_INVALID;
   if (derivative && (!s || !coef)) return SF_ERR_INVALID;
   if (w->C > 128) return SF_ERR_UNSUPPORTED;
-  Arena A(ws, ws_bytes);
-  SplitScope sp(A, (hipStream_t)stream);
-  CellBufs b;
-  if (!b.take(A, w->C, n_img * H * W)) return SF_ERR_WORKSPACE;
+  WithSplit<CellBufs> L;
+  if (!carve(L, ws, ws_bytes, w->C, (size_t)n_img * H * W)) return SF_ERR_WORKSPACE;
+  SplitScope sp(L.split, (hipStream_t)stream);
+  CellBufs& b = L.bufs;
   b.h1 = const_cast<float*>(r1);      // read only from here on
   b.r2 = const_cast<float*>(r2);
   return cell_tail(*w, s ? s : r1, out, derivative, base, coef, 0, nullptr, 0, b, n_img, H, W, (hipStream_t)stream);
 }
 
 // Bottleblock (convolutions.py:348-380) on cat[x0, x1]: out = layers(x) + (projection(x) | x)
-size_t sf_bottleblock_ws_bytes(int cin, int cout, int n_img, int H, int W) {
-  const size_t P = (size_t)n_img * H * W;
-  return (2 * al(P * (size_t)(cin / 2 > 0 ? cin / 2 : 1)) + al(P * (size_t)cout) + SPLIT_WS_FLOATS) * sizeof(float);
-}
+// mid = cin / 2 channels after the 7x7 and the 1x1 layer; the projection's buffer is carved whether or not the block has one
+struct BottleBufs {
+  float *t1, *t2, *sk;
+  void take(Arena& A, int cin, int cout, size_t P) {
+    const size_t mid = cin / 2 > 0 ? cin / 2 : 1;
+    t1 = A.take(P * mid); t2 = A.take(P * mid); sk = A.take(P * cout);
+  }
+};
+size_t sf_bottleblock_ws_bytes(int cin, int cout, int n_img, int H, int W) { return layout_bytes<WithSplit<BottleBufs>>(cin, cout, (size_t)n_img * H * W); }
 int sf_bottleblock_fwd(const sf_bottle_w* w, const float* x0, const float* x1, float* out, int n_img, int H, int W, float* ws,
                        size_t ws_bytes, void* stream) {
   if (!w || !x0 || !out || n_img < 1 || !valid_w(w->c7) || !valid_w(w->c1) || !valid_w(w->c3)) return SF_ERR_INVALID;
   const bool has_proj = w->proj.w != nullptr;
   if (!has_proj && (x1 || w->c7.c1 != 0 || w->c3.cout != w->c7.c0)) return SF_ERR_INVALID;      // the residual is x itself
   if (w->c7.cout_pad > 128 || w->c3.cout_pad > 128) return SF_ERR_UNSUPPORTED;                    // LayerNorm epilogue: all channels of a pixel in one wave
+  const int cin = w->c7.c0 + w->c7.c1, cout = w->c3.cout;      // the size query's arguments
+  if (w->c7.cout > cin / 2 || w->c1.cout > cin / 2 || (has_proj && w->proj.cout != cout)) return SF_ERR_INVALID;
   hipStream_t st = (hipStream_t)stream;
-  Arena A(ws, ws_bytes);
-  SplitScope sp(A, st);
-  const size_t P = (size_t)n_img * H * W;
-  float* t1 = A.take(P * w->c7.cout);
-  float* t2 = A.take(P * w->c1.cout);
-  float* sk = has_proj ? A.take(P * w->proj.cout) : nullptr;
-  if (!A.ok()) return SF_ERR_WORKSPACE;
+  WithSplit<BottleBufs> L;
+  if (!carve(L, ws, ws_bytes, cin, cout, (size_t)n_img * H * W)) return SF_ERR_WORKSPACE;
+  SplitScope sp(L.split, st);
+  const auto [t1, t2, sk] = L.bufs;
   ConvProblem ps[2];
   ps[0] = problem(w->c7, x0, x1, t1, n_img, H, W); ps[0].mode = 1;        // 7x7 + LN + GELU
   ConvProblem q = problem(w->c1, t1, nullptr, t2, n_img, H, W); q.mode = 1;
@@ -665,34 +663,29 @@ int sf_bottleblock_fwd(const sf_bottle_w* w, const float* x0, const float* x1, f
   return run1(f, EPI_LNG, st);
 }
 
-size_t sf_infer_state_ws_bytes(int C, int n_img, int H, int W) {
-  return (infer_ws_floats(C, n_img * H * W) + SPLIT_WS_FLOATS) * sizeof(float);
-}
+size_t sf_infer_state_ws_bytes(int C, int n_img, int H, int W) { return layout_bytes<WithSplit<InferBufs>>(C, n_img, (size_t)H * W); }
 int sf_infer_state_fwd(const sf_pmodel_w* w, const float* s, const float* eps, float* p_out, float* q_out, int n_img,
                        int H, int W, float* ws, size_t ws_bytes, void* stream) {
   if (!w || !s || !eps || !p_out || w->C <= 0 || (w->C % 8) || n_img < 1) return SF_ERR_INVALID;
-  Arena A(ws, ws_bytes);
-  SplitScope sp(A, (hipStream_t)stream);
-  return infer_state(*w, s, eps, p_out, q_out, n_img, H, W, A, (hipStream_t)stream);
+  WithSplit<InferBufs> L;
+  if (!carve(L, ws, ws_bytes, w->C, n_img, (size_t)H * W)) return SF_ERR_WORKSPACE;
+  SplitScope sp(L.split, (hipStream_t)stream);
+  return infer_state(*w, s, eps, p_out, q_out, n_img, H, W, L.bufs, (hipStream_t)stream);
 }
 
-size_t sf_ode_step_ws_bytes(int C, int n_img, int H, int W) {
-  const int P = n_img * H * W;
-  return (ode_step_ws_floats(C, P) + al((size_t)P * C) + SPLIT_WS_FLOATS) * sizeof(float);
-}
+size_t sf_ode_step_ws_bytes(int C, int n_img, int H, int W) { return layout_bytes<StepLayout>(C, n_img, (size_t)H * W); }
 int sf_ode_step_fwd(const sf_dual_w* gru_c, const sf_pmodel_w* pm, int solver, int impute, const float* state_in,
                     const float* p_in, const float* coef, const float* eps, float* state_out, float* p_out, int n_img,
                     int H, int W, float* ws, size_t ws_bytes, void* stream) {
   if (!gru_c || !pm || !state_in || !p_in || !coef || !eps || !state_out || !p_out || n_img < 1) return SF_ERR_INVALID;
   if (gru_c->C > 128 || (gru_c->C % 8)) return SF_ERR_UNSUPPORTED;
-  Arena A(ws, ws_bytes);
+  if (solver != SF_SOLVER_EULER && solver != SF_SOLVER_MIDPOINT && solver != SF_SOLVER_RK4) return SF_ERR_INVALID;
   hipStream_t st = (hipStream_t)stream;
-  SplitScope sp(A, st);
-  const size_t PC = (size_t)n_img * H * W * gru_c->C;
-  float* zeros = A.take(PC);
-  if (!A.ok()) return SF_ERR_WORKSPACE;
-  if (!impute) SF_HIP(zero_fill(zeros, al(PC) * sizeof(float), st));
-  return ode_step(*gru_c, *pm, solver, impute, state_in, p_in, coef, 0, eps, state_out, p_out, zeros, n_img, H, W, A, st);
+  StepLayout L;
+  if (!carve(L, ws, ws_bytes, gru_c->C, n_img, (size_t)H * W)) return SF_ERR_WORKSPACE;
+  SplitScope sp(L.split, st);
+  if (!impute) SF_HIP(zero_fill(L.zeros, al((size_t)n_img * H * W * gru_c->C) * sizeof(float), st));
+  return ode_step(*gru_c, *pm, solver, impute, state_in, p_in, coef, 0, eps, state_out, p_out, L, n_img, H, W, st);
 }
 
 // ---- rollout as a list of stages -----------------------------------------------------------------------------------------
@@ -710,29 +703,41 @@ struct ResumeCarry {
   bool allow_flow = true;            // false: launch-per-layer form whatever SF_PERSIST / sf_set_flow_mode say
   int draw0 = 0;                     // number of the segment's first draw: eps holds the segment's own draws, Philox is keyed by the number
 };
-size_t carry_floats(size_t PC) { return 2 * al(2 * PC) + 2 * al(PC); }
-Carry carry_view(float* base, size_t PC) {
-  Carry c;
-  c.g2 = base; c.g1s = base + al(2 * PC); c.rs2 = base + 2 * al(2 * PC); c.h2 = c.rs2 + al(PC);
-  return c;
-}
+// sf_nnfo_rollout_carry_bytes of caller memory
+struct CarryView : Carry { void take(Arena& A, size_t PC) { g2 = A.take(2 * PC); g1s = A.take(2 * PC); rs2 = A.take(PC); h2 = A.take(PC); } };
+Carry carry_view(float* base, size_t PC) { CarryView c; carve(c, base, ~size_t(0), PC); return c; }
 
-size_t rollout_ws_floats(int C, int P) {
-  const size_t cellw = dual_ws_floats(C, P), inf = infer_ws_floats(C, P);
-  return (cellw > inf ? cellw : inf) + 15 * al((size_t)P * C) + SPLIT_WS_FLOATS + flow_ws_floats() + 256;
-}
+// The workspace of a rollout: the state / input pairs the ops alternate between, the solver stages, the carried branch 2 (written during
+// one stage's infer_state, read by the next cell: outside the overlay), the persistent flow's tables under the flow mode in force, and
+// every stage's cell scratch overlaid with the infer_state's behind it
+struct RolloutLayout {
+  SplitBufs split;
+  float *zeros, *sbuf[2], *pbuf[2];
+  StageBufs sb;
+  Carry cb;
+  FlowBufs flow;
+  CellBufs cell;
+  InferBufs inf;
+  void take(Arena& A, int C, int B, size_t HW) {
+    const size_t PC = B * HW * C;
+    split.take(A);
+    zeros = A.take(PC);
+    sbuf[0] = A.take(PC); sbuf[1] = A.take(PC); pbuf[0] = A.take(PC); pbuf[1] = A.take(PC);
+    sb.take(A, PC);
+    cb.g2 = A.take(2 * PC); cb.rs2 = A.take(PC); cb.h2 = A.take(PC); cb.g1s = A.take(2 * PC);
+    flow.take(A);
+    A.larger_of([&] { cell.take(A, C, B * HW); }, [&] { inf.take(A, C, B, HW); });
+  }
+};
 
 int run_stages(const std::vector<Stage>& stages, const sf_pmodel_w& pm, const float* eps, const unsigned long long* philox, int coef_stride,
-               const int32_t* sel_nops, int n_targets, float* out_states, int B, int H, int W, Arena& A, hipStream_t st, const unsigned** flow_err,
-               const ResumeCarry& rc = ResumeCarry()) {
+               const int32_t* sel_nops, int n_targets, float* out_states, int B, int H, int W, const RolloutLayout& L, hipStream_t st,
+               const unsigned** flow_err, const ResumeCarry& rc = ResumeCarry()) {
   const size_t PC = (size_t)B * H * W * pm.C;
-  // buffers of the carried branch 2 (outside the per-stage arenas: written during one stage's infer_state, read by the next cell)
-  Carry cb, cnow;
-  cb.g2 = A.take(2 * PC); cb.rs2 = A.take(PC); cb.h2 = A.take(PC); cb.g1s = A.take(2 * PC);
-  cnow = cb;
+  const Carry& cb = L.cb;
+  Carry cnow = cb;
   // one latent: the launch groups of the stages become phases of ONE persistent flow launch (conv_sp.hip: sp_flow_kernel)
-  FlowScope flow(rc.allow_flow && B == 1 && (long)B * H * W < SP_MAX_P && tune().sp, A, st);      // for the duration of this function only
-  if (!A.ok()) return SF_ERR_WORKSPACE;
+  FlowScope flow(rc.allow_flow && B == 1 && (long)B * H * W < SP_MAX_P && tune().sp, L.flow, st);      // for the duration of this function only
   SF_TRY(flow.status);
   *flow_err = flow.err();
   bool carried = false;
@@ -745,8 +750,7 @@ int run_stages(const std::vector<Stage>& stages, const sf_pmodel_w& pm, const fl
   }
   for (size_t j = 0; j < stages.size(); ++j) {
     const Stage& g = stages[j];
-    Arena Ac = A;
-    SF_TRY(dual_cell(*g.w, g.x, g.s, g.out, g.derivative, g.base, g.coef, coef_stride, g.out2, g.acc2, B, H, W, Ac, st, carried ? &cnow : nullptr));
+    SF_TRY(dual_cell(*g.w, g.x, g.s, g.out, g.derivative, g.base, g.coef, coef_stride, g.out2, g.acc2, B, H, W, L.cell, st, carried ? &cnow : nullptr));
     carried = false;
     if (g.op_end >= 0)
       for (int t = 0; t < n_targets; ++t)
@@ -754,7 +758,6 @@ int run_stages(const std::vector<Stage>& stages, const sf_pmodel_w& pm, const fl
           SF_TRY(flow_copy_out(g.out, out_states + (size_t)t * PC, PC, st));
         }
     if (g.infer_after) {
-      Arena Ai = A;
       Side sd = {};
       const Stage* nx = j + 1 < stages.size() ? &stages[j + 1] : nullptr;
       // the last infer_state of a segment that hands its boundary on (rc.out): the side problems of the ODE cell that follows it
@@ -765,15 +768,15 @@ int run_stages(const std::vector<Stage>& stages, const sf_pmodel_w& pm, const fl
         cnow = cb;
         if (sd.n < 3) cnow.g1s = nullptr;
       }
-      SF_TRY(infer_state(pm, g.out, eps ? eps + (size_t)(g.draw - rc.draw0) * PC : nullptr, g.p_out, nullptr, B, H, W, Ai, st, philox, g.draw, pipe ? &sd : nullptr));
+      SF_TRY(infer_state(pm, g.out, eps ? eps + (size_t)(g.draw - rc.draw0) * PC : nullptr, g.p_out, nullptr, B, H, W, L.inf, st, philox, g.draw, pipe ? &sd : nullptr));
       carried = pipe && nx;
     }
   }
   return seg_flush();
 }
 
-size_t sf_nnfo_rollout_ws_bytes(int C, int n_img, int H, int W) { return rollout_ws_floats(C, n_img * H * W) * sizeof(float); }
-size_t sf_nnfo_rollout_carry_bytes(int C, int n_img, int H, int W) { return carry_floats((size_t)n_img * H * W * C) * sizeof(float); }
+size_t sf_nnfo_rollout_ws_bytes(int C, int n_img, int H, int W) { return layout_bytes<RolloutLayout>(C, n_img, (size_t)H * W); }
+size_t sf_nnfo_rollout_carry_bytes(int C, int n_img, int H, int W) { return layout_bytes<CarryView>((size_t)n_img * H * W * C); }
 struct SegmentIO {      // what only a resumed segment is given (sfnative.h: sf_nnfo_rollout_resume_fwd)
   const float* state_in = nullptr; const float* p_in = nullptr; const float* carry_in = nullptr; int draw_base = 0;
   float* p_out = nullptr; float* carry_out = nullptr;
@@ -793,20 +796,16 @@ static int rollout_core(const sf_dual_w* gru_c, const sf_dual_w* gru_obs, const 
   const int C = gru_c->C, B = n_img;
   const size_t PC = (size_t)B * H * W * C;
   const bool resumed = state_in || p_in || p_out;
-  Arena A(ws, ws_bytes);
-  SplitScope sp(A, (hipStream_t)stream);
-  float* zeros = A.take(PC);
-  float* sbuf[2] = {A.take(PC), A.take(PC)};
-  float* pbuf[2] = {A.take(PC), A.take(PC)};
-  const StageBufs sb = {A.take(PC), A.take(PC), A.take(PC), A.take(PC)};       // solver stages (midpoint / RK4)
-  if (!A.ok()) return SF_ERR_WORKSPACE;
+  RolloutLayout L;
+  if (!carve(L, ws, ws_bytes, C, B, (size_t)H * W)) return SF_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  SF_HIP(zero_fill(zeros, al(PC) * sizeof(float), st));
-  if (!state_in) SF_HIP(zero_fill(sbuf[0], al(PC) * sizeof(float), st));   // state = zeros  (temporal_ode_bayes.py:507)
-  if (!p_in) SF_HIP(zero_fill(pbuf[0], al(PC) * sizeof(float), st));       // input: overwritten by the first jump (:565,574)
-  // the carried state / input are read where they lie (the first op writes sbuf[1] / pbuf[1]); nothing below writes through s_cur / p_cur
-  const float* s_cur = state_in ? state_in : sbuf[0];
-  const float* p_cur = p_in ? p_in : pbuf[0];
+  SplitScope sp(L.split, st);
+  SF_HIP(zero_fill(L.zeros, al(PC) * sizeof(float), st));
+  if (!state_in) SF_HIP(zero_fill(L.sbuf[0], al(PC) * sizeof(float), st));   // state = zeros  (temporal_ode_bayes.py:507)
+  if (!p_in) SF_HIP(zero_fill(L.pbuf[0], al(PC) * sizeof(float), st));       // input: overwritten by the first jump (:565,574)
+  // the carried state / input are read where they lie (the first op writes L.sbuf[1] / L.pbuf[1]); nothing below writes through s_cur / p_cur
+  const float* s_cur = state_in ? state_in : L.sbuf[0];
+  const float* p_cur = p_in ? p_in : L.pbuf[0];
   int si = 0, pi = 0, draw = draw_base;
   const int cstride = coef_per_image ? SF_COEF_STRIDE : 0;
   const size_t step_stride = (size_t)SF_COEF_STRIDE * (coef_per_image ? B : 1);
@@ -819,11 +818,11 @@ static int rollout_core(const sf_dual_w* gru_c, const sf_dual_w* gru_obs, const 
     const bool next_is_step = (i + 1 < n_ops) && ops[2 * (i + 1)] == SF_OP_STEP;
     const bool last = i + 1 == n_ops;
     const bool need_p = (impute && next_is_step) || (last && p_out);
-    const float* s = s_cur; float* s2 = sbuf[si ^ 1];
-    const float* p = p_cur; float* p2 = (last && p_out) ? p_out : pbuf[pi ^ 1];
+    const float* s = s_cur; float* s2 = L.sbuf[si ^ 1];
+    const float* p = p_cur; float* p2 = (last && p_out) ? p_out : L.pbuf[pi ^ 1];
     if (kind == SF_OP_JUMP) {   // :562-574
       // (the jump's imputed input replaces the current one in place; p_in itself is never written)
-      float* pj = (last && p_out) ? p_out : pbuf[pi];
+      float* pj = (last && p_out) ? p_out : L.pbuf[pi];
       if (!hx_obs) return SF_ERR_INVALID;      // (NULL is fine for a segment without jumps)
       stages.push_back({.w = gru_obs, .x = hx_obs + (size_t)arg * PC, .s = s, .out = s2, .derivative = 0, .infer_after = need_p, .draw = draw, .p_out = pj, .op_end = i});
       draw += 1;
@@ -832,7 +831,7 @@ static int rollout_core(const sf_dual_w* gru_c, const sf_dual_w* gru_obs, const 
       if (need_p) p_cur = pj;
     } else if (kind == SF_OP_STEP) {
       if (!coef) return SF_ERR_INVALID;
-      draw += step_stages(solver, gru_c, impute ? p : zeros, s, s2, p2, need_p, coef + (size_t)arg * step_stride, draw, i, sb, stages);
+      draw += step_stages(solver, gru_c, impute ? p : L.zeros, s, s2, p2, need_p, coef + (size_t)arg * step_stride, draw, i, L.sb, stages);
       si ^= 1;
       pi ^= 1;
       s_cur = s2;
@@ -852,7 +851,7 @@ static int rollout_core(const sf_dual_w* gru_c, const sf_dual_w* gru_obs, const 
   rc.next_w = gru_c;
   rc.draw0 = draw_base;
   rc.allow_flow = !resumed;      // a resumed segment always runs in the launch-per-layer form (sfnative.h)
-  SF_TRY(run_stages(stages, *pm, eps, philox, cstride, sel_nops, n_targets, out_states, B, H, W, A, st, &flow_err, rc));
+  SF_TRY(run_stages(stages, *pm, eps, philox, cstride, sel_nops, n_targets, out_states, B, H, W, L, st, &flow_err, rc));
   if (final_state && final_state != s_cur) SF_HIP(copy_floats(s_cur, final_state, PC, st));
   if (p_out && n_ops == 0 && p_out != p_cur) SF_HIP(copy_floats(p_cur, p_out, PC, st));
   return flow_close(flow_err, out_states, (size_t)n_targets * PC, final_state, final_state ? PC : 0, st);
@@ -897,59 +896,60 @@ int sf_nnfo_rollout_philox_fwd(const sf_dual_w* gru_c, const sf_dual_w* gru_obs,
 int sf_infer_state_philox_fwd(const sf_pmodel_w* w, const float* s, const uint64_t* philox_state, int draw, float* p_out, float* q_out,
                               int n_img, int H, int W, float* ws, size_t ws_bytes, void* stream) {
   if (!w || !s || !philox_state || !p_out || w->C <= 0 || (w->C % 8) || n_img < 1 || draw < 0) return SF_ERR_INVALID;
-  Arena A(ws, ws_bytes);
-  SplitScope sp(A, (hipStream_t)stream);
-  return infer_state(*w, s, nullptr, p_out, q_out, n_img, H, W, A, (hipStream_t)stream, reinterpret_cast<const unsigned long long*>(philox_state), draw);
+  WithSplit<InferBufs> L;
+  if (!carve(L, ws, ws_bytes, w->C, n_img, (size_t)H * W)) return SF_ERR_WORKSPACE;
+  SplitScope sp(L.split, (hipStream_t)stream);
+  return infer_state(*w, s, nullptr, p_out, q_out, n_img, H, W, L.bufs, (hipStream_t)stream, reinterpret_cast<const unsigned long long*>(philox_state), draw);
 }
 
 // ---- SmallEncoder / SmallDecoder ------------------------------------------------------------------
-size_t sf_small_encoder_ws_bytes(int C, int F, int n, int H, int W) {
-  size_t P0 = (size_t)n * H * W;
-  int Cm = C > F ? C : F;
-  // level 0: t (C), pr (F), o0 (F), pooled (F@1/4); level 1 at P0/4: t (F), pr (2F), o (2F), pooled@1/16;
-  // level 2 at P0/16: t (4F)... be generous: 4 buffers of the largest tensor per level
-  size_t lvl0 = 3 * al(P0 * Cm), lvl1 = 4 * al(P0 / 4 * 2 * F + 64), lvl2 = 6 * al(P0 / 16 * 4 * F + 64);
-  return (lvl0 + lvl1 + lvl2) * sizeof(float);
-}
+// level 0 at H x W: conv1's output, the projection, the block's output (max(C, F) channels each); level 1 at H/2 x W/2: the pooled
+// input (F), t (F), pr and o (2F); level 2 at H/4 x W/4: the pooled input (2F), t, pr and three outputs (4F)
+struct EncoderBufs {
+  float *t0, *pr0, *o0, *q1, *t1, *pr1, *o1, *q2, *t2, *pr2, *o2, *o3, *o4;
+  void take(Arena& A, int C, int F, int n, int H, int W) {
+    const size_t P0 = (size_t)n * H * W, P1 = (size_t)n * (H / 2) * (W / 2), P2 = (size_t)n * (H / 2 / 2) * (W / 2 / 2);
+    const int Cm = C > F ? C : F;
+    t0 = A.take(P0 * Cm); pr0 = A.take(P0 * Cm); o0 = A.take(P0 * Cm);
+    q1 = A.take(P1 * F); t1 = A.take(P1 * F); pr1 = A.take(P1 * 2 * F); o1 = A.take(P1 * 2 * F);
+    q2 = A.take(P2 * 2 * F); t2 = A.take(P2 * 4 * F); pr2 = A.take(P2 * 4 * F);
+    o2 = A.take(P2 * 4 * F); o3 = A.take(P2 * 4 * F); o4 = A.take(P2 * 4 * F);
+  }
+};
+size_t sf_small_encoder_ws_bytes(int C, int F, int n, int H, int W) { return layout_bytes<EncoderBufs>(C, F, n, H, W); }
 int sf_small_encoder_fwd(const sf_encoder_w* w, const float* x, float* out, int n, int H, int W, float* ws,
                          size_t ws_bytes, void* stream) {
   if (!w || !x || !out) return SF_ERR_INVALID;
-  const int C = w->C, F = w->F;
   hipStream_t st = (hipStream_t)stream;
-  Arena A(ws, ws_bytes);
-  const size_t P0 = (size_t)n * H * W;
   const int H1 = H / 2, W1 = W / 2, H2 = H1 / 2, W2 = W1 / 2;
-  const size_t P1 = (size_t)n * H1 * W1, P2 = (size_t)n * H2 * W2;
-  const int Cm = C > F ? C : F;
-  float* t0 = A.take(P0 * Cm); float* pr0 = A.take(P0 * Cm); float* o0 = A.take(P0 * Cm);
-  float* q1 = A.take(P1 * F); float* t1 = A.take(P1 * F); float* pr1 = A.take(P1 * 2 * F); float* o1 = A.take(P1 * 2 * F);
-  float* q2 = A.take(P2 * 2 * F); float* t2 = A.take(P2 * 4 * F); float* pr2 = A.take(P2 * 4 * F);
-  float* o2 = A.take(P2 * 4 * F); float* o3 = A.take(P2 * 4 * F); float* o4 = A.take(P2 * 4 * F);
-  if (!A.ok()) return SF_ERR_WORKSPACE;
-  SF_TRY(res_block(w->blocks[0], x, o0, t0, pr0, n, H, W, 0, st, q1));        // res_models.py:101-105: block, MaxPool2d(2)
-  SF_TRY(res_block(w->blocks[1], q1, o1, t1, pr1, n, H1, W1, 0, st, q2));
-  SF_TRY(res_block(w->blocks[2], q2, o2, t2, pr2, n, H2, W2, 0, st));
-  SF_TRY(res_block(w->blocks[3], o2, o3, t2, pr2, n, H2, W2, 0, st));
-  SF_TRY(res_block(w->blocks[4], o3, o4, t2, pr2, n, H2, W2, 0, st));
-  return run1(problem(w->last, o4, nullptr, out, n, H2, W2), EPI_AFFINE, st);   // :106 conv+BN+tanh
+  EncoderBufs b;
+  if (!carve(b, ws, ws_bytes, w->C, w->F, n, H, W)) return SF_ERR_WORKSPACE;
+  SF_TRY(res_block(w->blocks[0], x, b.o0, b.t0, b.pr0, n, H, W, 0, st, b.q1));        // res_models.py:101-105: block, MaxPool2d(2)
+  SF_TRY(res_block(w->blocks[1], b.q1, b.o1, b.t1, b.pr1, n, H1, W1, 0, st, b.q2));
+  SF_TRY(res_block(w->blocks[2], b.q2, b.o2, b.t2, b.pr2, n, H2, W2, 0, st));
+  SF_TRY(res_block(w->blocks[3], b.o2, b.o3, b.t2, b.pr2, n, H2, W2, 0, st));
+  SF_TRY(res_block(w->blocks[4], b.o3, b.o4, b.t2, b.pr2, n, H2, W2, 0, st));
+  return run1(problem(w->last, b.o4, nullptr, out, n, H2, W2), EPI_AFFINE, st);   // :106 conv+BN+tanh
 }
 
-size_t sf_small_decoder_ws_bytes(int C, int F, int n, int h, int w) {
-  size_t P = (size_t)n * h * w;
-  return (4 * al(P * 4 * F) + 3 * al(4 * P * 2 * F) + 4 * al(16 * P * (size_t)(F > C ? F : C))) * sizeof(float);
-}
+struct DecoderBufs {      // four tensors at h x w (4F channels), three at 2h x 2w (2F), four at 4h x 4w (max(F, C))
+  float *a0, *a1, *a2, *a3, *b0, *b1, *b2, *c0, *c1, *c2, *c3;
+  void take(Arena& A, int C, int F, size_t P) {
+    const int Cm = F > C ? F : C;
+    a0 = A.take(P * 4 * F); a1 = A.take(P * 4 * F); a2 = A.take(P * 4 * F); a3 = A.take(P * 4 * F);
+    b0 = A.take(4 * P * 2 * F); b1 = A.take(4 * P * 2 * F); b2 = A.take(4 * P * 2 * F);
+    c0 = A.take(16 * P * Cm); c1 = A.take(16 * P * Cm); c2 = A.take(16 * P * Cm); c3 = A.take(16 * P * Cm);
+  }
+};
+size_t sf_small_decoder_ws_bytes(int C, int F, int n, int h, int w) { return layout_bytes<DecoderBufs>(C, F, (size_t)n * h * w); }
 int sf_small_decoder_fwd(const sf_decoder_w* w, const float* z, float* out, int n, int h, int wd, float* ws,
                          size_t ws_bytes, void* stream) {
   if (!w || !z || !out) return SF_ERR_INVALID;
-  const int F = w->F, C = w->C;
-  const int Cm = F > C ? F : C;
+  const int F = w->F;
   hipStream_t st = (hipStream_t)stream;
-  Arena A(ws, ws_bytes);
-  const size_t P = (size_t)n * h * wd;
-  float* a0 = A.take(P * 4 * F); float* a1 = A.take(P * 4 * F); float* a2 = A.take(P * 4 * F); float* a3 = A.take(P * 4 * F);
-  float* b0 = A.take(4 * P * 2 * F); float* b1 = A.take(4 * P * 2 * F); float* b2 = A.take(4 * P * 2 * F);
-  float* c0 = A.take(16 * P * Cm); float* c1 = A.take(16 * P * Cm); float* c2 = A.take(16 * P * Cm); float* c3 = A.take(16 * P * Cm);
-  if (!A.ok()) return SF_ERR_WORKSPACE;
+  DecoderBufs b;
+  if (!carve(b, ws, ws_bytes, w->C, F, (size_t)n * h * wd)) return SF_ERR_WORKSPACE;
+  const auto [a0, a1, a2, a3, b0, b1, b2, c0, c1, c2, c3] = b;
   SF_TRY(run1(problem(w->first, z, nullptr, a0, n, h, wd), EPI_AFFINE, st));           // res_models.py:136
   SF_TRY(res_block(w->blocks[0], a0, a1, a2, a3, n, h, wd, 0, st));                     // 4F -> 2F
   SF_TRY(res_block(w->blocks[1], a1, a0, a2, a3, n, h, wd, 0, st));                     // 2F -> 2F
@@ -969,10 +969,13 @@ int sf_small_decoder_fwd(const sf_decoder_w* w, const float* z, float* out, int 
 }
 
 // ---- Bottleneck / distribution heads (secondary, BEVerse-compatible classes) ------------------------
-size_t sf_bottleneck_ws_bytes(int Cin, int Cout, int n, int H, int W) {
-  size_t P = (size_t)n * H * W;
-  return (2 * al(P * (Cin / 2)) + al(P * Cin) + al(P * Cout)) * sizeof(float);
-}
+// the two hidden tensors (Cin / 2 channels), the pooled input and the projection: the last three at the input's size also where the
+// block downsamples (the size query is not told)
+struct BottleneckBufs {
+  float *t1, *t2, *xp, *pr;
+  void take(Arena& A, int Cin, int Cout, size_t P) { t1 = A.take(P * (Cin / 2)); t2 = A.take(P * (Cin / 2)); xp = A.take(P * Cin); pr = A.take(P * Cout); }
+};
+size_t sf_bottleneck_ws_bytes(int Cin, int Cout, int n, int H, int W) { return layout_bytes<BottleneckBufs>(Cin, Cout, (size_t)n * H * W); }
 // Bottleneck.forward (streamingflow/layers/convolutions.py:65-172, beverse basic_modules.py:68-178):
 // 1x1 -> BN,ReLU -> 3x3 (stride 2 if downsample) -> BN,ReLU -> 1x1 -> BN,ReLU, + skip (identity, or
 // [zero-pad + 2x2 max-pool] + 1x1 + BN).  out: [n][Ho][Wo][Cout], Ho = ceil(H/2) when downsampling.
@@ -980,15 +983,12 @@ int sf_bottleneck_fwd(const sf_bottleneck_w* w, const float* x, float* out, int 
                       size_t ws_bytes, void* stream) {
   if (!w || !x || !out || !valid_w(w->down) || !valid_w(w->conv) || !valid_w(w->up)) return SF_ERR_INVALID;
   hipStream_t st = (hipStream_t)stream;
-  Arena A(ws, ws_bytes);
   const int Cin = w->down.c0, Cm = w->down.cout, Cout = w->up.cout;
   const int Ho = w->downsample ? (H + 1) / 2 : H, Wo = w->downsample ? (W + 1) / 2 : W;
-  const size_t P = (size_t)n * H * W, Po = (size_t)n * Ho * Wo;
-  float* t1 = A.take(P * Cm);
-  float* t2 = A.take(Po * Cm);
-  float* xp = A.take(Po * Cin);
-  float* pr = A.take(Po * Cout);
-  if (!A.ok()) return SF_ERR_WORKSPACE;
+  if (Cm > Cin / 2 || w->conv.cout > Cin / 2 || (w->proj.w && w->proj.cout != Cout)) return SF_ERR_INVALID;
+  BottleneckBufs b;
+  if (!carve(b, ws, ws_bytes, Cin, Cout, (size_t)n * H * W)) return SF_ERR_WORKSPACE;
+  const auto [t1, t2, xp, pr] = b;
   SF_TRY(run1(problem(w->down, x, nullptr, t1, n, H, W), EPI_AFFINE, st));
   ConvProblem c = problem(w->conv, t1, nullptr, t2, n, H, W);
   if (c.Hout != Ho || c.Wout != Wo) return SF_ERR_INVALID;
@@ -1011,7 +1011,9 @@ int sf_bottleneck_fwd(const sf_bottleneck_w* w, const float* x, float* out, int 
 
 // 1x1 head of the (Spatial)DistributionModule (beverse motion_modules.py:34-46, 74-88): optional
 // global average pool, 1x1 conv with bias, log-sigma half clamped to [lo, hi] when clamp != 0.
-size_t sf_dist_head_ws_bytes(int C, int n) { return (al((size_t)n * 64 * C) + al((size_t)n * C)) * sizeof(float); }
+// the pooled form's slab sums and mean: carved also without global_pool (the size query is not told)
+struct DistHeadBufs { float *part, *mean; void take(Arena& A, int C, int n) { part = A.take((size_t)n * 64 * C); mean = A.take((size_t)n * C); } };
+size_t sf_dist_head_ws_bytes(int C, int n) { return layout_bytes<DistHeadBufs>(C, n); }
 int sf_dist_head_fwd(const sf_conv_w* w, const float* enc, float* out, int n, int H, int W, int global_pool, int clamp,
                      float lo, float hi, float* ws, size_t ws_bytes, void* stream) {
   if (!w || !enc || !out || !valid_w(*w)) return SF_ERR_INVALID;
@@ -1019,14 +1021,12 @@ int sf_dist_head_fwd(const sf_conv_w* w, const float* enc, float* out, int n, in
   const int C = w->c0;
   const float* src = enc;
   int Hh = H, Wh = W;
+  DistHeadBufs b;
+  if (!carve(b, ws, ws_bytes, C, n)) return SF_ERR_WORKSPACE;
   if (global_pool) {
-    Arena A(ws, ws_bytes);
-    float* part = A.take((size_t)n * 64 * C);
-    float* mean = A.take((size_t)n * C);
-    if (!A.ok()) return SF_ERR_WORKSPACE;
-    SF_HIP(launch_chan_partial(enc, part, n, H * W, C, 64, st));
-    SF_HIP(launch_mean_from_partials(part, mean, n, 64, C, H * W, st));
-    src = mean; Hh = 1; Wh = 1;
+    SF_HIP(launch_chan_partial(enc, b.part, n, H * W, C, 64, st));
+    SF_HIP(launch_mean_from_partials(b.part, b.mean, n, 64, C, H * W, st));
+    src = b.mean; Hh = 1; Wh = 1;
   }
   ConvProblem p = problem(*w, src, nullptr, out, n, Hh, Wh);
   if (clamp) { p.clamp_from = w->cout / 2; p.clamp_lo = lo; p.clamp_hi = hi; }
@@ -1034,20 +1034,18 @@ int sf_dist_head_fwd(const sf_conv_w* w, const float* enc, float* out, int n, in
 }
 
 // ---- head blocks ----------------------------------------------------------------------------------
-size_t sf_convnext_block_ws_bytes(int C, int n, int H, int W) {
-  size_t P = (size_t)n * H * W;
-  return (al(P * C) + al(P * 4 * C)) * sizeof(float);
-}
+// the depthwise + LayerNorm output and the hidden tensor
+struct ConvNextBufs { float *t, *u; void take(Arena& A, int C, size_t P) { t = A.take(P * C); u = A.take(P * 4 * C); } };
+size_t sf_convnext_block_ws_bytes(int C, int n, int H, int W) { return layout_bytes<ConvNextBufs>(C, (size_t)n * H * W); }
 int sf_convnext_block_fwd(const sf_convnext_w* w, const float* x, float* out, int n, int H, int W, float* ws,
                           size_t ws_bytes, void* stream) {
   if (!w || !x || !out) return SF_ERR_INVALID;
   const int C = w->C;
   hipStream_t st = (hipStream_t)stream;
-  Arena A(ws, ws_bytes);
   const size_t P = (size_t)n * H * W;
-  float* t = A.take(P * C);
-  float* u = A.take(P * 4 * C);
-  if (!A.ok()) return SF_ERR_WORKSPACE;
+  ConvNextBufs bufs;
+  if (!carve(bufs, ws, ws_bytes, C, P)) return SF_ERR_WORKSPACE;
+  float *t = bufs.t, *u = bufs.u;
   if (launch_dwconv7_ln(x, t, w->dw_w, w->dw_b, w->ln_w, w->ln_b, n, H, W, C, 1e-6f, st) != hipSuccess)
     return SF_ERR_UNSUPPORTED;
   // 64 -> 256 -> 64 (every ConvNeXt block of the reference's configs): the two pointwise layers in one launch, the hidden tensor
@@ -1070,23 +1068,23 @@ int sf_convnext_block_fwd(const sf_convnext_w* w, const float* x, float* out, in
   return run1(p2, EPI_AFFINE, st);
 }
 
-size_t sf_deeplab_head_ws_bytes(int C, int hid, int n, int H, int W) {
-  size_t P = (size_t)n * H * W;
-  return (al(P * 4 * hid) + 2 * al(P * hid) + al((size_t)n * ASPP_SLABS * C) + al((size_t)n * hid)) * sizeof(float);
-}
+struct DeepLabBufs {      // the four branches side by side, projection and 3x3 output, the pooling branch's slab sums and per-image bias
+  float *cat, *y, *z, *part, *bimg;
+  void take(Arena& A, int C, int hid, int n, size_t P) {
+    cat = A.take(P * 4 * hid); y = A.take(P * hid); z = A.take(P * hid);
+    part = A.take((size_t)n * ASPP_SLABS * C); bimg = A.take((size_t)n * hid);
+  }
+};
+size_t sf_deeplab_head_ws_bytes(int C, int hid, int n, int H, int W) { return layout_bytes<DeepLabBufs>(C, hid, n, (size_t)n * H * W); }
 static int deeplab_head(const sf_deeplab_w* w, const float* x, float* out, int n, int H, int W, int planar_group, size_t stride_major,
                         size_t stride_minor, float* ws, size_t ws_bytes, void* stream) {
   if (!w || !x || !out) return SF_ERR_INVALID;
   const int C = w->C, hid = w->hid;
   hipStream_t st = (hipStream_t)stream;
-  Arena A(ws, ws_bytes);
   const size_t P = (size_t)n * H * W;
-  float* cat = A.take(P * 4 * hid);
-  float* y = A.take(P * hid);
-  float* z = A.take(P * hid);
-  float* part = A.take((size_t)n * ASPP_SLABS * C);
-  float* bimg = A.take((size_t)n * hid);
-  if (!A.ok()) return SF_ERR_WORKSPACE;
+  DeepLabBufs b;
+  if (!carve(b, ws, ws_bytes, C, hid, n, P)) return SF_ERR_WORKSPACE;
+  const auto [cat, y, z, part, bimg] = b;
   SF_HIP(launch_aspp_pool(x, part, bimg, n, H * W, C, hid, w->pool_w, w->pool_scale, w->pool_bias, w->proj_pool_w,
                           w->project.scale, w->project.bias, ASPP_SLABS, st));
   ConvProblem ps[4];

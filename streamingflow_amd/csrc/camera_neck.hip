@@ -25,7 +25,7 @@
 #include <cmath>
 #include <cstdint>
 
-#include "../../include/sfnative.h"
+#include "dispatch.h"
 
 namespace sf {
 
@@ -92,10 +92,21 @@ static int depth_softmax_planar(const float* logits, int cs, int co, float* out_
   return hipGetLastError() == hipSuccess ? SF_OK : SF_ERR_LAUNCH;
 }
 
-static size_t al(size_t floats) { return (floats + 63) / 64 * 64; }      // 256-byte blocks
-
 struct NeckShape {
   int c_hi, c_lo, C, D, hid;
+};
+// the neck's workspace (dispatch.h: Arena): the twin head's output, its upsampling, conv1's output of either branch, the depth logits as
+// NHWC, and the workspaces of the head and of the convolutions' split-K, as their own queries size them
+struct NeckBufs {
+  float *head_out, *up, *t_feat, *t_depth, *d_nhwc, *head_ws, *conv_ws;
+  size_t head_ws_bytes, conv_ws_bytes;
+  void take(Arena& A, const NeckShape& s, int n, int H, int W) {
+    const size_t P = (size_t)n * H * W;
+    head_out = A.take(P * 2 * s.c_hi); up = A.take(4 * P * 2 * s.c_hi);
+    t_feat = A.take(4 * P * s.C); t_depth = A.take(4 * P * s.D); d_nhwc = A.take(4 * P * s.D);
+    head_ws_bytes = sf_deeplab_head_ws_bytes(s.c_hi, s.hid, n, H, W); conv_ws_bytes = sf_conv2d_ex_ws_bytes();
+    head_ws = A.take(head_ws_bytes / sizeof(float)); conv_ws = A.take(conv_ws_bytes / sizeof(float));
+  }
 };
 
 // the four convolutions must be the two UpsamplingConcat chains of one twin head: [feature conv1, feature conv2, depth conv1, depth conv2]
@@ -126,29 +137,19 @@ int sf_depth_softmax_planar_fwd(const float* logits_nhwc, int cs, int co, float*
 
 size_t sf_camera_neck_ws_bytes(int c_hi, int c_lo, int C, int D, int hid, int n, int H, int W) {
   if (c_hi < 1 || c_lo < 1 || C < 1 || D < 1 || hid < 1 || n < 1 || H < 1 || W < 1) return 0;
-  const size_t P = (size_t)n * H * W;
-  const size_t floats = al(P * 2 * c_hi) + al(4 * P * 2 * c_hi) + al(4 * P * C) + 2 * al(4 * P * D);
-  return floats * sizeof(float) + (sf_deeplab_head_ws_bytes(c_hi, hid, n, H, W) + 255) / 256 * 256 + sf_conv2d_ex_ws_bytes();
+  return layout_bytes<NeckBufs>(NeckShape{c_hi, c_lo, C, D, hid}, n, H, W);
 }
 
 int sf_camera_neck_fwd(const sf_deeplab_w* head, const sf_conv_w* convs, const float* hi, const float* lo, float* rays, float* depth_logits,
                        float* depth_prob, int n, int H, int W, float* ws, size_t ws_bytes, void* stream) {
   NeckShape s;
-  if (!hi || !lo || !rays || !depth_logits || !depth_prob || !ws || n < 1 || H < 1 || W < 1 || ((uintptr_t)ws & 15) || !neck_shape(head, convs, &s))
+  if (!hi || !lo || !rays || !depth_logits || !depth_prob || n < 1 || H < 1 || W < 1 || ((uintptr_t)ws & 15) || !neck_shape(head, convs, &s))
     return SF_ERR_INVALID;
   if ((s.D % 4) || s.D > DSP_MAX_D) return SF_ERR_UNSUPPORTED;      // the last launch's refusal, before anything is written
-  if (ws_bytes < sf_camera_neck_ws_bytes(s.c_hi, s.c_lo, s.C, s.D, s.hid, n, H, W)) return SF_ERR_WORKSPACE;
-  const size_t P = (size_t)n * H * W;
+  NeckBufs b;
+  if (!carve(b, ws, ws_bytes, s, n, H, W)) return SF_ERR_WORKSPACE;
   const int twin = 2 * s.c_hi;
-  float* head_out = ws;
-  float* up = head_out + al(P * twin);
-  float* t_feat = up + al(4 * P * twin);
-  float* t_depth = t_feat + al(4 * P * s.C);
-  float* d_nhwc = t_depth + al(4 * P * s.D);
-  float* head_ws = d_nhwc + al(4 * P * s.D);
-  const size_t head_ws_bytes = (sf_deeplab_head_ws_bytes(s.c_hi, s.hid, n, H, W) + 255) / 256 * 256;
-  float* conv_ws = head_ws + head_ws_bytes / sizeof(float);
-  const size_t conv_ws_bytes = sf_conv2d_ex_ws_bytes();
+  const auto [head_out, up, t_feat, t_depth, d_nhwc, head_ws, conv_ws, head_ws_bytes, conv_ws_bytes] = b;
   int rc = sf_deeplab_head_fwd(head, hi, head_out, n, H, W, head_ws, head_ws_bytes, stream);
   if (rc != SF_OK) return rc;
   rc = sf_upsample_bilinear2_add_fwd(head_out, nullptr, up, n, H, W, twin, stream);

@@ -13,20 +13,49 @@
 
 namespace sf {
 
+inline size_t al(size_t n) { return (n + 63) & ~size_t(63); }
+// A caller's workspace handed out in 256-byte blocks.  Every entry point has ONE layout struct whose take(Arena&, dims...) is the one place
+// its buffers are laid out: the forward runs an arena over the caller's memory through it and checks ok() before it enqueues anything, the
+// sf_*_ws_bytes query runs a measuring arena (no memory: take never fails, hands out null, and bytes() is the high-water mark) through the
+// same function (layout_bytes).  So exactly the queried size is enough, and the layout may depend on nothing the query is not given.
 struct Arena {
   float* base;
-  size_t cap, off;
-  Arena(float* b, size_t bytes) : base(b), cap(bytes / sizeof(float)), off(0) {}
+  size_t cap, off = 0, peak = 0;
+  bool measuring, failed = false;
+  Arena(float* b, size_t bytes) : base(b), cap(bytes / sizeof(float)), measuring(false) {}
+  Arena() : base(nullptr), cap(~size_t(0)), measuring(true) {}
   float* take(size_t n) {
-    size_t a = (n + 63) & ~size_t(63);
-    if (!base || off + a > cap) { off = cap + 1; return nullptr; }
-    float* p = base + off;
+    const size_t a = al(n);
+    if (!measuring && (!base || failed || a > cap - off)) { failed = true; return nullptr; }
     off += a;
-    return p;
+    peak = std::max(peak, off);
+    return measuring ? nullptr : base + (off - a);
   }
-  bool ok() const { return off <= cap; }
+  bool ok() const { return !failed; }
+  size_t bytes() const { return peak * sizeof(float); }
+  // buffers that are never live together (a cell's against the infer_state's behind it): every alternative is carved from the same
+  // offset, and the arena goes on behind the larger
+  template <class... Alt>
+  void larger_of(Alt&&... alt) {
+    const size_t start = off;
+    size_t end = off;
+    ((off = start, alt(), end = std::max(end, off)), ...);
+    off = end;
+  }
 };
-inline size_t al(size_t n) { return (n + 63) & ~size_t(63); }
+template <class Layout, class... Dims>
+size_t layout_bytes(Dims... dims) {      // the size query
+  Arena A;
+  Layout l{};
+  l.take(A, dims...);
+  return A.bytes();
+}
+template <class Layout, class... Dims>
+bool carve(Layout& l, float* ws, size_t ws_bytes, Dims... dims) {      // the call: false = SF_ERR_WORKSPACE, with nothing enqueued yet
+  Arena A(ws, ws_bytes);
+  l.take(A, dims...);
+  return A.ok();
+}
 
 // Switches, read once per process from the environment: the ones a test, bench.py, the package or a tools/*bench.py tool reads or sets, and
 // the printing aids (INTEGRATION.md has the table; tests/test_switches.py pins the set).  Measured thresholds nobody varies are constants
@@ -116,30 +145,44 @@ int debug_wino_plan(const sf_conv_w& w, int epi, int n_img, int Hin, int Win, in
 int debug_tiled_plan(const sf_conv_w* w, int epi, int n_img, int Hin, int Win, int in_up, int nprob, int flags, int32_t* out, int n_out);   // sf_debug_tiled_plan
 
 // Scratch for the cross-workgroup split-K path, carved from the caller's workspace by the top-level entry points for the duration of one
-// call (RAII; the pointer to it is thread-local inside dispatch.hip, no global allocation)
+// call (the pointer to it is thread-local inside dispatch.hip, no global allocation).  Two steps: SplitBufs::take is part of the entry
+// point's layout; SplitScope arms it (RAII) once the whole layout is known to fit — it enqueues the zero fill of the counters.  Buffers
+// that were not carved (null: the entry points whose scratch is optional) leave the call without split-K.
 struct SplitCtx { float* slab; size_t slab_floats; unsigned* counters; int ncounters; };
 constexpr size_t SPLIT_SLAB_FLOATS = size_t(8) << 20;   // 32 MB: 2048 (tile, slice) pairs of 64x64 fp32
 constexpr int SPLIT_COUNTERS = 4096;
-constexpr size_t SPLIT_WS_FLOATS = SPLIT_SLAB_FLOATS + SPLIT_COUNTERS + 128;
+struct SplitBufs {
+  float* slab = nullptr;
+  unsigned* counters = nullptr;
+  void take(Arena& A) {
+    slab = A.take(SPLIT_SLAB_FLOATS);
+    counters = reinterpret_cast<unsigned*>(A.take(SPLIT_COUNTERS));
+  }
+};
 struct SplitScope {
-  SplitCtx ctx;
+  SplitCtx ctx{};
   SplitCtx* prev;
-  SplitScope(Arena& A, hipStream_t st);
+  SplitScope(const SplitBufs& b, hipStream_t st);
   ~SplitScope();
 };
 
 // ---- persistent flow (one latent inside a rollout, SF_PERSIST=1 / sf_set_flow_mode): while a FlowScope is active, run() records its
 // small-P launch groups as phases of ONE persistent launch instead of launching them (dispatch.hip: FlowBuilder)
 struct FlowBuilder;
+struct FlowBufs {                   // the carve: tables and counters, flow_ws_floats() floats (nothing while the flow mode is off)
+  unsigned char* table = nullptr;
+  unsigned* done = nullptr;
+  void take(Arena& A);
+};
 struct FlowScope {
   FlowBuilder* fb = nullptr;
   int status = SF_OK;
-  // `allow` and the flow mode and a split-K scratch: carves the tables and counters from A (check A.ok(), then status) and zeroes the counters
-  FlowScope(bool allow, Arena& A, hipStream_t st);
+  // the arming step, after the layout is known to fit: `allow` and the flow mode and an armed split-K scratch: zeroes the counters (check status)
+  FlowScope(bool allow, const FlowBufs& b, hipStream_t st);
   ~FlowScope();
   const unsigned* err() const;      // error word of the flow's bounded waits (null: no flow)
 };
-size_t flow_ws_floats();            // workspace of a FlowScope under the flow mode in force now (0: off)
+size_t flow_ws_floats();            // what FlowBufs::take carves under the flow mode in force now (0: off)
 int seg_flush();                    // anything that is not a small-P launch first sends the recorded phases on their way (stream order)
 int flow_copy_out(const float* src, float* dst, size_t n, hipStream_t st);      // state copy-out: rides in the next phase, or a copy launch
 // end of a rollout: NaN over both outputs if a bounded wait of its flow timed out (err != null), and remember err for flow_errors()

@@ -246,7 +246,7 @@ int chansum_tile_px(const ConvProblem* group, int n, int epi) { return sp_takes(
 // graph-capturable) and the flow kernel is launched when the rollout ends or something that is not a small-P launch intervenes.
 constexpr size_t FLOW_TABLE_BYTES = size_t(1) << 20;       // phases + problems of one flow
 constexpr int FLOW_DONE_COUNTERS = 1 << 20;                // counter dwords of one flow (SP_FLOW_PHASE_DWORDS = 1536 per phase: every polled counter on its own line)
-constexpr size_t FLOW_WS_FLOATS = FLOW_TABLE_BYTES / 4 + FLOW_DONE_COUNTERS + 256;
+constexpr size_t FLOW_WS_FLOATS = FLOW_TABLE_BYTES / 4 + FLOW_DONE_COUNTERS + 64;      // what FlowBufs::take carves
 struct FlowBuilder {
   std::vector<FlowPhase> phases;
   std::vector<ConvProblem> probs;
@@ -380,13 +380,15 @@ int seg_flush() { return g_seg ? g_seg->flush() : SF_OK; }
 // the persistent flow's tables and counters (5 MB) only where the flow form is switched on at the time of the query: the size query and
 // the call see the same setting (a workspace sized without them makes a flow-mode call fail with SF_ERR_WORKSPACE, not overrun)
 size_t flow_ws_floats() { return flow_mode_on() ? FLOW_WS_FLOATS : 0; }
-FlowScope::FlowScope(bool allow, Arena& A, hipStream_t st) {
-  if (!(allow && flow_mode_on() && g_split != nullptr)) return;
-  unsigned char* table = reinterpret_cast<unsigned char*>(A.take(FLOW_TABLE_BYTES / 4));
-  unsigned* done = reinterpret_cast<unsigned*>(A.take(FLOW_DONE_COUNTERS + 64));
-  if (!A.ok()) return;
-  g_seg = fb = new FlowBuilder(table, done, done + FLOW_DONE_COUNTERS, st);
-  if (zero_fill(done, (FLOW_DONE_COUNTERS + 64) * sizeof(unsigned), st) != hipSuccess) status = SF_ERR_LAUNCH;
+void FlowBufs::take(Arena& A) {
+  if (!flow_mode_on()) return;
+  table = reinterpret_cast<unsigned char*>(A.take(FLOW_TABLE_BYTES / 4));
+  done = reinterpret_cast<unsigned*>(A.take(FLOW_DONE_COUNTERS + 64));
+}
+FlowScope::FlowScope(bool allow, const FlowBufs& b, hipStream_t st) {
+  if (!(allow && flow_mode_on() && g_split != nullptr && b.table && b.done)) return;
+  g_seg = fb = new FlowBuilder(b.table, b.done, b.done + FLOW_DONE_COUNTERS, st);
+  if (zero_fill(b.done, (FLOW_DONE_COUNTERS + 64) * sizeof(unsigned), st) != hipSuccess) status = SF_ERR_LAUNCH;
 }
 FlowScope::~FlowScope() {
   if (fb) g_seg = nullptr;
@@ -1123,14 +1125,10 @@ int run_dma128(const ConvProblem& p, bool producer, hipStream_t st) {
   return SF_OK;
 }
 
-// RAII: carve + zero the split-K scratch for the duration of one top-level call
-SplitScope::SplitScope(Arena& A, hipStream_t st) : prev(g_split) {
-  if (!tune().split) return;
-  ctx.slab = A.take(SPLIT_SLAB_FLOATS);
-  ctx.counters = reinterpret_cast<unsigned*>(A.take(SPLIT_COUNTERS));
-  ctx.slab_floats = SPLIT_SLAB_FLOATS;
-  ctx.ncounters = SPLIT_COUNTERS;
-  if (!A.ok() || !ctx.slab || !ctx.counters) return;
+// RAII: zero the counters of the carved split-K scratch and arm it for the duration of one top-level call
+SplitScope::SplitScope(const SplitBufs& b, hipStream_t st) : prev(g_split) {
+  if (!tune().split || !b.slab || !b.counters) return;
+  ctx = {b.slab, SPLIT_SLAB_FLOATS, b.counters, SPLIT_COUNTERS};
   if (zero_fill(ctx.counters, SPLIT_COUNTERS * sizeof(unsigned), st) != hipSuccess) return;
   g_split = &ctx;
 }
