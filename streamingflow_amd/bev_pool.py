@@ -9,7 +9,7 @@ every cell straight from the unsorted feature matrix.  No host synchronisation, 
 """
 import torch
 
-from . import _lib, runtime
+from . import runtime
 from .runtime import ptr
 
 
@@ -23,10 +23,7 @@ def cell_index_from_coords(coords, B, Z, X, Y):
     order = torch.empty((max(n, 1),), dtype=torch.int32, device=dev)
     start = torch.zeros((ncells + 1,), dtype=torch.int32, device=dev)
     if n:
-        L = _lib.lib()
-        ws = runtime.workspace(L.sf_lift_index_ws_bytes(n, ncells), dev)
-        _lib.check(L.sf_lift_index_coords_fwd(ptr(c32), n, B, Z, X, Y, ptr(order), ptr(start), ptr(ws), ws.numel() * 4,
-                                              runtime.stream_ptr(dev)), "lift_index_coords")
+        runtime.call("lift_index_coords", ptr(c32), n, B, Z, X, Y, ptr(order), ptr(start), device=dev, scratch=("lift_index", n, ncells))
     return order, start
 
 
@@ -35,8 +32,7 @@ def pool_cells(x, order, cell_start, n_cells, prev=None, discount=1.0, out=None)
     C = x.shape[1]
     if out is None:
         out = torch.empty((n_cells, C), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().sf_lift_pool_fwd(ptr(x), ptr(order), ptr(cell_start), n_cells, C, ptr(prev), float(discount), ptr(out),
-                                           runtime.stream_ptr(x.device)), "lift_pool")
+    runtime.call("lift_pool", ptr(x), ptr(order), ptr(cell_start), n_cells, C, ptr(prev), float(discount), ptr(out), device=x.device)
     return out
 
 
@@ -62,6 +58,6 @@ def bev_pool_forward(x, geom_feats, interval_lengths, interval_starts, B, D, H, 
     g = geom_feats.to(torch.int32).contiguous()
     ln, st = interval_lengths.to(torch.int32).contiguous(), interval_starts.to(torch.int32).contiguous()
     out = torch.empty((int(B), int(D), int(H), int(W), x.shape[1]), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().sf_bev_pool_fwd(ptr(x), ptr(g), ptr(ln), ptr(st), x.shape[0], x.shape[1], st.shape[0], int(B), int(D),
-                                          int(H), int(W), ptr(out), runtime.stream_ptr(x.device)), "bev_pool")
+    runtime.call("bev_pool", ptr(x), ptr(g), ptr(ln), ptr(st), x.shape[0], x.shape[1], st.shape[0], int(B), int(D), int(H), int(W),
+                 ptr(out), device=x.device)
     return out

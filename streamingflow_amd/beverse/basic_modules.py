@@ -8,9 +8,10 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import _lib, packing, runtime
+from .. import runtime
 from ..layers.convolutions import Bottleneck  # noqa: F401  (same block, same state_dict keys)
-from ..runtime import PackedModule, ptr
+from ..layers.temporal import gru_cell_nhwc, pack_gru_block, spatial_gru_nhwc
+from ..runtime import PackedModule
 
 
 class ConvBlock(nn.Module):
@@ -72,28 +73,11 @@ class SpatialGRU(PackedModule):
         self.conv_reset = nn.Conv2d(cat, hidden_size, kernel_size=3, bias=True, padding=1)
         self.conv_state_tilde = ConvBlock(cat, hidden_size, kernel_size=3, bias=False, norm=norm, activation=activation)
 
-    def _pack(self):
-        if self.training:
-            raise RuntimeError("streamingflow_amd is inference-only: call .eval()")
-        pk = packing.Pack(_lib.GruW())
-        s = pk.struct
-        wg = torch.cat([self.conv_update.weight, self.conv_reset.weight], 0)
-        bg = torch.cat([self.conv_update.bias, self.conv_reset.bias], 0) + float(self.gru_bias_init)
-        s.gates = packing.conv_w(pk, wg, self.input_size, self.hidden_size, bias=bg, act="sigmoid")
-        sc, bi = packing.bn_fold(self.conv_state_tilde.norm)
-        s.cand = packing.conv_w(pk, self.conv_state_tilde.conv.weight, self.input_size, self.hidden_size, scale=sc,
-                                bias=bi, act="relu")
-        return pk
+    _pack = pack_gru_block
 
     def forward_nhwc(self, x, state):
         """x [T, B, h, w, Cx], state [B, h, w, C] -> states [T, B, h, w, C]."""
-        T, B, h, w, _ = x.shape
-        L = _lib.lib()
-        ws = runtime.workspace(L.sf_spatial_gru_ws_bytes(self.hidden_size, B, h, w), x.device)
-        out = torch.empty((T, B, h, w, self.hidden_size), dtype=torch.float32, device=x.device)
-        _lib.check(L.sf_spatial_gru_fwd(self.packed().struct, ptr(x), ptr(state), ptr(out), T, B, h, w, ptr(ws),
-                                        ws.numel() * 4, runtime.stream_ptr(x.device)), "beverse_spatial_gru")
-        return out
+        return spatial_gru_nhwc(self.packed().struct, x, state, self.hidden_size, self.hidden_size)
 
     def forward(self, x, state=None, flow=None, mode='bilinear'):
         assert len(x.size()) == 5, 'Input tensor must be BxTxCxHxW.'
@@ -102,16 +86,15 @@ class SpatialGRU(PackedModule):
         runtime.require_cuda(x, state)
         b, T, c, h, w = x.size()
         assert c == self.input_size, f'feature sizes must match, got input {c} for layer with size {self.input_size}'
-        xn = runtime.to_nhwc(x.reshape(b * T, c, h, w)).view(b, T, h, w, c).permute(1, 0, 2, 3, 4).contiguous()
+        xn = runtime.frames_to_nhwc(x)
         s0 = (torch.zeros((b, h, w, self.hidden_size), dtype=torch.float32, device=x.device) if state is None
               else runtime.to_nhwc(state))
-        out = self.forward_nhwc(xn, s0).permute(1, 0, 2, 3, 4).reshape(b * T, h, w, self.hidden_size)
-        return runtime.to_nchw(out).view(b, T, self.hidden_size, h, w)
+        return runtime.frames_to_nchw(self.forward_nhwc(xn, s0))
 
 
 class GRUCell(PackedModule):
     """One conv-GRU step, ``forward(x, state)`` with x (b, input_size, h, w) and state (b, hidden_size, h, w): the cell
-    ResFuturePrediction* chain per frame.  Same parameters as ``SpatialGRU``, packed the same way, run by ``sf_gru_cell_fwd``."""
+    ResFuturePrediction* chain per frame.  Same parameters as ``SpatialGRU``, packed the same way, run by ``gru_cell_nhwc``."""
 
     def __init__(self, input_size, hidden_size, gru_bias_init=0.0, norm='bn', activation='relu'):
         super().__init__()
@@ -123,18 +106,11 @@ class GRUCell(PackedModule):
         self.conv_reset = nn.Conv2d(cat, hidden_size, kernel_size=3, bias=True, padding=1)
         self.conv_state_tilde = ConvBlock(cat, hidden_size, kernel_size=3, bias=False, norm=norm, activation=activation)
 
-    _pack = SpatialGRU._pack
+    _pack = pack_gru_block
 
     def forward_nhwc(self, x, state, out=None):
         """x [n, h, w, input_size], state [n, h, w, hidden_size] -> [n, h, w, hidden_size] (into `out` when given)."""
-        n, h, w, _ = x.shape
-        L = _lib.lib()
-        ws = runtime.workspace(L.sf_gru_cell_ws_bytes(self.hidden_size, n, h, w), x.device)
-        if out is None:
-            out = torch.empty((n, h, w, self.hidden_size), dtype=torch.float32, device=x.device)
-        _lib.check(L.sf_gru_cell_fwd(self.packed().struct, ptr(x), ptr(state), ptr(out), n, h, w, ptr(ws), ws.numel() * 4,
-                                     runtime.stream_ptr(x.device)), "beverse_gru_cell")
-        return out
+        return gru_cell_nhwc(self.packed().struct, x, state, out)
 
     def forward(self, x, state):
         require_eval(self)

@@ -3,13 +3,13 @@
 (:91-108), ``FuturePrediction`` (:111-146), ``ResFuturePrediction`` / ``ResFuturePredictionV2`` /
 ``ResFuturePredictionV1`` (:149-431) and ``warp_with_flow`` (:434-449).  Same signatures and state_dict keys; HIP execution."""
 import copy
-import ctypes
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import _lib, packing, runtime
+from ..layers.convolutions import dist_head_nhwc
 from ..runtime import PackedModule, ptr
 from .basic_modules import (Bottleneck, ConvBlock, GRUCell, SpatialGRU, conv_block_torch, gru_cell_torch, require_eval, spatial_gru_torch,
                             use_torch_path)
@@ -51,16 +51,7 @@ class _DistBase(PackedModule):
         return pk
 
     def _head(self, enc):
-        n, h, w, c = enc.shape
-        L = _lib.lib()
-        ws = runtime.workspace(L.sf_dist_head_ws_bytes(c, n), enc.device)
-        ho, wo = (1, 1) if self.global_pool else (h, w)
-        out = torch.empty((n, ho, wo, 2 * self.latent_dim), dtype=torch.float32, device=enc.device)
-        import ctypes
-        _lib.check(L.sf_dist_head_fwd(ctypes.byref(self.packed().struct), ptr(enc), ptr(out), n, h, w,
-                                      int(self.global_pool), 1, float(self.min_log_sigma), float(self.max_log_sigma),
-                                      ptr(ws), ws.numel() * 4, runtime.stream_ptr(enc.device)), "dist_head")
-        return out
+        return dist_head_nhwc(self.packed().struct, enc, self.global_pool, clamp=(self.min_log_sigma, self.max_log_sigma))
 
 
 class DistributionModule(_DistBase):
@@ -103,7 +94,7 @@ class FuturePrediction(nn.Module):
     def forward(self, x, hidden_state):
         runtime.require_cuda(x, hidden_state)
         b, T, c, h, w = x.shape
-        xn = runtime.to_nhwc(x.reshape(b * T, c, h, w)).view(b, T, h, w, c).permute(1, 0, 2, 3, 4).contiguous()
+        xn = runtime.frames_to_nhwc(x)
         hid = runtime.to_nhwc(hidden_state)
         for gru, blocks in zip(self.spatial_grus, self.res_blocks):
             xn = gru.forward_nhwc(xn, hid)                       # [T, b, h, w, C]
@@ -111,32 +102,16 @@ class FuturePrediction(nn.Module):
             for blk in blocks:
                 y = blk.forward_nhwc(y)
             xn = y.view(T, b, h, w, y.shape[-1])
-        C = xn.shape[-1]
-        out = runtime.to_nchw(xn.permute(1, 0, 2, 3, 4).reshape(b * T, h, w, C))
-        return out.view(b, T, C, h, w)
+        return runtime.frames_to_nchw(xn)
 
 
 # ---- ResFuturePrediction family (motion_modules.py:149-449): flow-warp GRU rollout ---------------------------------------------
-def _at(t, off=0):
-    """Device pointer `off` floats into tensor t."""
-    return ctypes.c_void_p(t.data_ptr() + 4 * off)
-
-
-def _conv(w, in0, in0_cs, in0_co, in1, out, out_cs, out_co, n, h, wd):
-    """Packed conv `w` on (channels in0_co.. of in0 [P][in0_cs], in1 [P][w.c1]) into channels out_co.. of out [P][out_cs]."""
-    L = _lib.lib()
-    ws = runtime.workspace(L.sf_conv2d_ex_ws_bytes(), out.device)
-    _lib.check(L.sf_conv2d_ex_fwd(ctypes.byref(w), _at(in0, in0_co), in0_cs, ptr(in1), w.c1, None, 0, 0, ptr(out), out_cs, out_co, n, h, wd,
-                                  0, ptr(ws), ws.numel() * 4, runtime.stream_ptr(out.device)), "conv2d_ex")
-
-
 def flow_warp_nhwc(state, out, out_cs, out_co, feat=None, w_off=None, b_off=None, flow=None, flow_out=None):
     """``sf_flow_warp_fwd``: state [B, h, w, C] resampled along a per-pixel flow into channels out_co .. out_co + C of out
     [B, h, w, out_cs].  The flow is `flow` [B, h, w, 2] (x, y) or the fused 1x1 head w_off [2, Cf] . feat [B, h, w, Cf] + b_off."""
     B, h, w, C = state.shape
-    _lib.check(_lib.lib().sf_flow_warp_fwd(ptr(state), ptr(feat), ptr(w_off), ptr(b_off), ptr(flow), ptr(out), ptr(flow_out), B, h, w, C,
-                                           feat.shape[-1] if feat is not None else 0, out_cs, out_co, runtime.stream_ptr(state.device)),
-               "flow_warp")
+    runtime.call("flow_warp", ptr(state), ptr(feat), ptr(w_off), ptr(b_off), ptr(flow), ptr(out), ptr(flow_out), B, h, w, C,
+                 feat.shape[-1] if feat is not None else 0, out_cs, out_co, device=state.device)
     return out
 
 
@@ -157,17 +132,6 @@ def warp_with_flow(x, flow):
     out = torch.empty_like(xn)
     flow_warp_nhwc(xn, out, C, 0, flow=runtime.to_nhwc(flow))
     return runtime.to_nchw(out)
-
-
-def _frames_to_nchw(frames):
-    """[T, B, h, w, C] NHWC frames -> the reference's (B, T, C, h, w): one strided transpose per frame."""
-    T, B, h, w, C = frames.shape
-    res = torch.empty((B, T, C, h, w), dtype=torch.float32, device=frames.device)
-    L = _lib.lib()
-    for t in range(T):
-        _lib.check(L.sf_nhwc_to_nchw_strided(ptr(frames[t]), h * w * C, ptr(res[0, t]), T * C * h * w, B, C, h * w,
-                                             runtime.stream_ptr(frames.device)), "nhwc_to_nchw_strided")
-    return res
 
 
 def _pack_block(pk, blk, c0, c1=0):
@@ -239,14 +203,14 @@ class _ResFutureBase(PackedModule):
         for i in range(self.n_future):
             if self.flow_warp:
                 cw, w_off, b_off = pk.flow[i]
-                _conv(cw, sn, L, 0, cur, feat, C + L, 0, B, h, w)
+                runtime.conv2d_ex(cw, sn, L, 0, B, h, w, feat, C + L, 0, in1=cur, in1_cs=C)
                 flow_warp_nhwc(cur, xbuf, C + L, w_co, feat=feat, w_off=w_off, b_off=b_off)
             else:
                 xbuf[..., w_co:w_co + C].copy_(cur)
             y = xbuf
             for cell in self.gru_cells:
                 y = cell.forward_nhwc(y, cur)
-            _conv(pk.spatial[i], y, C, 0, None, frames[i], C, 0, B, h, w)
+            runtime.conv2d_ex(pk.spatial[i], y, C, 0, B, h, w, frames[i], C, 0)
             cur = frames[i]
         return frames
 
@@ -274,7 +238,7 @@ class _ResFutureBase(PackedModule):
         if use_torch_path(sample_distribution, hidden_state, next(self.parameters())):
             with torch.no_grad():
                 return self._forward_torch(sample_distribution, hidden_state)
-        return _frames_to_nchw(self.forward_nhwc(runtime.to_nhwc(sample_distribution), runtime.to_nhwc(hidden_state)))
+        return runtime.frames_to_nchw_strided(self.forward_nhwc(runtime.to_nhwc(sample_distribution), runtime.to_nhwc(hidden_state)))
 
 
 class ResFuturePrediction(_ResFutureBase):
@@ -398,7 +362,7 @@ class ResFuturePredictionV1(PackedModule):
         cw, w_off, b_off = pk.flow
         for i in range(self.n_future):
             k = i if self.prob_each_future else 0
-            _conv(cw, sn, Ls, k * L, states[i], feat, C + L, 0, B, h, w)
+            runtime.conv2d_ex(cw, sn, Ls, k * L, B, h, w, feat, C + L, 0, in1=states[i], in1_cs=C)
             flow_warp_nhwc(states[i], xbuf[k], L + C, L, feat=feat, w_off=w_off, b_off=b_off)
             self.spatial_grus[0].forward_nhwc(xbuf[k], zeros if i == 0 else states[i], out=states[i + 1])
         y = states
@@ -407,9 +371,9 @@ class ResFuturePredictionV1(PackedModule):
             if k:
                 y = self.spatial_grus[k].forward_nhwc(y, zeros)
             blk, one = pk.spatial[k]
-            _conv(blk, y, C, 0, None, tmp, C, 0, T * B, h, w)
+            runtime.conv2d_ex(blk, y, C, 0, T * B, h, w, tmp, C, 0)
             y = torch.empty((T, B, h, w, C), dtype=torch.float32, device=dev)
-            _conv(one, tmp, C, 0, None, y, C, 0, T * B, h, w)
+            runtime.conv2d_ex(one, tmp, C, 0, T * B, h, w, y, C, 0)
         return y
 
     def _forward_torch(self, sample, hidden):
@@ -440,4 +404,4 @@ class ResFuturePredictionV1(PackedModule):
         if use_torch_path(sample_distribution, hidden_state, next(self.parameters())):
             with torch.no_grad():
                 return self._forward_torch(sample_distribution, hidden_state)
-        return _frames_to_nchw(self.forward_nhwc(runtime.to_nhwc(sample_distribution), runtime.to_nhwc(hidden_state)))
+        return runtime.frames_to_nchw_strided(self.forward_nhwc(runtime.to_nhwc(sample_distribution), runtime.to_nhwc(hidden_state)))

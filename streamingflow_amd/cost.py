@@ -28,7 +28,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, runtime
+from . import runtime
 from .models.lift_splat import calculate_birds_eye_view_parameters
 from .runtime import ptr
 
@@ -306,10 +306,8 @@ class Cost_Function(nn.Module):
         fo = torch.empty((B, N, T), dtype=torch.float32, device=dev)
         fc = torch.empty((B, N), dtype=torch.float32, device=dev)
         cs = torch.empty((B, N), dtype=torch.float32, device=dev)
-        L = _lib.lib()
-        ws = runtime.workspace(L.sf_plan_cost_ws_bytes(), dev)
-        _lib.check(L.sf_plan_cost_fwd(ptr(trajs), s, ptr(runtime.f32c(cost_volume)), ptr(occ), ptr(runtime.f32c(lane)), ptr(runtime.f32c(drv)),
-                                      ptr(runtime.f32c(target_point)), ptr(rc), n0, ctypes.c_void_p(rc.data_ptr() + n0 * 8), nl, ptr(sc.dx), ptr(sc.bx),
-                                      ptr(sc.w), ctypes.byref((ctypes.c_float * 7)(*self._factors)), float(HEADWAY_L), float(DIVIDER_L), B, N, T, G, G, ptr(fo), ptr(fc),
-                                      ptr(cs), ptr(ws), ws.numel() * 4, runtime.stream_ptr(dev)), "plan_cost")
+        runtime.call("plan_cost", ptr(trajs), s, ptr(runtime.f32c(cost_volume)), ptr(occ), ptr(runtime.f32c(lane)), ptr(runtime.f32c(drv)),
+                     ptr(runtime.f32c(target_point)), ptr(rc), n0, ctypes.c_void_p(rc.data_ptr() + n0 * 8), nl, ptr(sc.dx), ptr(sc.bx),
+                     ptr(sc.w), ctypes.byref((ctypes.c_float * 7)(*self._factors)), float(HEADWAY_L), float(DIVIDER_L), B, N, T, G, G, ptr(fo), ptr(fc),
+                     ptr(cs), device=dev, scratch=("plan_cost",))
         return fc, fo, cs

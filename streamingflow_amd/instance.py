@@ -38,7 +38,7 @@ import numpy as np
 import torch
 from scipy.optimize import linear_sum_assignment
 
-from . import _lib, runtime
+from . import runtime
 from .runtime import ptr
 
 MOMENT_SCALE = 1.0 / 1048576.0      # sf_instance_moments_fwd: flow-warped sums are 2^-20 fixed point
@@ -55,12 +55,10 @@ def find_instance_centers(center_prediction: torch.Tensor, conf_threshold: float
     runtime.require_cuda(center_prediction)
     H, W = center_prediction.shape[-2:]
     heat = runtime.f32c(center_prediction).view(H, W)
-    L = _lib.lib()
     found = torch.empty((H * W, 2), dtype=torch.int32, device=heat.device)
     count = torch.empty((), dtype=torch.int32, device=heat.device)
-    ws = runtime.workspace(L.sf_instance_centers_ws_bytes(H, W), heat.device)
-    _lib.check(L.sf_instance_centers_fwd(ptr(heat), H, W, float(conf_threshold), ptr(found), H * W, ptr(count), ptr(ws), ws.numel() * 4,
-                                         runtime.stream_ptr(heat.device)), "instance_centers")
+    runtime.call("instance_centers", ptr(heat), H, W, float(conf_threshold), ptr(found), H * W, ptr(count), device=heat.device,
+                 scratch=("instance_centers", H, W))
     return found[: int(count.item())].long()
 
 
@@ -76,8 +74,7 @@ def group_pixels(centers: torch.Tensor, offset_predictions: torch.Tensor, foregr
         inside = (foreground_mask.reshape(H, W) != 0).to(torch.uint8).contiguous()
     table = centers.to(torch.int32).contiguous()
     ids = torch.empty((1, H, W), dtype=torch.int64, device=votes.device)
-    _lib.check(_lib.lib().sf_group_pixels_fwd(ptr(table), table.shape[0], ptr(votes), ptr(inside), H, W, ptr(ids),
-                                              runtime.stream_ptr(votes.device)), "group_pixels")
+    runtime.call("group_pixels", ptr(table), table.shape[0], ptr(votes), ptr(inside), H, W, ptr(ids), device=votes.device)
     return ids
 
 
@@ -130,10 +127,8 @@ def instance_segmentation_sequence(center, offset, foreground, conf_threshold: f
     found = torch.empty((F, cap, 2), dtype=torch.int32, device=dev)
     count = torch.empty((F,), dtype=torch.int32, device=dev)
     ids = torch.empty((F, H, W), dtype=torch.int64, device=dev)
-    L = _lib.lib()
-    ws = runtime.workspace(L.sf_instance_seq_ws_bytes(F, H, W, cap), dev)
-    _lib.check(L.sf_instance_seq_fwd(ptr(heat), ptr(votes), ptr(inside), F, H, W, float(conf_threshold), cap, ptr(found), ptr(count), ptr(ids),
-                                     ptr(ws), ws.numel() * 4, runtime.stream_ptr(dev)), "instance_seq")
+    runtime.call("instance_seq", ptr(heat), ptr(votes), ptr(inside), F, H, W, float(conf_threshold), cap, ptr(found), ptr(count), ptr(ids),
+                 device=dev, scratch=("instance_seq", F, H, W, cap))
     if not return_centers:
         return ids
     kept = count.cpu().clamp(max=cap).tolist()
@@ -156,8 +151,7 @@ def _moments_on_device(ids, flow, top, with_tables=False):
     moved = buf[2 * n:4 * n] if fl is not None else None
     tables = buf[head:tail] if with_tables else None
     cnt = buf[tail:].view(torch.int32)
-    _lib.check(_lib.lib().sf_instance_moments_fwd(ptr(ids), ptr(fl), F, H, W, top, ptr(pos), ptr(moved), ptr(cnt),
-                                                  runtime.stream_ptr(ids.device)), "instance_moments")
+    runtime.call("instance_moments", ptr(ids), ptr(fl), F, H, W, top, ptr(pos), ptr(moved), ptr(cnt), device=ids.device)
     return buf, pos, moved, tables, cnt
 
 
@@ -183,10 +177,8 @@ def _track_on_device(counts, sums, warped, B, T, K, matching_threshold, tables=N
     if tables is None:
         tables = torch.empty((B * T * K,), dtype=torch.int64, device=dev)
     flags = torch.empty((B,), dtype=torch.int32, device=dev)
-    L = _lib.lib()
-    ws = runtime.workspace(L.sf_instance_track_ws_bytes(B, T, K), dev)
-    _lib.check(L.sf_instance_track_fwd(ptr(counts), ptr(sums), ptr(warped), B, T, K, float(matching_threshold), ptr(tables), ptr(flags),
-                                       ptr(ws), ws.numel() * 4, runtime.stream_ptr(dev)), "instance_track")
+    runtime.call("instance_track", ptr(counts), ptr(sums), ptr(warped), B, T, K, float(matching_threshold), ptr(tables), ptr(flags),
+                 device=dev, scratch=("instance_track", B, T, K))
     return tables.view(B * T, K), flags
 
 

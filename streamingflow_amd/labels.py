@@ -20,7 +20,7 @@ a batch does not carry them.
 """
 import torch
 
-from . import _lib, runtime
+from . import runtime
 from .models.lift_splat import pose_vec2mat
 from .runtime import ptr
 
@@ -63,8 +63,7 @@ def _resample(maps, theta, mode):
     n, c, h, w = maps.shape
     src = runtime.f32c(maps)
     dst = torch.empty_like(src)
-    _lib.check(_lib.lib().sf_warp_affine_fwd(ptr(src), ptr(theta), n, c, h, w, int(mode == "bilinear"), ptr(dst), runtime.stream_ptr(maps.device)),
-               "warp_affine")
+    runtime.call("warp_affine", ptr(src), ptr(theta), n, c, h, w, int(mode == "bilinear"), ptr(dst), device=maps.device)
     return dst.to(maps.dtype)
 
 
@@ -152,10 +151,8 @@ def instance_labels(instance, future_egomotion, num_instances, ignore_index=255,
     center = torch.empty((B, T, 1, H, W), dtype=torch.float32, device=dev)
     offset = torch.empty((B, T, 2, H, W), dtype=torch.float32, device=dev)
     flow = torch.empty((B, T, 2, H, W), dtype=torch.float32, device=dev)
-    L = _lib.lib()
-    ws = runtime.workspace(L.sf_instance_labels_ws_bytes(B, T, H, W, K), dev)
-    _lib.check(L.sf_instance_labels_fwd(ptr(ids), ptr(theta), B, T, H, W, K, float(sigma), float(ignore_index), ptr(center), ptr(offset),
-                                        ptr(flow), ptr(ws), ws.numel() * 4, runtime.stream_ptr(dev)), "instance_labels")
+    ws = runtime.call("instance_labels", ptr(ids), ptr(theta), B, T, H, W, K, float(sigma), float(ignore_index), ptr(center), ptr(offset),
+                      ptr(flow), device=dev, scratch=("instance_labels", B, T, H, W, K))
     if return_moments:
         return center, offset, flow, _label_moments(ws, B * T, K)
     return center, offset, flow

@@ -69,17 +69,27 @@ class Bottleneck(PackedModule):
 
     def forward_nhwc(self, x):
         n, h, w, c = x.shape
-        L = _lib.lib()
         ho, wo = ((h + 1) // 2, (w + 1) // 2) if self._downsample else (h, w)
-        ws = runtime.workspace(L.sf_bottleneck_ws_bytes(self.cin, self.cout, n, h, w), x.device)
         out = torch.empty((n, ho, wo, self.cout), dtype=torch.float32, device=x.device)
-        _lib.check(L.sf_bottleneck_fwd(self.packed().struct, ptr(x), ptr(out), n, h, w, ptr(ws), ws.numel() * 4,
-                                       runtime.stream_ptr(x.device)), "bottleneck")
+        runtime.call("bottleneck", self.packed().struct, ptr(x), ptr(out), n, h, w, device=x.device,
+                     scratch=("bottleneck", self.cin, self.cout, n, h, w))
         return out
 
     def forward(self, *args):
         (x,) = args
         return runtime.to_nchw(self.forward_nhwc(runtime.to_nhwc(x)))
+
+
+def dist_head_nhwc(cw, enc, global_pool, clamp=None):
+    """``sf_dist_head_fwd``, the last layer of the distribution modules: [global average pool +] the packed 1x1 conv `cw` on enc
+    [n, h, w, C] -> [n, 1, 1, cout] ([n, h, w, cout] without the pool); ``clamp`` = (lo, hi) bounds the second half of the channels."""
+    n, h, w, c = enc.shape
+    ho, wo = (1, 1) if global_pool else (h, w)
+    out = torch.empty((n, ho, wo, cw.cout), dtype=torch.float32, device=enc.device)
+    lo, hi = (0.0, 0.0) if clamp is None else clamp
+    runtime.call("dist_head", cw, ptr(enc), ptr(out), n, h, w, int(global_pool), int(clamp is not None), float(lo), float(hi),
+                 device=enc.device, scratch=("dist_head", c, n))
+    return out
 
 
 class LayerNorm(nn.Module):
@@ -124,11 +134,9 @@ class Block(PackedModule):
 
     def forward_nhwc(self, x):
         n, h, w, c = x.shape
-        L = _lib.lib()
-        ws = runtime.workspace(L.sf_convnext_block_ws_bytes(c, n, h, w), x.device)
         out = torch.empty_like(x)
-        _lib.check(L.sf_convnext_block_fwd(self.packed().struct, ptr(x), ptr(out), n, h, w, ptr(ws),
-                                           ws.numel() * 4, runtime.stream_ptr(x.device)), "convnext_block")
+        runtime.call("convnext_block", self.packed().struct, ptr(x), ptr(out), n, h, w, device=x.device,
+                     scratch=("convnext_block", c, n, h, w))
         return out
 
     def forward(self, x):
@@ -177,11 +185,9 @@ class Bottleblock(PackedModule):
                 raise ValueError("a Bottleblock without projection adds its input: pass one tensor")
             st = _lib.BottleW.from_buffer_copy(st)
             st.c7.c0, st.c7.c1, st.proj.c0, st.proj.c1 = c0, c1, c0, c1
-        L = _lib.lib()
-        ws = runtime.workspace(L.sf_bottleblock_ws_bytes(self.in_channels, self.out_channels, n, h, w), x0.device)
         out = torch.empty((n, h, w, self.out_channels), dtype=torch.float32, device=x0.device)
-        _lib.check(L.sf_bottleblock_fwd(st, ptr(x0), ptr(x1), ptr(out), n, h, w, ptr(ws), ws.numel() * 4,
-                                        runtime.stream_ptr(x0.device)), "bottleblock")
+        runtime.call("bottleblock", st, ptr(x0), ptr(x1), ptr(out), n, h, w, device=x0.device,
+                     scratch=("bottleblock", self.in_channels, self.out_channels, n, h, w))
         return out
 
     def forward(self, *args):
@@ -254,27 +260,25 @@ class DeepLabHead(nn.Sequential, PackedModule):
         s.C, s.hid = C, hid
         return pk
 
-    def forward_nhwc(self, x, st=None):
+    def _run(self, name, st, x, out, *layout):
+        """``sf_<name>_fwd`` of the head (both forms take the same scratch) with the packed struct `st`, this module's own for None;
+        out None: [n, h, w, classes] is allocated."""
         n, h, w, c = x.shape
-        L = _lib.lib()
         st = self.packed().struct if st is None else st
-        ws = runtime.workspace(L.sf_deeplab_head_ws_bytes(c, self.hidden_channel, n, h, w), x.device)
-        out = torch.empty((n, h, w, st.cls.cout), dtype=torch.float32, device=x.device)
-        _lib.check(L.sf_deeplab_head_fwd(st, ptr(x), ptr(out), n, h, w, ptr(ws), ws.numel() * 4,
-                                         runtime.stream_ptr(x.device)), "deeplab_head")
+        if out is None:
+            out = torch.empty((n, h, w, st.cls.cout), dtype=torch.float32, device=x.device)
+        runtime.call(name, st, ptr(x), ptr(out), n, h, w, *layout, device=x.device,
+                     scratch=("deeplab_head", c, self.hidden_channel, n, h, w))
         return out
+
+    def forward_nhwc(self, x, st=None):
+        return self._run("deeplab_head", st, x, None)
 
     def forward_nhwc_into_planar(self, x, out, group, stride_major, stride_minor, st=None):
         """The same head, its classifier writing the reference's planar layout itself: image i of x [n, h, w, C] lands as
         [cout][h][w] planes at ``out.data_ptr() + 4 * ((i // group) * stride_major + (i % group) * stride_minor)`` (strides in
         floats) — FuturePredictionODE writes frames (t, b) straight into its [B, T, C, H, W] result, no transpose launches."""
-        n, h, w, c = x.shape
-        L = _lib.lib()
-        st = self.packed().struct if st is None else st
-        ws = runtime.workspace(L.sf_deeplab_head_ws_bytes(c, self.hidden_channel, n, h, w), x.device)
-        _lib.check(L.sf_deeplab_head_planar_fwd(st, ptr(x), ptr(out), n, h, w, int(group), int(stride_major), int(stride_minor),
-                                                ptr(ws), ws.numel() * 4, runtime.stream_ptr(x.device)), "deeplab_head_planar")
-        return out
+        return self._run("deeplab_head_planar", st, x, out, int(group), int(stride_major), int(stride_minor))
 
     def forward(self, x):
         return runtime.to_nchw(self.forward_nhwc(runtime.to_nhwc(x)))

@@ -84,11 +84,9 @@ class SmallEncoder(PackedModule):
 
     def forward_nhwc(self, x):
         n, h, w, c = x.shape
-        L = _lib.lib()
-        ws = runtime.workspace(L.sf_small_encoder_ws_bytes(max(c, self.nh), self.nf, n, h, w), x.device)
         out = torch.empty((n, (h // 2) // 2, (w // 2) // 2, self.nh), dtype=torch.float32, device=x.device)
-        _lib.check(L.sf_small_encoder_fwd(self.packed().struct, ptr(x), ptr(out), n, h, w, ptr(ws), ws.numel() * 4,
-                                          runtime.stream_ptr(x.device)), "small_encoder")
+        runtime.call("small_encoder", self.packed().struct, ptr(x), ptr(out), n, h, w, device=x.device,
+                     scratch=("small_encoder", max(c, self.nh), self.nf, n, h, w))
         return out
 
     def forward(self, x, return_skip=False):
@@ -125,11 +123,9 @@ class SmallDecoder(PackedModule):
 
     def forward_nhwc(self, z):
         n, h, w, c = z.shape
-        L = _lib.lib()
-        ws = runtime.workspace(L.sf_small_decoder_ws_bytes(max(c, self.nh), self.nf, n, h, w), z.device)
         out = torch.empty((n, 4 * h, 4 * w, self.nh), dtype=torch.float32, device=z.device)
-        _lib.check(L.sf_small_decoder_fwd(self.packed().struct, ptr(z), ptr(out), n, h, w, ptr(ws), ws.numel() * 4,
-                                          runtime.stream_ptr(z.device)), "small_decoder")
+        runtime.call("small_decoder", self.packed().struct, ptr(z), ptr(out), n, h, w, device=z.device,
+                     scratch=("small_decoder", max(c, self.nh), self.nf, n, h, w))
         return out
 
     def forward(self, z, skip=None, sigmoid=False):

@@ -14,10 +14,10 @@ from .. import _lib, packing, runtime
 from ..runtime import PackedModule, ptr
 
 
-def pack_gru(pk, update, reset, tilde, cx, ch, decoder=None, fold_dup=False, gate_bias=0.0):
+def pack_gru(pk, update, reset, tilde, cx, ch, decoder=None, fold_dup=False, gate_bias=0.0, tilde_bn=None):
     """Pack a conv-GRU cell: gates = [update; reset] stacked on the output-channel axis.  ``gate_bias`` is the
     reference's ``gru_bias_init`` — a constant added to both gate pre-activations (temporal.py:50-51) — folded into the
-    gates' bias."""
+    gates' bias.  ``tilde_bn``: the candidate is conv + this BatchNorm (folded) + ReLU, not a plain biased conv."""
     s = _lib.GruW()
     wg = torch.cat([update.weight, reset.weight], 0)
     bg = torch.cat([update.bias, reset.bias], 0) + float(gate_bias)
@@ -25,10 +25,25 @@ def pack_gru(pk, update, reset, tilde, cx, ch, decoder=None, fold_dup=False, gat
         s.gates = packing.conv_w(pk, wg, ch, 0, bias=bg, act="sigmoid", fold_dup=True)
     else:
         s.gates = packing.conv_w(pk, wg, cx, ch, bias=bg, act="sigmoid")
-    s.cand = packing.conv_w(pk, tilde.weight, cx, ch, bias=tilde.bias)
+    if tilde_bn is None:
+        s.cand = packing.conv_w(pk, tilde.weight, cx, ch, bias=tilde.bias)
+    else:
+        sc, bi = packing.bn_fold(tilde_bn)
+        s.cand = packing.conv_w(pk, tilde.weight, cx, ch, scale=sc, bias=bi, act="relu")
     if decoder is not None:
         s.decoder = packing.conv_w(pk, decoder.weight, ch, bias=decoder.bias)
     return s
+
+
+def pack_gru_block(mod):
+    """``_pack`` of the cells whose candidate is a ConvBlock (conv + BatchNorm + ReLU): BEVerse ``SpatialGRU`` / ``GRUCell`` and the
+    single-branch cells of temporal_ode_bayes.py."""
+    if mod.training:
+        raise RuntimeError("streamingflow_amd is inference-only: call .eval()")
+    pk = packing.Pack(None)
+    pk.struct = pack_gru(pk, mod.conv_update, mod.conv_reset, mod.conv_state_tilde.conv, mod.input_size, mod.hidden_size,
+                         gate_bias=mod.gru_bias_init, tilde_bn=mod.conv_state_tilde.norm)
+    return pk
 
 
 class SpatialGRU(PackedModule):
@@ -61,65 +76,62 @@ class SpatialGRU(PackedModule):
         one = x.dim() == 4
         if one:
             x, state = x[:, None], state[None]
-        T, B, h, w, _ = x.shape
-        L = _lib.lib()
-        ws = runtime.workspace(L.sf_spatial_gru_ws_bytes(self.hidden_size, B, h, w), x.device)
-        out = torch.empty((T, B, h, w, self.input_size if st is None else self.hidden_size), dtype=torch.float32, device=x.device)
-        _lib.check(L.sf_spatial_gru_fwd(self.packed().struct if st is None else st, ptr(x), ptr(state), ptr(out), T, B, h, w, ptr(ws),
-                                        ws.numel() * 4, runtime.stream_ptr(x.device)), "spatial_gru")
+        if st is None:
+            out = spatial_gru_nhwc(self.packed().struct, x, state, self.input_size, self.hidden_size)
+        else:
+            out = spatial_gru_nhwc(st, x, state, self.hidden_size, self.hidden_size)
         return out[:, 0] if one else out
 
     def gru_cell(self, x, state):
         """One cell update on NCHW tensors (temporal.py:44-57)."""
         runtime.require_cuda(x, state)
-        xn, sn = runtime.to_nhwc(x), runtime.to_nhwc(state)
-        n, h, w, _ = xn.shape
-        L = _lib.lib()
-        ws = runtime.workspace(L.sf_gru_cell_ws_bytes(self.hidden_size, n, h, w), x.device)
-        out = torch.empty_like(sn)
-        _lib.check(L.sf_gru_cell_fwd(self.packed().struct, ptr(xn), ptr(sn), ptr(out), n, h, w, ptr(ws), ws.numel() * 4,
-                                     runtime.stream_ptr(x.device)), "gru_cell")
-        return runtime.to_nchw(out)
+        return runtime.to_nchw(gru_cell_nhwc(self.packed().struct, runtime.to_nhwc(x), runtime.to_nhwc(state)))
 
     def forward(self, x, state=None):
         assert len(x.size()) == 5, 'Input tensor must be BxTxCxHxW.'
         runtime.require_cuda(x, state)
         b, T, c, h, w = x.shape
-        xn = runtime.to_nhwc(x.reshape(b * T, c, h, w)).view(b, T, h, w, c).permute(1, 0, 2, 3, 4).contiguous()
+        xn = runtime.frames_to_nhwc(x)
         s0 = (torch.zeros((b, h, w, self.hidden_size), dtype=torch.float32, device=x.device) if state is None
               else runtime.to_nhwc(state))
-        out = self.forward_nhwc(xn, s0).permute(1, 0, 2, 3, 4).reshape(b * T, h, w, self.input_size)
-        return runtime.to_nchw(out).view(b, T, self.input_size, h, w)
+        return runtime.frames_to_nchw(self.forward_nhwc(xn, s0))
 
 
 # ---- building blocks on NHWC tensors (shared with the dual cells of temporal_ode_bayes.py) ---------------------------
 
-def gru_cell_nhwc(gw, x, s):
-    """One conv-GRU update (1 - u) * s + u * h~ (temporal.py:126-152): x [n, h, w, Cx], s [n, h, w, C]."""
+def gru_cell_nhwc(gw, x, s, out=None, ode=False):
+    """One conv-GRU update (1 - u) * s + u * h~ (temporal.py:126-152), ``sf_gru_cell_fwd``: x [n, h, w, Cx], s [n, h, w, C] -> [n, h, w, C]
+    (into `out` when given).  ``ode``: the derivative u * (h~ - s) instead (``sf_gru_ode_cell_fwd``, same scratch)."""
     n, h, w, C = s.shape
-    L = _lib.lib()
-    ws = runtime.workspace(L.sf_gru_cell_ws_bytes(C, n, h, w), s.device)
-    out = torch.empty_like(s)
-    _lib.check(L.sf_gru_cell_fwd(gw, ptr(x), ptr(s), ptr(out), n, h, w, ptr(ws), ws.numel() * 4, runtime.stream_ptr(s.device)),
-               "gru_cell")
+    if out is None:
+        out = torch.empty((n, h, w, C), dtype=torch.float32, device=s.device)
+    runtime.call("gru_ode_cell" if ode else "gru_cell", gw, ptr(x), ptr(s), ptr(out), n, h, w, device=s.device,
+                 scratch=("gru_cell", C, n, h, w))
+    return out
+
+
+def spatial_gru_nhwc(gw, x, state, c_out, hidden):
+    """The cell over the frames of x [T, B, h, w, Cx] from state [B, h, w, hidden] (``sf_spatial_gru_fwd``) -> [T, B, h, w, c_out]:
+    each state through the 1x1 decoder of ``gw``, or the states themselves (c_out = hidden) when it has none."""
+    T, B, h, w, _ = x.shape
+    out = torch.empty((T, B, h, w, c_out), dtype=torch.float32, device=x.device)
+    runtime.call("spatial_gru", gw, ptr(x), ptr(state), ptr(out), T, B, h, w, device=x.device, scratch=("spatial_gru", hidden, B, h, w))
     return out
 
 
 def conv_nhwc(cw, x):
     n, h, w, _ = x.shape
     out = torch.empty((n, h, w, cw.cout), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().sf_conv2d_fwd(cw, ptr(x), None, None, ptr(out), n, h, w, 0, runtime.stream_ptr(x.device)), "conv2d")
+    runtime.call("conv2d", cw, ptr(x), None, None, ptr(out), n, h, w, 0, device=x.device)
     return out
 
 
 def trust_mix_nhwc(dw, r1, r2):
     """softmax(trusting_gate(cat[r1, r2])) mixes the two branch states: r2 * g0 + r1 * g1 (temporal.py:118-122)."""
     n, h, w, C = r1.shape
-    L = _lib.lib()
-    ws = runtime.workspace(L.sf_dual_cell_ws_bytes(C, n, h, w), r1.device)
     out = torch.empty_like(r1)
-    _lib.check(L.sf_trust_mix_fwd(dw, ptr(r1), ptr(r2), None, ptr(out), 0, None, None, n, h, w, ptr(ws), ws.numel() * 4,
-                                  runtime.stream_ptr(r1.device)), "trust_mix")
+    runtime.call("trust_mix", dw, ptr(r1), ptr(r2), None, ptr(out), 0, None, None, n, h, w, device=r1.device,
+                 scratch=("dual_cell", C, n, h, w))
     return out
 
 

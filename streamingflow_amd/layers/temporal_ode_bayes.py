@@ -20,7 +20,7 @@ from .. import _lib, packing, runtime, schedule as sched
 from ..runtime import PackedModule, ptr
 from .convolutions import Bottleblock
 from .res_models import ConvNet, SmallDecoder, SmallEncoder
-from .temporal import pack_gru
+from .temporal import conv_nhwc, gru_cell_nhwc, pack_gru, pack_gru_block, pack_trust_gate, trust_mix_nhwc
 
 
 class _SingleGRU(PackedModule):
@@ -40,30 +40,11 @@ class _SingleGRU(PackedModule):
         self.conv_reset = nn.Conv2d(cat, hidden_size, kernel_size=3, bias=True, padding=1)
         self.conv_state_tilde = ConvBlock(cat, hidden_size, kernel_size=3, bias=False, norm=norm, activation=activation)
 
-    def _pack(self):
-        if self.training:
-            raise RuntimeError("streamingflow_amd is inference-only: call .eval()")
-        pk = packing.Pack(_lib.GruW())
-        s = pk.struct
-        wg = torch.cat([self.conv_update.weight, self.conv_reset.weight], 0)
-        bg = torch.cat([self.conv_update.bias, self.conv_reset.bias], 0) + float(self.gru_bias_init)     # :54-55
-        s.gates = packing.conv_w(pk, wg, self.input_size, self.hidden_size, bias=bg, act="sigmoid")
-        sc, bi = packing.bn_fold(self.conv_state_tilde.norm)
-        s.cand = packing.conv_w(pk, self.conv_state_tilde.conv.weight, self.input_size, self.hidden_size, scale=sc,
-                                bias=bi, act="relu")
-        return pk
+    _pack = pack_gru_block
 
     def forward(self, x, state):
         runtime.require_cuda(x, state)
-        xn, sn = runtime.to_nhwc(x), runtime.to_nhwc(state)
-        n, h, w, _ = xn.shape
-        L = _lib.lib()
-        ws = runtime.workspace(L.sf_gru_cell_ws_bytes(self.hidden_size, n, h, w), x.device)
-        out = torch.empty_like(sn)
-        fn = L.sf_gru_ode_cell_fwd if self.ode else L.sf_gru_cell_fwd
-        _lib.check(fn(self.packed().struct, ptr(xn), ptr(sn), ptr(out), n, h, w, ptr(ws), ws.numel() * 4,
-                      runtime.stream_ptr(x.device)), "single_gru_cell")
-        return runtime.to_nchw(out)
+        return runtime.to_nchw(gru_cell_nhwc(self.packed().struct, runtime.to_nhwc(x), runtime.to_nhwc(state), ode=self.ode))
 
 
 class SpatialGRUODECell(_SingleGRU):
@@ -108,24 +89,14 @@ class _DualCell(PackedModule):
         s.gates1_x = packing.conv_w(pk, wg[:, :C], C, bias=bg, act="sigmoid")
         s.gates1_s = packing.conv_w(pk, wg[:, C:], C)
         s.dec2 = packing.conv_w(pk, self.conv_decoder_2.weight, C, bias=self.conv_decoder_2.bias)
-        bb = self.trusting_gate[0]
-        L = bb.layers
-        s.tg7 = packing.conv_w(pk, L[0].weight, C, C, scale=L[1].weight, bias=L[1].bias)
-        s.tg1 = packing.conv_w(pk, L[3].weight, C, scale=L[4].weight, bias=L[4].bias)
-        s.tg3 = packing.conv_w(pk, L[6].weight, C, scale=L[7].weight, bias=L[7].bias)
-        s.tgproj = packing.conv_w(pk, bb.projection[0].weight, C, C)
-        s.w_logit = pk.hold(self.trusting_gate[1].weight.reshape(2, C))
-        s.C = C
+        pack_trust_gate(pk, s, self.trusting_gate, C)
         return pk
 
     def run_nhwc(self, x, s, out, derivative, base=None, coef=None):
         """x, s, out: [B, h, w, C] (B samples processed as one pixel space)."""
         B, h, w, C = s.shape
-        L = _lib.lib()
-        ws = runtime.workspace(L.sf_dual_cell_ws_bytes(C, B, h, w), s.device)
-        _lib.check(L.sf_dual_cell_fwd(self.packed().struct, ptr(x), ptr(s), ptr(out), int(derivative), ptr(base),
-                                      ptr(coef), None, 0, B, h, w, ptr(ws), ws.numel() * 4,
-                                      runtime.stream_ptr(s.device)), "dual_cell")
+        runtime.call("dual_cell", self.packed().struct, ptr(x), ptr(s), ptr(out), int(derivative), ptr(base), ptr(coef), None, 0,
+                     B, h, w, device=s.device, scratch=("dual_cell", C, B, h, w))
         return out
 
     def _general_pack(self):
@@ -148,7 +119,6 @@ class _DualCell(PackedModule):
         """state [b, n_present > 1, C, h, w] (temporal_ode_bayes.py:101-131 / :248-275): branch 2's hidden state starts from
         the first frame (the ODE cell warms it up over the present frames), both branches start from the last one.
         Unused by the reference's forward path."""
-        from .temporal import conv_nhwc, gru_cell_nhwc, trust_mix_nhwc
         g1, g2, dec2 = self._general_pack()
         n = state.shape[1]
         frames = [runtime.to_nhwc(state[:, t]) for t in range(n)]
@@ -302,10 +272,8 @@ class NNFOwithBayesianJumps(nn.Module):
         eps = self._draw_eps(self.noise, 1, B, h, w, x.device)
         p = torch.empty_like(sn)
         q = torch.empty((B, h, w, 2 * C), dtype=torch.float32, device=x.device)
-        L = _lib.lib()
-        ws = runtime.workspace(L.sf_infer_state_ws_bytes(C, B, h, w), x.device)
-        _lib.check(L.sf_infer_state_fwd(self.p_model.packed().struct, ptr(sn), ptr(eps), ptr(p), ptr(q), B, h, w,
-                                        ptr(ws), ws.numel() * 4, runtime.stream_ptr(x.device)), "infer_state")
+        runtime.call("infer_state", self.p_model.packed().struct, ptr(sn), ptr(eps), ptr(p), ptr(q), B, h, w, device=x.device,
+                     scratch=("infer_state", C, B, h, w))
         return runtime.to_nchw(p), runtime.to_nchw(q)
 
     def ode_step(self, state, input, delta_t, current_time):
@@ -318,12 +286,9 @@ class NNFOwithBayesianJumps(nn.Module):
         coef = torch.from_numpy(sc.coef_array()).to(dev)
         eps = self._draw_eps(self.noise, sched.DRAWS_PER_STEP[self.solver], B, h, w, dev)
         s_out, p_out = torch.empty_like(sn), torch.empty_like(pn)
-        L = _lib.lib()
-        ws = runtime.workspace(L.sf_ode_step_ws_bytes(C, B, h, w), dev)
-        _lib.check(L.sf_ode_step_fwd(self.gru_c.packed().struct, self.p_model.packed().struct,
-                                     _lib.SOLVER[self.solver], int(bool(self.impute)), ptr(sn), ptr(pn), ptr(coef),
-                                     ptr(eps), ptr(s_out), ptr(p_out), B, h, w, ptr(ws), ws.numel() * 4,
-                                     runtime.stream_ptr(dev)), "ode_step")
+        runtime.call("ode_step", self.gru_c.packed().struct, self.p_model.packed().struct, _lib.SOLVER[self.solver],
+                     int(bool(self.impute)), ptr(sn), ptr(pn), ptr(coef), ptr(eps), ptr(s_out), ptr(p_out), B, h, w, device=dev,
+                     scratch=("ode_step", C, B, h, w))
         current_time = current_time + delta_t
         return (runtime.to_nchw(s_out), runtime.to_nchw(p_out), current_time,
                 torch.tensor([0], device=dev, dtype=torch.float64), torch.tensor([0], device=dev, dtype=torch.float32))
@@ -331,7 +296,8 @@ class NNFOwithBayesianJumps(nn.Module):
     # ---- the rollout ----------------------------------------------------------------------------
     def _enqueue(self, sc, hx, eps, philox, coef, per_image, out, final, B, h, w, ws, device, resume=None):
         """The C call of a whole rollout (`resume` None) or of one segment of a session (`resume` = state_in, p_in, carry_in,
-        draw_base, p_out, carry_out: include/sfnative.h).  The noise is the `philox` record when there is one, else the `eps` rows."""
+        draw_base, p_out, carry_out: include/sfnative.h).  The noise is the `philox` record when there is one, else the `eps` rows;
+        `ws` is the scratch as ``runtime.call`` takes it: the size query (eager) or a graph's static buffer."""
         L = _lib.lib()
         if resume is None:
             fn, block = (L.sf_nnfo_rollout_fwd if philox is None else L.sf_nnfo_rollout_philox_fwd), ()
@@ -341,10 +307,10 @@ class NNFOwithBayesianJumps(nn.Module):
             block = (ptr(state_in), ptr(p_in), ptr(carry_in), int(draw_base), ptr(p_out), ptr(carry_out))
         ops = sc.ops_array()
         sel = np.asarray(sc.sel_nops, dtype=np.int32)
-        _lib.check(fn(self.gru_c.packed().struct, self.gru_obs.gru_d.packed().struct, self.p_model.packed().struct,
-                      _lib.SOLVER[self.solver], int(bool(self.impute)), ops.ctypes.data_as(_lib.i32p), len(sc.ops), ptr(hx),
-                      ptr(eps if philox is None else philox), ptr(coef), int(per_image), sel.ctypes.data_as(_lib.i32p), len(sel),
-                      ptr(out), ptr(final), *block, B, h, w, ptr(ws), ws.numel() * 4, runtime.stream_ptr(device)), fn.__name__[3:-4])
+        runtime.call(fn, self.gru_c.packed().struct, self.gru_obs.gru_d.packed().struct, self.p_model.packed().struct,
+                     _lib.SOLVER[self.solver], int(bool(self.impute)), ops.ctypes.data_as(_lib.i32p), len(sc.ops), ptr(hx),
+                     ptr(eps if philox is None else philox), ptr(coef), int(per_image), sel.ctypes.data_as(_lib.i32p), len(sel),
+                     ptr(out), ptr(final), *block, B, h, w, device=device, scratch=ws)
 
     def _pack_generations(self):
         """The packed copies a captured graph holds raw pointers into: a graph is stale once any of the three was rebuilt."""
@@ -425,8 +391,7 @@ class NNFOwithBayesianJumps(nn.Module):
         dev = hx_obs.device
         out = torch.empty((len(s0.sel_nops), B, h, w, C), dtype=torch.float32, device=dev)
         final = torch.empty((B, h, w, C), dtype=torch.float32, device=dev)
-        ws = runtime.workspace(_lib.lib().sf_nnfo_rollout_ws_bytes(C, B, h, w), dev)
-        self._enqueue(s0, hx_obs, eps, philox, coef, per_image, out, final, B, h, w, ws, dev)
+        self._enqueue(s0, hx_obs, eps, philox, coef, per_image, out, final, B, h, w, ("nnfo_rollout", C, B, h, w), dev)
         return out, final
 
     def _run_graph(self, s0, per_image, hx_obs, eps, philox, coef):

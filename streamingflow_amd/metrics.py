@@ -39,7 +39,7 @@ def confusion(pred, target, K):
         raise ValueError("prediction and target must have the same number of elements")
     hist = torch.empty((K, K), dtype=torch.int64, device=a.device)
     flag = torch.empty((1,), dtype=torch.int32, device=a.device)
-    _lib.check(_lib.lib().sf_confusion_fwd(ptr(a), ptr(b), a.numel(), int(K), ptr(hist), ptr(flag), runtime.stream_ptr(a.device)), "confusion")
+    runtime.call("confusion", ptr(a), ptr(b), a.numel(), int(K), ptr(hist), ptr(flag), device=a.device)
     return hist, flag
 
 
@@ -51,8 +51,7 @@ def frame_confusions(pred, target, n_frames, K):
         raise ValueError("prediction and target must hold n_frames equally sized maps")
     hist = torch.empty((n_frames, K, K), dtype=torch.int64, device=a.device)
     flag = torch.empty((1,), dtype=torch.int32, device=a.device)
-    _lib.check(_lib.lib().sf_confusion_frames_fwd(ptr(a), ptr(b), a.numel() // n_frames, int(n_frames), int(K), ptr(hist), ptr(flag),
-                                                  runtime.stream_ptr(a.device)), "confusion_frames")
+    runtime.call("confusion_frames", ptr(a), ptr(b), a.numel() // n_frames, int(n_frames), int(K), ptr(hist), ptr(flag), device=a.device)
     return hist, flag
 
 
@@ -169,15 +168,13 @@ class PanopticMetric(_Accumulator):
         if any(getattr(self, n).dtype != torch.float32 for n in self._counter_names):
             raise RuntimeError("PanopticMetric: the counters must stay float32")
         hist, flag = frame_confusions(pred_instance, gt_instance, batch * steps, K)
-        L = _lib.lib()
-        need = L.sf_panoptic_score_ws_bytes(batch, steps, K)
+        need = _lib.lib().sf_panoptic_score_ws_bytes(batch, steps, K)      # int32 / fp32 parts: a multiple of 4
         if need == 0:
             raise ValueError("max_instances: batch * time * (max_instances + 1) must stay below 2^31")
-        ws = torch.empty((need + 3) // 4, dtype=torch.int32, device=dev)
+        ws = torch.empty(need // 4, dtype=torch.int32, device=dev)
         track = bool(self.temporally_consistent) and THING_CLASS == self.vehicles_id
-        _lib.check(L.sf_panoptic_score_fwd(ptr(hist), h * w, batch, steps, K, self.n_classes, int(track), ptr(flag), ptr(self.iou),
-                                           ptr(self.true_positive), ptr(self.false_positive), ptr(self.false_negative), ptr(self._errors),
-                                           ptr(ws), need, runtime.stream_ptr(dev)), "panoptic_score")
+        runtime.call("panoptic_score", ptr(hist), h * w, batch, steps, K, self.n_classes, int(track), ptr(flag), ptr(self.iou),
+                     ptr(self.true_positive), ptr(self.false_positive), ptr(self.false_negative), ptr(self._errors), device=dev, scratch=ws)
 
     def reset(self):
         super().reset()
@@ -320,9 +317,9 @@ class PlanningMetric(_Accumulator):
         B, T, s = trajs.shape
         if T != self.n_future or s < 2:
             raise ValueError("expected [B, %d, >= 2] trajectories" % self.n_future)
-        _lib.check(_lib.lib().sf_plan_metric_fwd(ptr(trajs), ptr(gt_trajs), s, ptr(seg), ptr(self._rc), self._rc.shape[0], ptr(self.dx), ptr(self.bx),
-                                                 B, T, seg.shape[-2], seg.shape[-1], ptr(self.obj_col), ptr(self.obj_box_col), ptr(self.L2),
-                                                 ptr(self.total), runtime.stream_ptr(trajs.device)), "plan_metric")
+        runtime.call("plan_metric", ptr(trajs), ptr(gt_trajs), s, ptr(seg), ptr(self._rc), self._rc.shape[0], ptr(self.dx), ptr(self.bx),
+                     B, T, seg.shape[-2], seg.shape[-1], ptr(self.obj_col), ptr(self.obj_box_col), ptr(self.L2), ptr(self.total),
+                     device=trajs.device)
 
     def compute(self):
         return {"obj_col": self.obj_col / self.total, "obj_box_col": self.obj_box_col / self.total, "L2": self.L2 / self.total}

@@ -2,7 +2,7 @@
 
 Same constructor, ``forward`` signature, output dict and ``state_dict`` keys as the reference
 (including the torchvision ResNet-18 names ``layer{1,2,3}.{0,1}.{conv1,bn1,conv2,bn2,downsample.{0,1}}``).
-Every convolution runs through ``sf_conv2d_ex_fwd`` (implicit-GEMM fp32 MFMA, BatchNorm folded into
+Every convolution runs through ``runtime.conv2d_ex`` (implicit-GEMM fp32 MFMA, BatchNorm folded into
 the epilogue, residual add + ReLU fused); differences in *how* the same function is computed:
 
 * ``UpsamplingAdd`` (convolutions.py:204-215): the 1x1 conv + BatchNorm run BEFORE the bilinear x2
@@ -16,7 +16,7 @@ Evaluation mode only (BatchNorm running statistics are folded); CPU tensors rais
 import torch
 import torch.nn as nn
 
-from .. import _lib, packing, runtime
+from .. import packing, runtime
 from ..runtime import PackedModule, ptr
 
 
@@ -131,26 +131,18 @@ class Decoder(PackedModule):
     # ---- device helpers -----------------------------------------------------------------------------
     @staticmethod
     def _conv(w, x, n, H, W_, in_cs=None, in_co=0, add=None, act_after_add=False, out=None):
-        L = _lib.lib()
-        dev = x.device
         Ho = (H + 2 * w.pad - w.dil * (w.kh - 1) - 1) // w.stride + 1
         Wo = (W_ + 2 * w.pad - w.dil * (w.kw - 1) - 1) // w.stride + 1
         if out is None:
-            out = torch.empty((n, Ho, Wo, w.cout), dtype=torch.float32, device=dev)
-        ws = runtime.workspace(L.sf_conv2d_ex_ws_bytes(), dev)
-        cs = in_cs if in_cs is not None else w.c0
-        xin = C_void(x, in_co)
-        _lib.check(L.sf_conv2d_ex_fwd(_lib.C.byref(w), xin, cs, None, 0, ptr(add), w.cout if add is not None else 0,
-                                      int(act_after_add), ptr(out), w.cout, 0, n, H, W_, 0, ptr(ws), ws.numel() * 4,
-                                      runtime.stream_ptr(dev)), "conv2d_ex")
+            out = torch.empty((n, Ho, Wo, w.cout), dtype=torch.float32, device=x.device)
+        runtime.conv2d_ex(w, x, in_cs if in_cs is not None else w.c0, in_co, n, H, W_, out, w.cout, 0, add=add,
+                          add_cs=w.cout if add is not None else 0, act_after_add=act_after_add)
         return out, Ho, Wo
 
     def _run(self, x):
         """x [n, H, W, C] NHWC -> (shared feature map [n, H, W, C], dict key -> [n, H, W, k4] head outputs)."""
         W = self.packed().struct
         n, H, Wd, C = x.shape
-        L = _lib.lib()
-        st = runtime.stream_ptr(x.device)
         y, h, w = self._conv(W["first"], x, n, H, Wd)
         skips = {1: (x, H, Wd)}
         for ln, layer, tag in (("layer1", self.layer1, 2), ("layer2", self.layer2, 3), ("layer3", self.layer3, None)):
@@ -168,7 +160,7 @@ class Decoder(PackedModule):
                 raise RuntimeError("Decoder needs a BEV size divisible by 8 (UpsamplingAdd x2 must meet its skip)")
             lo, _, _ = self._conv(W[name], y, n, h, w)
             y = torch.empty_like(sk)
-            _lib.check(L.sf_upsample_bilinear2_add_fwd(ptr(lo), ptr(sk), ptr(y), n, h, w, lo.shape[-1], st), "upsample_add")
+            runtime.call("upsample_bilinear2_add", ptr(lo), ptr(sk), ptr(y), n, h, w, lo.shape[-1], device=x.device)
             h, w = hs, ws_
         return y
 
@@ -202,6 +194,4 @@ class Decoder(PackedModule):
         return out
 
 
-def C_void(t, chan_offset=0):
-    """Pointer to channel `chan_offset` of an NHWC tensor."""
-    return _lib.C.c_void_p(t.data_ptr() + 4 * int(chan_offset))
+C_void = runtime.ptr_at      # the name this helper had here, kept for code outside the package that imports it

@@ -1,13 +1,11 @@
 """MI355X-native counterpart of streamingflow/models/distributions.py (``DistributionModule``
 :7-51, ``DistributionEncoder`` :54-68).  The reference imports but never instantiates it
 (SURVEY.md §0); kept for signature / state_dict compatibility: all three methods."""
-import ctypes
-
 import torch
 import torch.nn as nn
 
-from .. import _lib, packing, runtime
-from ..layers.convolutions import Bottleneck
+from .. import packing, runtime
+from ..layers.convolutions import Bottleneck, dist_head_nhwc
 from ..runtime import PackedModule, ptr
 
 
@@ -61,17 +59,10 @@ class DistributionModule(PackedModule):
         b, s = s_t.shape[:2]
         assert s == 1
         runtime.require_cuda(s_t)
-        L = _lib.lib()
         if self.method == "BERNOULLI":
             enc = self.encoder[0].forward_nhwc(runtime.to_nhwc(s_t[:, 0]))
             out = torch.empty_like(enc)
-            _lib.check(L.sf_logsigmoid_fwd(ptr(enc), ptr(out), enc.numel(), runtime.stream_ptr(enc.device)), "logsigmoid")
+            runtime.call("logsigmoid", ptr(enc), ptr(out), enc.numel(), device=enc.device)
             return runtime.to_nchw(out)
-        enc = self.encoder.forward_nhwc(runtime.to_nhwc(s_t[:, 0]))
-        n, h, w, c = enc.shape
-        st = self.packed().struct
-        ws = runtime.workspace(L.sf_dist_head_ws_bytes(c, n), enc.device)
-        out = torch.empty((n, 1, 1, st.cout), dtype=torch.float32, device=enc.device)
-        _lib.check(L.sf_dist_head_fwd(ctypes.byref(st), ptr(enc), ptr(out), n, h, w, 1, 0, 0.0, 0.0,
-                                      ptr(ws), ws.numel() * 4, runtime.stream_ptr(enc.device)), "dist_head")
-        return out.view(b, 1, st.cout)[:, :, : self.n_out]
+        out = dist_head_nhwc(self.packed().struct, self.encoder.forward_nhwc(runtime.to_nhwc(s_t[:, 0])), True)
+        return out.view(b, 1, -1)[:, :, : self.n_out]

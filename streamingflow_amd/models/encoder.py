@@ -198,13 +198,11 @@ class Encoder(nn.Module):
         hi, lo = runtime.to_nhwc(reduction_hi), runtime.to_nhwc(reduction_lo)
         pk = self.packed(H, W)
         dev = hi.device
-        L = _lib.lib()
-        ws = runtime.workspace(L.sf_camera_neck_ws_bytes(self.c_hi, self.c_lo, self.C, self.D, 2 * HIDDEN, n, H, W), dev)
         rays = torch.empty((n * 4 * H * W, self.C), dtype=torch.float32, device=dev)
         logits = torch.empty((n, self.D, 4 * H * W), dtype=torch.float32, device=dev)
         prob = torch.empty_like(logits)
-        _lib.check(L.sf_camera_neck_fwd(pk.struct, pk.convs, ptr(hi), ptr(lo), ptr(rays), ptr(logits), ptr(prob), n, H, W, ptr(ws),
-                                        ws.numel() * 4, runtime.stream_ptr(dev)), "camera_neck")
+        runtime.call("camera_neck", pk.struct, pk.convs, ptr(hi), ptr(lo), ptr(rays), ptr(logits), ptr(prob), n, H, W, device=dev,
+                     scratch=("camera_neck", self.c_hi, self.c_lo, self.C, self.D, 2 * HIDDEN, n, H, W))
         return rays, logits, prob
 
     def neck(self, reduction_hi, reduction_lo):

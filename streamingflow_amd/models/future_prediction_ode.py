@@ -127,8 +127,8 @@ class FuturePredictionODE(nn.Module):
         for o, (src, i) in enumerate(src0):
             t = states[src]
             first = t[b0, i]
-            _lib.check(L.sf_nchw_to_nhwc_strided(runtime.ptr(first), t.shape[1] * C * H * W, runtime.ptr(obs[o]), C * H * W, B, C, H * W,
-                                                 runtime.stream_ptr(dev)), "nchw_to_nhwc_strided")
+            runtime.call(L.sf_nchw_to_nhwc_strided, runtime.ptr(first), t.shape[1] * C * H * W, runtime.ptr(obs[o]), C * H * W, B, C, H * W,
+                         device=dev)
         return obs
 
     def _run_group(self, frames, scs, sources=None, states=None, out=None, members=None):
@@ -158,12 +158,7 @@ class FuturePredictionODE(nn.Module):
         y = self.head_nhwc(x)                                   # [T, B, H, W, C]
         T, _, H, W, C = y.shape
         if whole:          # the group is the whole batch, in order: write [B, T, C, H, W] directly
-            res = torch.empty((B, T, C, H, W), dtype=torch.float32, device=y.device)
-            L = _lib.lib()
-            for t in range(T):                                  # frame (t, b) -> res[b, t]: one strided transpose per t
-                _lib.check(L.sf_nhwc_to_nchw_strided(runtime.ptr(y[t]), H * W * C, runtime.ptr(res[0, t]), T * C * H * W, B, C,
-                                                     H * W, runtime.stream_ptr(y.device)), "nhwc_to_nchw_strided")
-            return res
+            return runtime.frames_to_nchw_strided(y)
         res = runtime.to_nchw(y.view(T * B, H, W, C))
         return res.view(T, B, *res.shape[1:]).permute(1, 0, 2, 3, 4)
 

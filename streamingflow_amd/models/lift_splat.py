@@ -108,11 +108,8 @@ class LiftSplat(nn.Module):
         order = torch.empty((n,), dtype=torch.int32, device=dev)
         start = torch.empty((ncells + 1,), dtype=torch.int32, device=dev)
         coords = torch.empty((n, 4), dtype=torch.int32, device=dev) if want_coords else None
-        L = _lib.lib()
-        ws = runtime.workspace(L.sf_lift_index_ws_bytes(n, ncells), dev)
-        lo, res, dim = self._grid_args()
-        _lib.check(L.sf_lift_index_fwd(ptr(g), n, n_batch, lo, res, dim, ptr(coords), ptr(order), ptr(start), ptr(ws),
-                                       ws.numel() * 4, runtime.stream_ptr(dev)), "lift_index")
+        runtime.call("lift_index", ptr(g), n, n_batch, *self._grid_args(), ptr(coords), ptr(order), ptr(start), device=dev,
+                     scratch=("lift_index", n, ncells))
         return order, start, coords
 
     # ---- reference API ------------------------------------------------------------------------------
@@ -193,14 +190,12 @@ class LiftSplat(nn.Module):
         if (D, fH, fW) != tuple(self.frustum.shape[:3]):
             raise RuntimeError("feature / depth shape does not match the frustum %s" % (tuple(self.frustum.shape[:3]),))
         dev = depth_logits.device
-        L = _lib.lib()
-        st = runtime.stream_ptr(dev)
         fHW = fH * fW
         rows = b * s * n
         if depth_prob is None:
             logits = runtime.f32c(depth_logits).view(rows, D, fHW)
             prob = torch.empty_like(logits)
-            _lib.check(L.sf_depth_softmax_fwd(ptr(logits), ptr(prob), rows, D, fHW, st), "depth_softmax")
+            runtime.call("depth_softmax", ptr(logits), ptr(prob), rows, D, fHW, device=dev)
         else:
             prob = runtime.f32c(depth_prob)
             if prob.numel() != rows * D * fHW:
@@ -220,16 +215,13 @@ class LiftSplat(nn.Module):
         ncells = b * s * X * Y
         order = torch.empty((npts,), dtype=torch.int32, device=dev)
         start = torch.empty((ncells + 1,), dtype=torch.int32, device=dev)
-        ws = runtime.workspace(L.sf_lift_index_ws_bytes(npts, ncells), dev)
-        lo, res, dim = self._grid_args()
-        _lib.check(L.sf_lift_index_rig_fwd(ptr(aff), ptr(us), ptr(vs), ptr(ds), b * s, n, D, fH, fW, lo, res, dim, ptr(order),
-                                           ptr(start), ptr(ws), ws.numel() * 4, st), "lift_index_rig")
+        runtime.call("lift_index_rig", ptr(aff), ptr(us), ptr(vs), ptr(ds), b * s, n, D, fH, fW, *self._grid_args(), ptr(order),
+                     ptr(start), device=dev, scratch=("lift_index", npts, ncells))
         out = torch.empty((b, s, X * Y, C), dtype=torch.float32, device=dev)
         for bi in range(b):
             for t in range(s):
                 f = bi * s + t
-                _lib.check(L.sf_lift_pool_fused_fwd(ptr(rays), ptr(prob), D, fHW, ptr(order), ptr(start[f * X * Y:]), X * Y, C,
-                                                    ptr(out[bi, t - 1]) if t else ptr(None), self.discount, ptr(out[bi, t]), st),
-                           "lift_pool_fused")
+                runtime.call("lift_pool_fused", ptr(rays), ptr(prob), D, fHW, ptr(order), ptr(start[f * X * Y:]), X * Y, C,
+                             ptr(out[bi, t - 1] if t else None), self.discount, ptr(out[bi, t]), device=dev)
         out = out.view(b, s, X, Y, C)
         return out if nhwc else runtime.to_nchw(out.view(b * s, X, Y, C)).view(b, s, C, X, Y)

@@ -15,7 +15,7 @@ The plain-torch path (CPU inputs or ``SF_PLAN_TORCH=1``) states the same semanti
 import torch
 import torch.nn as nn
 
-from .. import _lib, runtime
+from .. import runtime
 from ..cost import Cost_Function, use_torch_path
 from ..layers.convolutions import Bottleneck
 from ..runtime import ptr
@@ -67,8 +67,8 @@ class Planning(nn.Module):
         w = [runtime.f32c(t) for t in (g.weight_ih, g.weight_hh, g.bias_ih, g.bias_hh, d[0].weight, d[0].bias, d[2].weight, d[2].bias)] if S else [None] * 8
         target = runtime.f32c(target_points) if S else None
         h0 = runtime.f32c(h0) if S else None
-        _lib.check(_lib.lib().sf_plan_select_refine_fwd(ptr(cs), ptr(trajs), 3, ptr(target), ptr(h0), *[ptr(t) for t in w], B, N, T, S,
-                                                        ptr(selected), ptr(refined), runtime.stream_ptr(dev)), "plan_select_refine")
+        runtime.call("plan_select_refine", ptr(cs), ptr(trajs), 3, ptr(target), ptr(h0), *[ptr(t) for t in w], B, N, T, S,
+                     ptr(selected), ptr(refined), device=dev)
         return selected, refined
 
     def select(self, trajs, cost_volume, semantic_pred, lane_divider, drivable_area, target_points, k=1):

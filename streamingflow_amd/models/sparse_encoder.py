@@ -125,18 +125,15 @@ class SparseEncoder(PackedModule):
         return (C.c_int32 * 3)(*[int(x) for x in v])
 
     def _table(self, in_coords, out_coords, batch, shape, k, s, p, subm):
-        L = _lib.lib()
         dev = in_coords.device
         n_in, n_out = in_coords.shape[0], out_coords.shape[0]
         ntaps = k[0] * k[1] * k[2]
         nbr = torch.empty((max(n_out, 1), ntaps), dtype=torch.int32, device=dev)
-        ws = runtime.workspace(L.sf_sparse_index_ws_bytes(n_in, ntaps), dev)
-        _lib.check(L.sf_sparse_table_fwd(ptr(in_coords), n_in, ptr(out_coords), n_out, batch, self._i3(shape), self._i3(k), self._i3(s),
-                                         self._i3(p), int(subm), ptr(nbr), ptr(ws), ws.numel() * 4, runtime.stream_ptr(dev)), "sparse_table")
+        runtime.call("sparse_table", ptr(in_coords), n_in, ptr(out_coords), n_out, batch, self._i3(shape), self._i3(k), self._i3(s),
+                     self._i3(p), int(subm), ptr(nbr), device=dev, scratch=("sparse_index", n_in, ntaps))
         return nbr
 
     def _out_sites(self, coords, batch, shape, k, s, p):
-        L = _lib.lib()
         dev = coords.device
         n_in = coords.shape[0]
         ntaps = k[0] * k[1] * k[2]
@@ -144,19 +141,15 @@ class SparseEncoder(PackedModule):
         cap = min(n_in * ntaps, batch * oshape[0] * oshape[1] * oshape[2])
         out = torch.empty((cap, 4), dtype=torch.int32, device=dev)
         cnt = torch.zeros((), dtype=torch.int32, device=dev)
-        ws = runtime.workspace(L.sf_sparse_index_ws_bytes(n_in, ntaps), dev)
-        _lib.check(L.sf_sparse_out_sites_fwd(ptr(coords), n_in, batch, self._i3(shape), self._i3(k), self._i3(s), self._i3(p), ptr(out), cap,
-                                             ptr(cnt), ptr(ws), ws.numel() * 4, runtime.stream_ptr(dev)), "sparse_out_sites")
+        runtime.call("sparse_out_sites", ptr(coords), n_in, batch, self._i3(shape), self._i3(k), self._i3(s), self._i3(p), ptr(out), cap,
+                     ptr(cnt), device=dev, scratch=("sparse_index", n_in, ntaps))
         return out[: int(cnt.item())], oshape
 
     @staticmethod
     def _conv(w, feats, nbr, n_out, add=None, act_after_add=False, mask=None):
-        L = _lib.lib()
-        dev = feats.device
-        out = torch.empty((n_out, w.cout), dtype=torch.float32, device=dev)
-        ws = runtime.workspace(L.sf_conv2d_ex_ws_bytes(), dev)
-        _lib.check(L.sf_sparse_conv_masked_fwd(C.byref(w), ptr(feats), feats.shape[1], feats.shape[0], ptr(nbr), ptr(mask), n_out, ptr(add), int(act_after_add),
-                                               ptr(out), ptr(ws), ws.numel() * 4, runtime.stream_ptr(dev)), "sparse_conv")
+        out = torch.empty((n_out, w.cout), dtype=torch.float32, device=feats.device)
+        runtime.call("sparse_conv_masked", w, ptr(feats), feats.shape[1], feats.shape[0], ptr(nbr), ptr(mask), n_out, ptr(add),
+                     int(act_after_add), ptr(out), device=feats.device, scratch=("conv2d_ex",))
         return out
 
     # ---- rows sorted by neighbour mask + per-tile tap masks (round 6) --------------------------------------------------------------
@@ -244,8 +237,7 @@ class SparseEncoder(PackedModule):
         x, coords, shape, n, _, _ = self._strided(W["conv_out"], self.conv_out[0], x, coords, B, shape, n)
         Cc = x.shape[1] if n else self.output_channels
         out = torch.empty((B, shape[0], shape[1], Cc * shape[2]), dtype=torch.float32, device=dev)
-        _lib.check(_lib.lib().sf_sparse_to_dense_fwd(ptr(x), ptr(coords), n, Cc, B, shape[0], shape[1], shape[2], ptr(out),
-                                                     runtime.stream_ptr(dev)), "sparse_to_dense")
+        runtime.call("sparse_to_dense", ptr(x), ptr(coords), n, Cc, B, shape[0], shape[1], shape[2], ptr(out), device=dev)
         return out if nhwc else runtime.to_nchw(out)
 
     def _strided(self, w, conv, x, coords, B, shape, n, sort_for_subm=False):

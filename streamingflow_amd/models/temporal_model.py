@@ -22,10 +22,9 @@ from collections import OrderedDict
 import torch
 import torch.nn as nn
 
-from .. import _lib, packing, runtime
+from .. import packing, runtime
 from ..layers.convolutions import DeepLabHead
 from ..runtime import PackedModule, ptr
-from .decoder import C_void
 
 
 def conv_1x1x1_norm_activated(in_channels, out_channels):
@@ -239,66 +238,53 @@ class TemporalModel(PackedModule):
         Cp, Cbp, Co = W["Cp"], W["Cbp"], W["Co"]
         A = torch.zeros((b, T + 1, H, Wd, Cbp), dtype=torch.float32, device=dev)      # one zero frame = the causal time padding
         for bi in range(b):
-            self._conv(W["down"], x[bi * T:], Cp, 0, T, H, Wd, A[bi, 1:], Cbp, 0)
+            runtime.conv2d_ex(W["down"], x[bi * T:], Cp, 0, T, H, Wd, A[bi, 1:], Cbp, 0)
         y = torch.empty((n, H, Wd, Cbp), dtype=torch.float32, device=dev)
         for bi in range(b):
             if W["kt"] == 2:
-                self._conv(W["conv"], A[bi, :T], Cbp, 0, T, H, Wd, y[bi * T:], Cbp, 0, in1=A[bi, 1:], in1_cs=Cbp, in1_co=0)
+                runtime.conv2d_ex(W["conv"], A[bi, :T], Cbp, 0, T, H, Wd, y[bi * T:], Cbp, 0, in1=A[bi, 1:], in1_cs=Cbp, in1_co=0)
             else:
-                self._conv(W["conv"], A[bi, 1:], Cbp, 0, T, H, Wd, y[bi * T:], Cbp, 0)
+                runtime.conv2d_ex(W["conv"], A[bi, 1:], Cbp, 0, T, H, Wd, y[bi * T:], Cbp, 0)
         if "proj" in W:
             res = torch.empty((n, H, Wd, Co), dtype=torch.float32, device=dev)
-            self._conv(W["proj"], x, Cp, 0, n, H, Wd, res, Co, 0)
+            runtime.conv2d_ex(W["proj"], x, Cp, 0, n, H, Wd, res, Co, 0)
         else:
             res = x
         out = torch.empty((n, H, Wd, Co), dtype=torch.float32, device=dev)
-        self._conv(W["up"], y, Cbp, 0, n, H, Wd, out, Co, 0, add=res, add_cs=Co)
+        runtime.conv2d_ex(W["up"], y, Cbp, 0, n, H, Wd, out, Co, 0, add=res, add_cs=Co)
         return out
-
-    # ---- device side ------------------------------------------------------------------------------
-    @staticmethod
-    def _conv(w, in0, in0_cs, in0_co, n, H, Wd, out, out_cs, out_co, in1=None, in1_cs=0, in1_co=0, add=None, add_cs=0):
-        L = _lib.lib()
-        dev = out.device
-        ws = runtime.workspace(L.sf_conv2d_ex_ws_bytes(), dev)
-        _lib.check(L.sf_conv2d_ex_fwd(_lib.C.byref(w), C_void(in0, in0_co), in0_cs, C_void(in1, in1_co) if in1 is not None else None,
-                                      in1_cs, ptr(add), add_cs, 0, ptr(out), out_cs, out_co, n, H, Wd, 0, ptr(ws), ws.numel() * 4,
-                                      runtime.stream_ptr(dev)), "conv2d_ex")
 
     def _block(self, W, x, b, T, H, Wd):
         """x [b*T, H, W, Cp] -> [b*T, H, W, Co]."""
         dev = x.device
-        L = _lib.lib()
-        st = runtime.stream_ptr(dev)
         n = b * T
         Cp, Chp, Co, Wc = W["Cp"], W["Chp"], W["Co"], W["Wc"]
         # leading 1x1x1 convs: (a0 | a1) with one zero frame in front of every sample, a2 into the concat tensor
         A = torch.zeros((b, T + 1, H, Wd, 2 * Chp), dtype=torch.float32, device=dev)
         cat = torch.empty((n, H, Wd, Wc), dtype=torch.float32, device=dev)
         for bi in range(b):
-            self._conv(W["a01"], x[bi * T:], Cp, 0, T, H, Wd, A[bi, 1:], 2 * Chp, 0)
-        self._conv(W["a2"], x, Cp, 0, n, H, Wd, cat, Wc, 2 * Chp)
+            runtime.conv2d_ex(W["a01"], x[bi * T:], Cp, 0, T, H, Wd, A[bi, 1:], 2 * Chp, 0)
+        runtime.conv2d_ex(W["a2"], x, Cp, 0, n, H, Wd, cat, Wc, 2 * Chp)
         for bi in range(b):       # causal (2,3,3): frames t-1 (A[bi, t]) and t (A[bi, t+1]), channel slice a0
-            self._conv(W["p0"], A[bi, :T], 2 * Chp, 0, T, H, Wd, cat[bi * T:], Wc, 0, in1=A[bi, 1:], in1_cs=2 * Chp, in1_co=0)
-            self._conv(W["p1"], A[bi, 1:], 2 * Chp, Chp, T, H, Wd, cat[bi * T:], Wc, Chp)
+            runtime.conv2d_ex(W["p0"], A[bi, :T], 2 * Chp, 0, T, H, Wd, cat[bi * T:], Wc, 0, in1=A[bi, 1:], in1_cs=2 * Chp, in1_co=0)
+            runtime.conv2d_ex(W["p1"], A[bi, 1:], 2 * Chp, Chp, T, H, Wd, cat[bi * T:], Wc, Chp)
         if "pool" in W:
             Crp = W["Crp"]
             mean = torch.empty((n, Cp), dtype=torch.float32, device=dev)
-            wsm = runtime.workspace(L.sf_channel_mean_ws_bytes(Cp, n), dev)
-            _lib.check(L.sf_channel_mean_fwd(ptr(x), ptr(mean), n, H * Wd, Cp, ptr(wsm), wsm.numel() * 4, st), "channel_mean")
+            runtime.call("channel_mean", ptr(x), ptr(mean), n, H * Wd, Cp, device=dev, scratch=("channel_mean", Cp, n))
             m = mean.view(b, T, Cp)
             pooled = m.clone()
             pooled[:, 1:] = (m[:, :-1] + m[:, 1:]) * 0.5         # AvgPool3d((2,h,w), pad (1,0,0), count_include_pad=False)[:-1]
             vec = torch.empty((n, Crp), dtype=torch.float32, device=dev)
-            self._conv(W["pool"], pooled.view(n, Cp), Cp, 0, n, 1, 1, vec, Crp, 0)
-            _lib.check(L.sf_broadcast_channels_fwd(ptr(vec), ptr(cat), n, H * Wd, Crp, Wc, 3 * Chp, st), "broadcast")
+            runtime.conv2d_ex(W["pool"], pooled.view(n, Cp), Cp, 0, n, 1, 1, vec, Crp, 0)
+            runtime.call("broadcast_channels", ptr(vec), ptr(cat), n, H * Wd, Crp, Wc, 3 * Chp, device=dev)
         if "proj" in W:
             res = torch.empty((n, H, Wd, Co), dtype=torch.float32, device=dev)
-            self._conv(W["proj"], x, Cp, 0, n, H, Wd, res, Co, 0)
+            runtime.conv2d_ex(W["proj"], x, Cp, 0, n, H, Wd, res, Co, 0)
         else:
             res = x
         out = torch.empty((n, H, Wd, Co), dtype=torch.float32, device=dev)
-        self._conv(W["agg"], cat, Wc, 0, n, H, Wd, out, Co, 0, add=res, add_cs=Co)
+        runtime.conv2d_ex(W["agg"], cat, Wc, 0, n, H, Wd, out, Co, 0, add=res, add_cs=Co)
         return out
 
     def forward(self, x):

@@ -39,6 +39,39 @@ def ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
+def ptr_at(t, chan_offset=0):
+    """Pointer `chan_offset` floats into t: channel `chan_offset` of an NHWC tensor (null for None)."""
+    return ctypes.c_void_p(t.data_ptr() + 4 * int(chan_offset)) if t is not None else ctypes.c_void_p(0)
+
+
+def call(fn, *args, device, scratch=None):
+    """The library's calling convention, in its one place: a forward ends in ``(..., stream)``, or in
+    ``(..., ws, ws_bytes, stream)`` when it takes scratch.  ``fn``: the short name of ``sf_<fn>_fwd``, or the ctypes function itself
+    where the caller picks between variants; ``args``: its arguments up to ``ws``.  ``scratch``: None, or the size query
+    ``(name, *dims)`` — ``sf_<name>_ws_bytes(*dims)``, often not the forward's own name — answered from ``workspace``, or a tensor
+    to use as it is (a captured graph's ``static_workspace``).  Raises on a non-zero status; returns the scratch tensor."""
+    L = _lib.lib()
+    if isinstance(fn, str):
+        fn = getattr(L, "sf_" + fn + "_fwd")
+    if scratch is None:
+        status = fn(*args, stream_ptr(device))
+    else:
+        if isinstance(scratch, tuple):
+            scratch = workspace(getattr(L, "sf_" + scratch[0] + "_ws_bytes")(*scratch[1:]), device)
+        status = fn(*args, ptr(scratch), scratch.numel() * 4, stream_ptr(device))
+    if status != 0:      # (the name is looked up on the failing call only)
+        _lib.check(status, fn.__name__)
+    return scratch
+
+
+def conv2d_ex(w, in0, in0_cs, in0_co, n, h, wd, out, out_cs, out_co, in1=None, in1_cs=0, in1_co=0, add=None, add_cs=0,
+              act_after_add=False):
+    """``sf_conv2d_ex_fwd``: packed conv ``w`` on channels in0_co.. of in0 [P][in0_cs] (beside them in1_co.. of in1 [P][in1_cs]) into channels out_co.. of
+    out [P][out_cs], P = n * h * wd input pixels; ``add`` [P'][add_cs] joins after the activation, or before it (act_after_add)."""
+    call("conv2d_ex", w, ptr_at(in0, in0_co), in0_cs, ptr_at(in1, in1_co), in1_cs, ptr(add), add_cs, int(act_after_add), ptr(out),
+         out_cs, out_co, n, h, wd, 0, device=out.device, scratch=("conv2d_ex",))
+
+
 def require_no_grad(*tensors):
     """Inference only (the reference evaluates under torch.no_grad(), evaluate.py:117): the HIP path records no autograd
     history, so an input that asks for gradients while grad mode is on would silently get none — refuse it instead.
@@ -63,7 +96,7 @@ def to_nhwc(x):
     n, c, h, w = x.shape
     out = torch.empty((n, h, w, c), dtype=torch.float32, device=x.device)
     if out.numel():
-        _lib.check(_lib.lib().sf_nchw_to_nhwc(ptr(x), ptr(out), n, c, h * w, stream_ptr(x.device)), "nchw_to_nhwc")
+        call(_lib.lib().sf_nchw_to_nhwc, ptr(x), ptr(out), n, c, h * w, device=x.device)
     return out
 
 
@@ -73,8 +106,41 @@ def to_nchw(x):
     n, h, w, c = x.shape
     out = torch.empty((n, c, h, w), dtype=torch.float32, device=x.device)
     if out.numel():
-        _lib.check(_lib.lib().sf_nhwc_to_nchw(ptr(x), ptr(out), n, c, h * w, stream_ptr(x.device)), "nhwc_to_nchw")
+        call(_lib.lib().sf_nhwc_to_nchw, ptr(x), ptr(out), n, c, h * w, device=x.device)
     return out
+
+
+def frames_first(y, b):
+    """[b * T, h, w, C] (sample-major) -> [T, b, h, w, C] contiguous."""
+    return y.view(b, -1, *y.shape[1:]).permute(1, 0, 2, 3, 4).contiguous()
+
+
+def frames_last(y):
+    """[T, b, h, w, C] -> [b * T, h, w, C] (sample-major)."""
+    T, b = y.shape[:2]
+    return y.permute(1, 0, 2, 3, 4).reshape(b * T, *y.shape[2:])
+
+
+def frames_to_nhwc(x):
+    """[b, T, C, h, w] -> [T, b, h, w, C] contiguous, the layout of the sequence entry points: one transpose launch, one copy."""
+    b, T, c, h, w = x.shape
+    return frames_first(to_nhwc(x.reshape(b * T, c, h, w)), b)
+
+
+def frames_to_nchw(y):
+    """[T, b, h, w, C] -> [b, T, C, h, w]: the inverse of ``frames_to_nhwc``."""
+    T, b, h, w, C = y.shape
+    return to_nchw(frames_last(y)).view(b, T, C, h, w)
+
+
+def frames_to_nchw_strided(y):
+    """[T, b, h, w, C] -> [b, T, C, h, w] written in place: one strided transpose launch per frame, no copy."""
+    T, b, h, w, C = y.shape
+    res = torch.empty((b, T, C, h, w), dtype=torch.float32, device=y.device)
+    fn = _lib.lib().sf_nhwc_to_nchw_strided
+    for t in range(T):          # frame (t, b) -> res[b, t]
+        call(fn, ptr(y[t]), h * w * C, ptr(res[0, t]), T * C * h * w, b, C, h * w, device=y.device)
+    return res
 
 
 _PACK_GENERATION = [0]      # process-wide, monotonically increasing: never reused (unlike id() of a freed Pack)

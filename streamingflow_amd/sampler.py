@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _fresnel_tables as FT
-from . import _lib, runtime
+from . import runtime
 from .runtime import ptr
 
 WHEELBASE = 2.588            # NuscenesData.py:539
@@ -167,10 +167,8 @@ def sample_device(v0, kappa, t0, n0, tt_kept, t_key, uniforms, n_straight, n_lef
     dev = uniforms.device
     out = torch.empty((B, M, n_t, 3), dtype=torch.float32, device=dev)
     order = torch.empty((B, M), dtype=torch.int32, device=dev) if want_order else None
-    L = _lib.lib()
-    ws = runtime.workspace(L.sf_plan_sample_ws_bytes(B, M, n_t), dev)
-    _lib.check(L.sf_plan_sample_fwd(ptr(v0), ptr(kappa), ptr(t0), ptr(n0), ptr(tt_kept), float(t_key), ptr(uniforms), n_straight, n_left, n_right,
-                                    B, M, n_t, ptr(out), ptr(order), ptr(ws), ws.numel() * 4, runtime.stream_ptr(dev)), "plan_sample")
+    runtime.call("plan_sample", ptr(v0), ptr(kappa), ptr(t0), ptr(n0), ptr(tt_kept), float(t_key), ptr(uniforms), n_straight, n_left, n_right,
+                 B, M, n_t, ptr(out), ptr(order), device=dev, scratch=("plan_sample", B, M, n_t))
     return out, order
 
 

@@ -12,7 +12,7 @@ import torch
 from torch import nn
 from torch.nn.modules.utils import _pair
 
-from . import _lib, runtime
+from . import runtime
 from .runtime import ptr
 
 
@@ -29,12 +29,10 @@ def hard_voxelize_padded(points, voxel_size, coors_range, max_points, max_voxels
     num = torch.empty((max_voxels,), dtype=torch.int32, device=dev)
     mean = torch.empty((max_voxels, F), dtype=torch.float32, device=dev) if want_mean else None
     vnum = torch.empty((), dtype=torch.int32, device=dev)
-    L = _lib.lib()
-    ws = runtime.workspace(L.sf_hard_voxelize_ws_bytes(max(n, 1)), dev)
     vs = (C.c_float * 3)(*[float(v) for v in voxel_size])
     cr = (C.c_float * 6)(*[float(v) for v in coors_range])
-    _lib.check(L.sf_hard_voxelize_fwd(ptr(pts), n, F, vs, cr, max_points, max_voxels, ptr(voxels), ptr(coors), ptr(num), ptr(mean),
-                                      ptr(vnum), ptr(ws), ws.numel() * 4, runtime.stream_ptr(dev)), "hard_voxelize")
+    runtime.call("hard_voxelize", ptr(pts), n, F, vs, cr, max_points, max_voxels, ptr(voxels), ptr(coors), ptr(num), ptr(mean), ptr(vnum),
+                 device=dev, scratch=("hard_voxelize", max(n, 1)))
     return {"voxels": voxels, "coors": coors, "num": num, "mean": mean, "voxel_num": vnum}
 
 
@@ -47,7 +45,7 @@ def dynamic_voxelize(points, voxel_size, coors_range):
     coors = torch.empty((n, 3), dtype=torch.int32, device=pts.device)
     vs = (C.c_float * 3)(*[float(v) for v in voxel_size])
     cr = (C.c_float * 6)(*[float(v) for v in coors_range])
-    _lib.check(_lib.lib().sf_dynamic_voxelize_fwd(ptr(pts), n, F, vs, cr, ptr(coors), runtime.stream_ptr(pts.device)), "dynamic_voxelize")
+    runtime.call("dynamic_voxelize", ptr(pts), n, F, vs, cr, ptr(coors), device=pts.device)
     return coors
 
 

@@ -91,6 +91,33 @@ def test_cell_into_given_out_and_slack(case):
     assert maxabs(runtime.to_nchw(own), U.reference(case)) <= U.tolerance(case)
 
 
+def test_one_step_is_bitwise_the_same_through_every_module_that_shares_the_cell():
+    """``GRUCell.forward_nhwc``, ``SpatialGRU.forward_nhwc`` over T = 1 and ``SpatialGRUCell.forward`` (NCHW in and out) pack the same
+    parameters with one routine (layers/temporal.py: pack_gru_block) and run them through one wrapper each of sf_gru_cell_fwd and
+    sf_spatial_gru_fwd: the same weights and inputs give the same bits, at the smallest shape of this file (1 x 9 x 7), gate bias 0.3."""
+    from streamingflow_amd import runtime
+    from streamingflow_amd.beverse import basic_modules as B
+    from streamingflow_amd.layers.temporal_ode_bayes import SpatialGRUCell
+    case = U.BY_NAME["direct_24_16"]
+    cell = U.build(case).cuda()
+    gru = B.SpatialGRU(case["Cx"], case["C"], gru_bias_init=case["gru_bias_init"])
+    single = SpatialGRUCell(case["Cx"], case["C"], gru_bias_init=case["gru_bias_init"])
+    for m in (gru, single):
+        m.load_state_dict(cell.state_dict())
+        m.cuda().eval()
+    x, s = (t.cuda() for t in U.inputs(case))
+    xn, sn = runtime.to_nhwc(x), runtime.to_nhwc(s)
+    a = cell.forward_nhwc(xn, sn)
+    b = gru.forward_nhwc(xn[None], sn)
+    c = single(x, s)
+    torch.cuda.synchronize()
+    assert tuple(b.shape) == (1,) + tuple(a.shape) and tuple(c.shape) == tuple(s.shape)
+    print("max |GRUCell - SpatialGRU| %.3e, max |GRUCell - SpatialGRUCell| %.3e" % (maxabs(a, b[0]), maxabs(runtime.to_nchw(a), c)))
+    assert maxabs(c, U.reference(case)) <= U.tolerance(case)
+    assert torch.equal(a, b[0])
+    assert torch.equal(runtime.to_nchw(a), c)
+
+
 @pytest.mark.parametrize("case", _WINO, ids=_name)
 def test_winograd_and_direct_forms_agree(case):
     from streamingflow_amd import packing
