@@ -540,6 +540,35 @@ int sf_sparse_conv_masked_fwd(const sf_conv_w* w, const float* feats, int feats_
                               int n_out, const float* add, int act_after_add, float* out, float* ws, size_t ws_bytes, void* stream);
 int sf_sparse_to_dense_fwd(const float* feats, const int32_t* coords, int n, int C, int batch, int X, int Y, int D, float* out,
                            void* stream);
+/* ---- static form of the index entry points: sizes fixed in advance, counts stay on the device ---------------------------------------
+ * INACTIVE ROWS.  A site row coords[i] = (batch, x, y, z) is inactive when batch < 0; the entry points below write (-1, -1, -1, -1).
+ *   Inactive rows may lie anywhere in a buffer (holes between per-cloud blocks, not only a tail); their feature rows may hold anything
+ *   finite; no table entry of an active row ever points at one.  Every index kernel honours the convention, the entry points above
+ *   included: an inactive input row has the sentinel key (never found, feeds no output site), an inactive output row reads -1 under
+ *   every tap, and sf_sparse_to_dense_fwd skips inactive rows — it is its own static form.  The convolution needs nothing new: a -1
+ *   entry gathers a zero row, so an inactive output row comes out as act(bias) (+ add), finite, and nothing reads it.
+ * sf_voxel_rows_fwd — block k of a K-cloud row buffer from the padded outputs of sf_hard_voxelize_fwd for cloud k (coors
+ *   [max_voxels][3], mean_feats [max_voxels][F], the device voxel_num): rows k*max_voxels + v of coords4 [K*max_voxels][4] and of
+ *   feats [K*max_voxels][feats_cs] (feats_cs >= F, the rest zeros) = (k, x, y, z) and the mean for v < *voxel_num, inactive rows with
+ *   zero features from there on; counts[k] = *voxel_num.  One launch, nothing read back.
+ * sf_sparse_out_sites_static_fwd — sf_sparse_out_sites_fwd over cap_in input rows, some of them inactive: the sorted unique output
+ *   sites into rows [0, min(count, cap_out)) of out_coords, inactive rows from there up to cap_out, the TRUE count into the device int
+ *   n_out also where it exceeds cap_out (the caller compares when it chooses); nothing is written from cap_out on.
+ * sf_sparse_table_static_fwd — sf_sparse_table_fwd over cap_in / cap_out rows with inactive rows on either side, plus the tap masks of
+ *   sf_sparse_conv_masked_fwd: tile_mask64[i], i < ceil(cap_out / 64), = OR over the rows of the tile of their live taps (wave ballots).
+ *   ONE-BIT RULE: a tile without any live tap (inactive rows only) gets bit 0 alone, never a zero word — the convolution reads zero as
+ *   "walk every tap", one bit costs it one tap of zero rows instead of all of them, and the OR over an aligned 128-row pair of dead
+ *   tiles is still one bit.  ntaps > 32: zero words (no mask).  The split-K launch ignores the mask and is correct without it.
+ * Workspace: sf_sparse_index_ws_bytes(cap_in, ntaps), as above.  Enqueue-only (no allocation, no synchronisation, no atomics): the
+ *   calls can be recorded into a graph.  SF_ERR_INVALID as above, or tile_mask64 NULL / cap_out < 1. */
+int sf_voxel_rows_fwd(const int32_t* coors, const float* mean_feats, const int32_t* voxel_num, int max_voxels, int num_features, int k,
+                      int feats_cs, int32_t* coords4, float* feats, int32_t* counts, void* stream);
+int sf_sparse_out_sites_static_fwd(const int32_t* in_coords, int cap_in, int batch, const int32_t* shape, const int32_t* ksize,
+                                   const int32_t* stride, const int32_t* padding, int32_t* out_coords, int cap_out, int32_t* n_out,
+                                   void* ws, size_t ws_bytes, void* stream);
+int sf_sparse_table_static_fwd(const int32_t* in_coords, int cap_in, const int32_t* out_coords, int cap_out, int batch,
+                               const int32_t* shape, const int32_t* ksize, const int32_t* stride, const int32_t* padding, int subm,
+                               int32_t* nbr, uint32_t* tile_mask64, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- N4: evaluation harness kernels (streamingflow/metrics.py, streamingflow/utils/instance.py) ------------
  * sf_confusion_fwd — out[b[i]*K + a[i]] += 1 over n int64 labels in [0, K) (zero-filled here); *bad != 0 when

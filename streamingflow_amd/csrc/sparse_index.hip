@@ -13,6 +13,10 @@
 //                          unique output sites; their count goes back to the host (one sync per strided conv)
 //   sp_to_dense_kernel     structure.py dense() + the permute/view of sparse_encoder.py:133-137, written
 //                          directly as the NHWC BEV tensor [b][x][y][c*D + z]
+// Static form (sizes fixed in advance, counts stay on the device): a row with batch < 0 is INACTIVE.  Its key is the sentinel, so it
+// is never found and feeds no candidate; as an output row it reads -1 under every tap and is skipped by the dense scatter.
+//   sp_fill_inactive_kernel   rows from the count up to the capacity of an output-site buffer become (-1, -1, -1, -1)
+//   sp_tile_mask_kernel       tap mask of every 64-row tile of a table by wave ballots; a tile without a live tap gets one bit
 // Integer work, HBM/latency-bound; deterministic (sorts + scans, no atomics).
 #include <hip/hip_runtime.h>
 
@@ -41,7 +45,7 @@ __global__ void sp_key_kernel(const int* __restrict__ coords, int n, SpGeom G, u
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int4 c = *reinterpret_cast<const int4*>(coords + 4 * (size_t)i);
-  key[i] = sp_key(c.x, c.y, c.z, c.w, G.shape);
+  key[i] = c.x < 0 ? 0xFFFFFFFFu : sp_key(c.x, c.y, c.z, c.w, G.shape);      // inactive row: the sentinel, no cell has it (sp_geom)
   val[i] = (unsigned)i;
 }
 
@@ -70,7 +74,7 @@ __global__ void sp_table_kernel(const int* __restrict__ out_coords, int n_out, c
     q[0] = c.y * G.s[0] - G.p[0] + kx; q[1] = c.z * G.s[1] - G.p[1] + ky; q[2] = c.w * G.s[2] - G.p[2] + kz;
   }
   int r = -1;
-  if (q[0] >= 0 && q[0] < G.shape[0] && q[1] >= 0 && q[1] < G.shape[1] && q[2] >= 0 && q[2] < G.shape[2]) {
+  if (c.x >= 0 && q[0] >= 0 && q[0] < G.shape[0] && q[1] >= 0 && q[1] < G.shape[1] && q[2] >= 0 && q[2] < G.shape[2]) {
     const int pos = sp_find(in_keys, n_in, sp_key(c.x, q[0], q[1], q[2], G.shape));
     if (pos >= 0) r = (int)in_rows[pos];
   }
@@ -87,7 +91,7 @@ __global__ void sp_candidates_kernel(const int* __restrict__ coords, int n, SpGe
   const int4 c = *reinterpret_cast<const int4*>(coords + 4 * (size_t)i);
   const int pin[3] = {c.y, c.z, c.w};
   int o[3];
-  bool ok = true;
+  bool ok = c.x >= 0;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
     const int num = pin[a] + G.p[a] - kk[a];
@@ -119,14 +123,47 @@ __global__ void sp_compact_kernel(const unsigned* __restrict__ keys, const int* 
   *reinterpret_cast<int4*>(out_coords + 4 * (size_t)r) = make_int4((int)k, x, y, z);
 }
 
-// out[b][x][y][c*D + z] = feats[row][c]   (zero elsewhere: the caller's memset)
+// Zero fill as a kernel, not hipMemsetAsync: inside a captured graph it is a kernel node like everything around it (memset nodes of a
+// replayed graph are not reliable on this runtime: dispatch.hip, zero_fill_kernel)
+__global__ void sp_zero_kernel(unsigned* __restrict__ p, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = 0u;
+}
+
+// out[b][x][y][c*D + z] = feats[row][c]   (zero elsewhere: sp_zero_kernel before it)
 __global__ void sp_to_dense_kernel(const float* __restrict__ feats, const int* __restrict__ coords, int n, int C, int X, int Y, int D,
                                    float* __restrict__ out) {
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (long)n * C) return;
   const int i = (int)(idx / C), c = (int)(idx - (long)i * C);
   const int4 q = *reinterpret_cast<const int4*>(coords + 4 * (size_t)i);
+  if (q.x < 0) return;      // inactive row
   out[((((size_t)q.x * X + q.y) * Y + q.z) * C + c) * D + q.w] = feats[idx];
+}
+
+// rows [min(*n_out, cap), cap) of an output-site buffer become inactive (after sp_compact_kernel wrote *n_out, the TRUE count)
+__global__ void sp_fill_inactive_kernel(int* __restrict__ out_coords, int cap, const int* __restrict__ n_out) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= cap || j < n_out[0]) return;
+  *reinterpret_cast<int4*>(out_coords + 4 * (size_t)j) = make_int4(-1, -1, -1, -1);
+}
+
+// mask[i]: bit t set when a row of 64 i .. 64 i + 63 has nbr[row][t] >= 0 — one wave per tile, one ballot per tap.  A tile without any
+// live tap (inactive rows only) gets bit 0 alone: the convolution reads a zero word as "walk every tap", one bit costs it one tap of
+// zero rows, and the OR over a 128-row pair of dead tiles is still one bit.  ntaps > 32 has no mask: zero words.
+__global__ void sp_tile_mask_kernel(const int* __restrict__ nbr, int n_out, int ntaps, unsigned* __restrict__ mask) {
+  const int lane = threadIdx.x & 63;
+  const int tile = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);      // wave-uniform
+  if (tile >= (n_out + 63) / 64) return;
+  const int row = tile * 64 + lane;
+  unsigned m = 0;
+  if (ntaps <= 32) {
+    for (int t = 0; t < ntaps; ++t) {
+      const bool live = row < n_out && nbr[(size_t)row * ntaps + t] >= 0;
+      if (__ballot(live) != 0ull) m |= 1u << t;
+    }
+    if (m == 0) m = 1u;
+  }
+  if (lane == 0) mask[tile] = m;
 }
 
 inline size_t a256s(size_t n) { return (n + 255) & ~size_t(255); }
@@ -206,9 +243,10 @@ static int sp_sort_inputs(const int32_t* coords, int n, const SpGeom& G, char*& 
   return SF_OK;
 }
 
-int sf_sparse_table_fwd(const int32_t* in_coords, int n_in, const int32_t* out_coords, int n_out, int batch, const int32_t* shape,
-                        const int32_t* ksize, const int32_t* stride, const int32_t* padding, int subm, int32_t* nbr, void* ws,
-                        size_t ws_bytes, void* stream) {
+// tile_mask64 != NULL: the static form, the tap mask of every 64-row tile follows the table
+static int sp_table(const int32_t* in_coords, int n_in, const int32_t* out_coords, int n_out, int batch, const int32_t* shape,
+                    const int32_t* ksize, const int32_t* stride, const int32_t* padding, int subm, int32_t* nbr, uint32_t* tile_mask64,
+                    void* ws, size_t ws_bytes, void* stream) {
   SpGeom G;
   double ci, co;
   if (!in_coords || !out_coords || !nbr || n_in < 1 || n_out < 0 || !sp_geom(shape, ksize, stride, padding, subm, batch, &G, &ci, &co) || !ws)
@@ -223,12 +261,30 @@ int sf_sparse_table_fwd(const int32_t* in_coords, int n_in, const int32_t* out_c
   if (rc != SF_OK) return rc;
   const long total = (long)n_out * G.k[0] * G.k[1] * G.k[2];
   hipLaunchKernelGGL(sp_table_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, out_coords, n_out, keys, rows, n_in, G, nbr);
+  if (tile_mask64) {
+    const int tiles = (n_out + 63) / 64;
+    hipLaunchKernelGGL(sp_tile_mask_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, st, nbr, n_out, G.k[0] * G.k[1] * G.k[2], tile_mask64);
+  }
   return hipGetLastError() == hipSuccess ? SF_OK : SF_ERR_LAUNCH;
 }
 
-int sf_sparse_out_sites_fwd(const int32_t* in_coords, int n_in, int batch, const int32_t* shape, const int32_t* ksize,
-                            const int32_t* stride, const int32_t* padding, int32_t* out_coords, int cap, int32_t* n_out, void* ws,
-                            size_t ws_bytes, void* stream) {
+int sf_sparse_table_fwd(const int32_t* in_coords, int n_in, const int32_t* out_coords, int n_out, int batch, const int32_t* shape,
+                        const int32_t* ksize, const int32_t* stride, const int32_t* padding, int subm, int32_t* nbr, void* ws,
+                        size_t ws_bytes, void* stream) {
+  return sp_table(in_coords, n_in, out_coords, n_out, batch, shape, ksize, stride, padding, subm, nbr, nullptr, ws, ws_bytes, stream);
+}
+
+int sf_sparse_table_static_fwd(const int32_t* in_coords, int cap_in, const int32_t* out_coords, int cap_out, int batch, const int32_t* shape,
+                               const int32_t* ksize, const int32_t* stride, const int32_t* padding, int subm, int32_t* nbr,
+                               uint32_t* tile_mask64, void* ws, size_t ws_bytes, void* stream) {
+  if (!tile_mask64 || cap_out < 1) return SF_ERR_INVALID;
+  return sp_table(in_coords, cap_in, out_coords, cap_out, batch, shape, ksize, stride, padding, subm, nbr, tile_mask64, ws, ws_bytes, stream);
+}
+
+// fill_tail: the static form, rows from the count up to cap become inactive
+static int sp_out_sites(const int32_t* in_coords, int n_in, int batch, const int32_t* shape, const int32_t* ksize, const int32_t* stride,
+                        const int32_t* padding, int32_t* out_coords, int cap, int32_t* n_out, bool fill_tail, void* ws, size_t ws_bytes,
+                        void* stream) {
   SpGeom G;
   double ci, co;
   if (!in_coords || !out_coords || !n_out || n_in < 1 || cap < 1 || !sp_geom(shape, ksize, stride, padding, 0, batch, &G, &ci, &co) || !ws)
@@ -255,14 +311,30 @@ int sf_sparse_out_sites_fwd(const int32_t* in_coords, int n_in, int batch, const
   t2 = tb_scan;
   if (rocprim::exclusive_scan(tmp_scan, t2, (const int*)flag, scan, 0, nc, rocprim::plus<int>(), st) != hipSuccess) return SF_ERR_LAUNCH;
   hipLaunchKernelGGL(sp_compact_kernel, grid, block, 0, st, sorted, flag, scan, (long)nc, G, cap, out_coords, n_out);
+  if (fill_tail) hipLaunchKernelGGL(sp_fill_inactive_kernel, dim3((unsigned)((cap + 255) / 256)), block, 0, st, out_coords, cap, n_out);
   return hipGetLastError() == hipSuccess ? SF_OK : SF_ERR_LAUNCH;
+}
+
+int sf_sparse_out_sites_fwd(const int32_t* in_coords, int n_in, int batch, const int32_t* shape, const int32_t* ksize,
+                            const int32_t* stride, const int32_t* padding, int32_t* out_coords, int cap, int32_t* n_out, void* ws,
+                            size_t ws_bytes, void* stream) {
+  return sp_out_sites(in_coords, n_in, batch, shape, ksize, stride, padding, out_coords, cap, n_out, false, ws, ws_bytes, stream);
+}
+
+int sf_sparse_out_sites_static_fwd(const int32_t* in_coords, int cap_in, int batch, const int32_t* shape, const int32_t* ksize,
+                                   const int32_t* stride, const int32_t* padding, int32_t* out_coords, int cap_out, int32_t* n_out,
+                                   void* ws, size_t ws_bytes, void* stream) {
+  return sp_out_sites(in_coords, cap_in, batch, shape, ksize, stride, padding, out_coords, cap_out, n_out, true, ws, ws_bytes, stream);
 }
 
 int sf_sparse_to_dense_fwd(const float* feats, const int32_t* coords, int n, int C, int batch, int X, int Y, int D, float* out,
                            void* stream) {
   if (!out || batch < 1 || X < 1 || Y < 1 || D < 1 || C < 1 || n < 0) return SF_ERR_INVALID;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(out, 0, (size_t)batch * X * Y * C * D * sizeof(float), st) != hipSuccess) return SF_ERR_LAUNCH;
+  const size_t cells = (size_t)batch * X * Y * C * D;
+  hipLaunchKernelGGL(sp_zero_kernel, dim3((unsigned)((cells + 1023) / 1024 < 4096 ? (cells + 1023) / 1024 : 4096)), dim3(256), 0, st,
+                     reinterpret_cast<unsigned*>(out), cells);
+  if (hipGetLastError() != hipSuccess) return SF_ERR_LAUNCH;
   if (n == 0) return SF_OK;
   if (!feats || !coords) return SF_ERR_INVALID;
   const long total = (long)n * C;

@@ -133,6 +133,34 @@ __global__ void vox_assign_kernel(const float* __restrict__ points, int n, int F
   }
 }
 
+// block k of a K-cloud row buffer from one cloud's padded voxels: row k*V + v = (k, x, y, z) and the mean padded with zeros to feats_cs
+// floats for v < *voxel_num, an inactive row (-1, -1, -1, -1) with zero features from there on; counts[k] = *voxel_num
+__global__ void vox_rows_kernel(const int* __restrict__ coors, const float* __restrict__ mean, const int* __restrict__ voxel_num, int V, int F,
+                                int k, int feats_cs, int* __restrict__ coords4, float* __restrict__ feats, int* __restrict__ counts) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  const int m = voxel_num[0];
+  if (v == 0) counts[k] = m;
+  if (v >= V) return;
+  const size_t row = (size_t)k * V + v;
+  const bool live = v < m;
+  *reinterpret_cast<int4*>(coords4 + 4 * row) =
+      live ? make_int4(k, coors[3 * v], coors[3 * v + 1], coors[3 * v + 2]) : make_int4(-1, -1, -1, -1);
+  float* dst = feats + row * feats_cs;
+  for (int f = 0; f < feats_cs; ++f) dst[f] = (live && f < F) ? mean[(size_t)v * F + f] : 0.f;
+}
+
+// Zero fill as a kernel, not hipMemsetAsync: inside a captured graph it is a kernel node like everything around it (memset nodes of a
+// replayed graph are not reliable on this runtime: dispatch.hip, zero_fill_kernel)
+__global__ void vox_zero_kernel(unsigned* __restrict__ p, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = 0u;
+}
+inline bool vox_zero(void* p, size_t words, hipStream_t st) {
+  if (words == 0) return true;
+  const size_t blocks = (words + 1023) / 1024;
+  hipLaunchKernelGGL(vox_zero_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, static_cast<unsigned*>(p), words);
+  return hipGetLastError() == hipSuccess;
+}
+
 inline size_t a256(size_t n) { return (n + 255) & ~size_t(255); }
 inline int bits_for(unsigned sentinel) {
   int b = 1;
@@ -212,14 +240,12 @@ int sf_hard_voxelize_fwd(const float* points, int num_points, int num_features, 
     if (!ws || ws_bytes < 6 * a + a256(tb_sort) + a256(tb_scan)) return SF_ERR_WORKSPACE;
   }
   // the reference hands back zero-initialised outputs (voxelize.py:52-54)
-  if (voxels && hipMemsetAsync(voxels, 0, (size_t)max_voxels * max_points * num_features * sizeof(float), st) != hipSuccess)
-    return SF_ERR_LAUNCH;
-  if (hipMemsetAsync(coors, 0, (size_t)max_voxels * 3 * sizeof(int), st) != hipSuccess) return SF_ERR_LAUNCH;
-  if (hipMemsetAsync(num_points_per_voxel, 0, (size_t)max_voxels * sizeof(int), st) != hipSuccess) return SF_ERR_LAUNCH;
-  if (mean_feats && hipMemsetAsync(mean_feats, 0, (size_t)max_voxels * num_features * sizeof(float), st) != hipSuccess)
-    return SF_ERR_LAUNCH;
+  if (voxels && !vox_zero(voxels, (size_t)max_voxels * max_points * num_features, st)) return SF_ERR_LAUNCH;
+  if (!vox_zero(coors, (size_t)max_voxels * 3, st)) return SF_ERR_LAUNCH;
+  if (!vox_zero(num_points_per_voxel, (size_t)max_voxels, st)) return SF_ERR_LAUNCH;
+  if (mean_feats && !vox_zero(mean_feats, (size_t)max_voxels * num_features, st)) return SF_ERR_LAUNCH;
   if (num_points == 0) {
-    if (voxel_num && hipMemsetAsync(voxel_num, 0, sizeof(int), st) != hipSuccess) return SF_ERR_LAUNCH;
+    if (voxel_num && !vox_zero(voxel_num, 1, st)) return SF_ERR_LAUNCH;
     return SF_OK;
   }
   char* p = static_cast<char*>(ws);
@@ -237,13 +263,23 @@ int sf_hard_voxelize_fwd(const float* points, int num_points, int num_features, 
   if (rocprim::radix_sort_pairs(tmp_sort, tb, (const unsigned*)key, key_s, (const unsigned*)val, order, (size_t)n, 0u, (unsigned)bits,
                                 st) != hipSuccess)
     return SF_ERR_LAUNCH;
-  if (hipMemsetAsync(flag, 0, (size_t)n * sizeof(int), st) != hipSuccess) return SF_ERR_LAUNCH;
+  if (!vox_zero(flag, (size_t)n, st)) return SF_ERR_LAUNCH;
   hipLaunchKernelGGL(vox_head_kernel, grid, block, 0, st, key_s, order, n, sentinel, flag);
   tb = tb_scan;
   if (rocprim::exclusive_scan(tmp_scan, tb, (const int*)flag, scan, 0, (size_t)n, rocprim::plus<int>(), st) != hipSuccess)
     return SF_ERR_LAUNCH;
   hipLaunchKernelGGL(vox_assign_kernel, grid, block, 0, st, points, n, num_features, key_s, order, scan, flag, G, sentinel, max_points,
                      max_voxels, voxels, coors, num_points_per_voxel, mean_feats, voxel_num);
+  return hipGetLastError() == hipSuccess ? SF_OK : SF_ERR_LAUNCH;
+}
+
+int sf_voxel_rows_fwd(const int32_t* coors, const float* mean_feats, const int32_t* voxel_num, int max_voxels, int num_features, int k,
+                      int feats_cs, int32_t* coords4, float* feats, int32_t* counts, void* stream) {
+  if (!coors || !mean_feats || !voxel_num || !coords4 || !feats || !counts || max_voxels < 1 || num_features < 1 || k < 0 ||
+      feats_cs < num_features)
+    return SF_ERR_INVALID;
+  hipLaunchKernelGGL(vox_rows_kernel, dim3((unsigned)((max_voxels + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), coors,
+                     mean_feats, voxel_num, max_voxels, num_features, k, feats_cs, coords4, feats, counts);
   return hipGetLastError() == hipSuccess ? SF_OK : SF_ERR_LAUNCH;
 }
 

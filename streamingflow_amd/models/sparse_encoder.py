@@ -200,45 +200,99 @@ class SparseEncoder(PackedModule):
         runtime.require_cuda(voxel_features, coors)
         if self.training:
             raise RuntimeError("streamingflow_amd.SparseEncoder is inference-only (BatchNorm statistics are folded): call .eval()")
-        W = self.packed().struct
-        B = int(batch_size)
-        dev = voxel_features.device
         coords = coors.to(torch.int32).contiguous()
         n = coords.shape[0]
-        shape = list(self.sparse_shape)
-        x = torch.zeros((n, self._cin_pad), dtype=torch.float32, device=dev)
+        x = torch.zeros((n, self._cin_pad_width()), dtype=torch.float32, device=voxel_features.device)
         x[:, : self.in_channels] = voxel_features
-        k3, one3, zero3 = [3, 3, 3], [1, 1, 1], [0, 0, 0]
-        tab = self._table(coords, coords, B, shape, k3, one3, zero3, True) if n else None
-        tmask = None
-        if n and self.SORT:      # the voxels in neighbour-mask order (features, coordinates and the table together)
-            perm = self._mask_order(tab, n)
-            x, coords, tab = x[perm].contiguous(), coords[perm].contiguous(), self._permute_subm(tab, perm)
-        if n and self.SORT:
-            tmask = self._tile_mask(tab, n)
+        return self._walk(_CountedSites(self), x, coords, n, int(batch_size), nhwc)
+
+    def _cin_pad_width(self):
+        self.packed()
+        return self._cin_pad
+
+    def _walk(self, ix, x, coords, n, B, nhwc):
+        """The layer walk of both forms.  ``ix`` says how the sites are indexed: ``_CountedSites`` sizes every stage by its site count
+        (one host read per strided convolution), ``_StaticSites`` by capacities fixed in advance, with inactive rows."""
+        W = self.packed().struct
+        shape = list(self.sparse_shape)
+        x, coords, tab, tmask = ix.enter(x, coords, n, B, shape)
         x = self._conv(W["conv_input"], x, tab, n, mask=tmask)
         for i, stage in enumerate(self.encoder_layers):
             for j, blk in enumerate(stage):
                 if isinstance(blk, SparseBasicBlock):
                     if tab is None and n:
-                        tab = self._table(coords, coords, B, shape, k3, one3, zero3, True)
-                        tmask = self._tile_mask(tab, n) if self.SORT else None
+                        tab, tmask = ix.subm_table(coords, n, B, shape)
                     y = self._conv(W[f"{i}.{j}.c1"], x, tab, n, mask=tmask)
                     x = self._conv(W[f"{i}.{j}.c2"], y, tab, n, add=x, act_after_add=True, mask=tmask)
                 elif blk[0].subm:                       # conv_module: submanifold conv + BN + ReLU
                     if tab is None and n:
-                        tab = self._table(coords, coords, B, shape, k3, one3, zero3, True)
-                        tmask = self._tile_mask(tab, n) if self.SORT else None
+                        tab, tmask = ix.subm_table(coords, n, B, shape)
                     x = self._conv(W[f"{i}.{j}"], x, tab, n, mask=tmask)
                 else:
                     nxt = stage[j + 1] if j + 1 < len(stage) else (self.encoder_layers[i + 1][0] if i + 1 < len(self.encoder_layers) else None)
                     subm_next = nxt is not None and (isinstance(nxt, SparseBasicBlock) or nxt[0].subm)
-                    x, coords, shape, n, tab, tmask = self._strided(W[f"{i}.{j}"], blk[0], x, coords, B, shape, n, sort_for_subm=subm_next and self.SORT)
-        x, coords, shape, n, _, _ = self._strided(W["conv_out"], self.conv_out[0], x, coords, B, shape, n)
+                    x, coords, shape, n, tab, tmask = ix.strided(W[f"{i}.{j}"], blk[0], x, coords, B, shape, n, subm_next)
+        x, coords, shape, n, _, _ = ix.strided(W["conv_out"], self.conv_out[0], x, coords, B, shape, n, False)
         Cc = x.shape[1] if n else self.output_channels
-        out = torch.empty((B, shape[0], shape[1], Cc * shape[2]), dtype=torch.float32, device=dev)
-        runtime.call("sparse_to_dense", ptr(x), ptr(coords), n, Cc, B, shape[0], shape[1], shape[2], ptr(out), device=dev)
+        out = torch.empty((B, shape[0], shape[1], Cc * shape[2]), dtype=torch.float32, device=x.device)
+        runtime.call("sparse_to_dense", ptr(x), ptr(coords), n, Cc, B, shape[0], shape[1], shape[2], ptr(out), device=x.device)
         return out if nhwc else runtime.to_nchw(out)
+
+    # ---- static form: capacities fixed in advance, counts on the device, nothing read back ------------------------------------------
+    def strided_convs(self):
+        """The strided convolutions in forward order (the last one is ``conv_out``)."""
+        return [blk[0] for stage in self.encoder_layers for blk in stage if not isinstance(blk, SparseBasicBlock) and not blk[0].subm] + \
+            [self.conv_out[0]]
+
+    def default_capacities(self, rows, batch_size):
+        """One capacity per strided convolution: min(rows of the input, cells of that stage's grid) — never too small for the first
+        stages of a sparse cloud (a stride-2 convolution seldom has more output sites than input sites) but no guarantee:
+        ``check_static`` tells."""
+        caps, shape = [], list(self.sparse_shape)
+        for conv in self.strided_convs():
+            k, s, p = conv.kernel_size, conv.stride, conv.padding
+            shape = [(shape[a] + 2 * p[a] - (k[a] - 1) - 1) // s[a] + 1 for a in range(3)]
+            caps.append(max(1, min(int(rows), int(batch_size) * shape[0] * shape[1] * shape[2])))
+        return caps
+
+    def forward_static(self, feats, coords, batch_size, capacities=None, nhwc=False):
+        """``forward`` over a row buffer with inactive rows (``coords[i, 0] < 0``: ``voxelize_static`` writes them), every later stage
+        sized by ``capacities`` (one int per strided convolution; default ``default_capacities``) instead of a count read back from
+        the device -> (dense, site_counts).  ``site_counts`` int32 [1 + strided convolutions], on the device: the active input rows,
+        then the TRUE number of output sites of every strided convolution — where one exceeds its capacity the sites beyond it were
+        dropped (in sorted order: the last samples' last cells) and the result is incomplete, though finite: ``check_static`` reads
+        the counts back and raises.  Enqueue-only: the call can be recorded into a graph."""
+        runtime.require_cuda(feats, coords)
+        if self.training:
+            raise RuntimeError("streamingflow_amd.SparseEncoder is inference-only (BatchNorm statistics are folded): call .eval()")
+        coords = coords.to(torch.int32).contiguous()
+        n = coords.shape[0]
+        if n < 1:
+            raise ValueError("forward_static needs a row buffer of at least one row (rows may all be inactive)")
+        B = int(batch_size)
+        caps = [int(c) for c in (capacities if capacities is not None else self.default_capacities(n, B))]
+        if len(caps) != len(self.strided_convs()) or min(caps) < 1:
+            raise ValueError("capacities: one positive int per strided convolution (%d)" % len(self.strided_convs()))
+        cp = self._cin_pad_width()
+        if feats.shape[1] == cp and feats.dtype == torch.float32 and feats.is_contiguous():
+            x = feats
+        else:
+            x = torch.zeros((n, cp), dtype=torch.float32, device=feats.device)
+            x[:, : self.in_channels] = feats
+        ix = _StaticSites(self, caps, torch.zeros((1 + len(caps),), dtype=torch.int32, device=feats.device))
+        ix.counts[0] = (coords[:, 0] >= 0).sum()
+        return self._walk(ix, x, coords, n, B, nhwc), ix.counts
+
+    def check_static(self, site_counts, capacities):
+        """The one place of the static form that reads back: raises when a strided convolution had more output sites than its
+        capacity.  Call it when the caller chooses, after a synchronisation it already has."""
+        counts = [int(v) for v in site_counts.tolist()]
+        names = ["strided convolution %d (%s)" % (s + 1, c.indice_key) for s, c in enumerate(self.strided_convs())]
+        for name, cnt, cap in zip(names, counts[1:], capacities):
+            if cnt > int(cap):
+                raise RuntimeError("SparseEncoder.forward_static: %s has %d output sites, capacity %d: the sites beyond the capacity "
+                                   "were dropped — raise that capacity" % (name, cnt, int(cap)))
+        return counts
 
     def _strided(self, w, conv, x, coords, B, shape, n, sort_for_subm=False):
         """strided SparseConv3d; returns (features, coordinates, grid, sites, submanifold table of the new sites or None, its tile masks).
@@ -259,3 +313,65 @@ class SparseEncoder(PackedModule):
             tmask = self._tile_mask(tab, m)
         nbr = self._table(coords, oc, B, shape, k, s, p, False)
         return self._conv(w, x, nbr, m, mask=self._tile_mask(nbr, m) if self.SORT else None), oc, oshape, m, tab, tmask
+
+
+class _CountedSites:
+    """Indexing of ``SparseEncoder._walk`` for ``forward``: every stage has exactly its sites, counted on the host."""
+
+    def __init__(self, enc):
+        self.enc = enc
+
+    def enter(self, x, coords, n, B, shape):
+        e = self.enc
+        tab = e._table(coords, coords, B, shape, [3, 3, 3], [1, 1, 1], [0, 0, 0], True) if n else None
+        tmask = None
+        if n and e.SORT:      # the voxels in neighbour-mask order (features, coordinates and the table together)
+            perm = e._mask_order(tab, n)
+            x, coords, tab = x[perm].contiguous(), coords[perm].contiguous(), e._permute_subm(tab, perm)
+            tmask = e._tile_mask(tab, n)
+        return x, coords, tab, tmask
+
+    def subm_table(self, coords, n, B, shape):
+        e = self.enc
+        tab = e._table(coords, coords, B, shape, [3, 3, 3], [1, 1, 1], [0, 0, 0], True)
+        return tab, (e._tile_mask(tab, n) if e.SORT else None)
+
+    def strided(self, w, conv, x, coords, B, shape, n, subm_next):
+        return self.enc._strided(w, conv, x, coords, B, shape, n, sort_for_subm=subm_next and self.enc.SORT)
+
+
+class _StaticSites:
+    """Indexing of ``SparseEncoder._walk`` for ``forward_static``: stage s has ``caps[s]`` rows, the inactive ones wherever they
+    are; tables come with their tile masks (a dead tile costs the convolution one tap); counts[1 + s] receives the true site count."""
+
+    def __init__(self, enc, caps, counts):
+        self.enc, self.caps, self.counts, self.stage = enc, caps, counts, 0
+
+    def _table(self, in_coords, out_coords, B, shape, k, s, p, subm):
+        dev = in_coords.device
+        n_in, n_out = in_coords.shape[0], out_coords.shape[0]
+        ntaps = k[0] * k[1] * k[2]
+        i3 = self.enc._i3
+        nbr = torch.empty((n_out, ntaps), dtype=torch.int32, device=dev)
+        mask = torch.empty(((n_out + 63) // 64,), dtype=torch.int32, device=dev)
+        runtime.call("sparse_table_static", ptr(in_coords), n_in, ptr(out_coords), n_out, B, i3(shape), i3(k), i3(s), i3(p), int(subm),
+                     ptr(nbr), ptr(mask), device=dev, scratch=("sparse_index", n_in, ntaps))
+        return nbr, (mask if ntaps <= 32 else None)
+
+    def enter(self, x, coords, n, B, shape):
+        return (x, coords) + self.subm_table(coords, n, B, shape)
+
+    def subm_table(self, coords, n, B, shape):
+        return self._table(coords, coords, B, shape, [3, 3, 3], [1, 1, 1], [0, 0, 0], True)
+
+    def strided(self, w, conv, x, coords, B, shape, n, subm_next):
+        k, s, p = conv.kernel_size, conv.stride, conv.padding
+        oshape = [(shape[a] + 2 * p[a] - (k[a] - 1) - 1) // s[a] + 1 for a in range(3)]
+        cap = self.caps[self.stage]
+        self.stage += 1
+        i3 = self.enc._i3
+        oc = torch.empty((cap, 4), dtype=torch.int32, device=x.device)
+        runtime.call("sparse_out_sites_static", ptr(coords), n, B, i3(shape), i3(k), i3(s), i3(p), ptr(oc), cap,
+                     runtime.ptr_at(self.counts, self.stage), device=x.device, scratch=("sparse_index", n, k[0] * k[1] * k[2]))
+        nbr, mask = self._table(coords, oc, B, shape, k, s, p, False)
+        return self.enc._conv(w, x, nbr, cap, mask=mask), oc, oshape, cap, None, None

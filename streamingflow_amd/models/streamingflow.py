@@ -25,7 +25,7 @@ from .lift_splat import LiftSplat
 from .planning import Planning
 from .sparse_encoder import SparseEncoder
 from .temporal_model import TemporalModel
-from ..voxelize import Voxelization, voxelize
+from ..voxelize import Voxelization, voxelize, voxelize_static
 
 # the LiDAR encoder configuration hard-coded at streamingflow.py:111
 LIDAR_ENCODER = {"voxelize": {"max_num_points": 10, "point_cloud_range": [-50.0, -50.0, -5.0, 50.0, 50.0, 3.0],
@@ -105,6 +105,12 @@ class streamingflow(nn.Module):
                 "voxelize": Voxelization(**{k: (tuple(v) if k == "max_voxels" else v) for k, v in enc["voxelize"].items()}),
                 "backbone": SparseEncoder(**enc["backbone"])})})
             self.voxelize_reduce = True
+            # opt-in: the LiDAR branch sized by capacities fixed in advance (max_voxels per cloud, SparseEncoder.default_capacities or
+            # `lidar_capacities`), no host read, so `forward` can be recorded into a graph; the device counts of the last call stay in
+            # `lidar_site_counts` for SparseEncoder.check_static
+            self.static_lidar = False
+            self.lidar_capacities = None
+            self.lidar_site_counts = None
             self.lidar_channels = enc["backbone"]["output_channels"] * self._lidar_depth(enc["backbone"])
             self.temporal_model_lidar = TemporalModel(self.lidar_channels, self.receptive_field, **kw)
 
@@ -123,6 +129,11 @@ class streamingflow(nn.Module):
         return voxelize(points, self.encoders["lidar"]["voxelize"], self.voxelize_reduce)
 
     def extract_lidar_features(self, x):
+        if self.static_lidar:
+            backbone = self.encoders["lidar"]["backbone"]
+            feats, coords, _ = voxelize_static(x, self.encoders["lidar"]["voxelize"], pad_to=backbone._cin_pad_width())
+            feature, self.lidar_site_counts = backbone.forward_static(feats, coords, len(x), self.lidar_capacities)
+            return feature
         feats, coords, sizes = self.voxelize(x)
         return self.encoders["lidar"]["backbone"](feats, coords, len(x))
 

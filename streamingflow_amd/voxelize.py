@@ -94,3 +94,24 @@ def voxelize(points, voxelizer, voxelize_reduce=True):
         sizes.append(r["num"][:m])
     feats, coords, sizes = torch.cat(feats, 0), torch.cat(coords, 0), torch.cat(sizes, 0)
     return feats.contiguous(), coords, sizes
+
+
+def voxelize_static(points, voxelizer, pad_to=None):
+    """``voxelize`` without the host read: K clouds (a list or a [K, N, F] tensor) -> (feats [K*V, pad_to or F] mean point of every
+    voxel, coords [K*V, 4] int32, counts [K] int32), V = the voxelizer's ``max_voxels``.  Cloud k owns rows k*V .. k*V+V-1: its
+    ``counts[k]`` voxels as ``voxelize`` orders them, then inactive rows (-1, -1, -1, -1) with zero features.  Every size is fixed
+    by (K, V), so the calls can be recorded into a graph; ``pad_to`` widens the feature rows with zeros (the encoder's input width)."""
+    K = len(points)
+    V = int(voxelizer.max_voxels[0] if voxelizer.training else voxelizer.max_voxels[1])
+    dev = points[0].device
+    F = int(points[0].shape[-1])
+    cs = int(pad_to) if pad_to else F
+    feats = torch.empty((K * V, cs), dtype=torch.float32, device=dev)
+    coords = torch.empty((K * V, 4), dtype=torch.int32, device=dev)
+    counts = torch.empty((K,), dtype=torch.int32, device=dev)
+    for k in range(K):
+        r = hard_voxelize_padded(points[k], voxelizer.voxel_size, voxelizer.point_cloud_range, voxelizer.max_num_points, V,
+                                 want_voxels=False, want_mean=True)
+        runtime.call("voxel_rows", ptr(r["coors"]), ptr(r["mean"]), ptr(r["voxel_num"]), V, F, k, cs, ptr(coords), ptr(feats), ptr(counts),
+                     device=dev)
+    return feats, coords, counts
