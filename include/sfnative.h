@@ -213,7 +213,7 @@ int sf_conv2d_fwd(const sf_conv_w* w, const float* in0, const float* in1, const 
 int sf_conv2d_repeat(const sf_conv_w* w, const float* in0, const float* in1, const float* add, float* out,
                      int n_img, int Hin, int Win, int in_up, int reps, float* ws, size_t ws_bytes, void* stream);
 
-/* ---- Workspaces of the model entry points below (sf_gru_cell_fwd ... sf_dist_head_fwd, sf_channel_mean_fwd, sf_camera_neck_fwd) ----------
+/* ---- Workspaces of the model entry points below (sf_gru_cell_fwd ... sf_dist_head_fwd, sf_channel_mean_fwd, sf_camera_neck_fwd, sf_effnet_trunk_fwd) ----------
  * Each takes caller-owned scratch `ws` of `ws_bytes` bytes and has a size query beside it.  The query IS the call's own layout,
  * measured: it depends on the query's arguments only (and, where said, on the flow mode in force), never on the weights; a call derives
  * those arguments from its weights and carves exactly what the query returns for them.  So exactly that size is enough, and with less
@@ -483,6 +483,42 @@ int sf_depth_softmax_planar_fwd(const float* logits_nhwc, int cs, int co, float*
 size_t sf_camera_neck_ws_bytes(int c_hi, int c_lo, int C, int D, int hid, int n, int H, int W);   /* exactly that size is enough; less (or ws NULL): SF_ERR_WORKSPACE, nothing enqueued or written */
 int sf_camera_neck_fwd(const sf_deeplab_w* head, const sf_conv_w* convs, const float* hi, const float* lo, float* rays,
                        float* depth_logits, float* depth_prob, int n, int H, int W, float* ws, size_t ws_bytes, void* stream);
+
+/* ---- N8: EfficientNet trunk of the camera encoder (streamingflow/models/encoder.py:64-105; efficientnet_pytorch 0.7.x model.py) ----------------
+ * Eval mode, fp32: image [n][3][H][W] (planar != 0) or [n][H][W][3] -> the two endpoints the neck reads, NHWC:
+ *   out_hi = reduction_{index + 1} and out_lo = reduction_{index}, by the reference's rule: an endpoint is the tensor in front of every
+ *   block that lowers the resolution, and the last block's output is the final one.  Their sizes follow from the pads in the structs.
+ * MBConv: expand 1x1 + BN + swish (absent at ratio 1) -> depthwise k x k + BN + swish -> SE (mean over H x W -> reduce 1x1 + bias -> swish
+ * -> expand 1x1 + bias -> sigmoid -> scale) -> project 1x1 + BN (+ input).  The SE's channel sums are accumulated in 2^-24 fixed point
+ * with integer atomics, so results are bitwise reproducible run to run and between eager and captured runs.
+ * Weights: sf_effnet_w over a host array of sf_mbconv_w, both defined in include/sfnative_effnet.h — an extension header with its own
+ * layout guard (SF_EFFNET_ABI_VERSION, sf_effnet_abi_sizeof), so the struct set and SF_ABI_VERSION of this header are what they were; the
+ * entry points below take them as `const void*`.  A host compares SF_EFFNET_ABI_VERSION with sf_effnet_abi_version() and its struct sizes
+ * with sf_effnet_abi_sizeof(SF_EFFNET_STRUCT_*) once after loading (the static inline sf_effnet_abi_check_header of the extension header does).
+ * The workspace queries read the integers of the structs only (channel counts, kernel sizes, strides, pads, n_blocks, expand.w as a
+ * flag), never device memory.  SF_ERR_UNSUPPORTED, before anything is enqueued: k not 3 or 5, stride not 1 or 2, a channel count that is
+ * not a multiple of 8; SF_ERR_INVALID: NULL or misaligned pointers, structs that are no such block, an image too small to reach the endpoint;
+ * SF_ERR_WORKSPACE as everywhere. */
+#define SF_EFFNET_ABI_VERSION 1
+enum { SF_EFFNET_STRUCT_MBCONV_W = 0, SF_EFFNET_STRUCT_EFFNET_W, SF_EFFNET_STRUCT_COUNT };
+int sf_effnet_abi_version(void);          /* the library's SF_EFFNET_ABI_VERSION */
+size_t sf_effnet_abi_sizeof(int which);   /* sizeof(struct SF_EFFNET_STRUCT_<which>) as the library was compiled; 0 for an unknown id */
+size_t sf_effnet_trunk_ws_bytes(const void* w, int n, int H, int W);   /* exactly that size is enough; less (or ws NULL): SF_ERR_WORKSPACE, nothing enqueued or written */
+int sf_effnet_trunk_fwd(const void* w, const float* image, int planar, float* out_hi, float* out_lo, int n, int H, int W, float* ws,
+                        size_t ws_bytes, void* stream);
+/* one MBConv block: x [n][H][W][cin] -> out [n][Ho][Wo][cout], Ho = (H + pad_t + pad_b - k) / stride + 1 */
+size_t sf_mbconv_ws_bytes(const void* b, int n, int H, int W);   /* exactly that size is enough; less (or ws NULL): SF_ERR_WORKSPACE, nothing enqueued or written */
+int sf_mbconv_fwd(const void* b, const float* x, float* out, int n, int H, int W, float* ws, size_t ws_bytes, void* stream);
+/* The trunk's launches on their own (test hooks and building blocks).
+ * stem: out [n][Ho][Wo][c_stem].  dwconv: depthwise + BN + swish of block b on x [n][H][W][cexp] -> out [n][Ho][Wo][cexp], and
+ * sums [n][cexp] (zeroed by the call) = sum over the image's pixels of llrint(out * 2^24).  se_gate: sums of HW pixels -> gate [n][cexp].
+ * pointwise: out [n * HW][cout] = act((x * gate[image]) . w * scale + bias) + residual on a 1x1 pack; gate [n][cin] and residual may be
+ * NULL; swish != 0: act = swish, else none. */
+int sf_effnet_stem_fwd(const void* w, const float* image, int planar, float* out, int n, int H, int W, void* stream);
+int sf_effnet_dwconv_fwd(const void* b, const float* x, float* out, uint64_t* sums, int n, int H, int W, void* stream);
+int sf_effnet_se_gate_fwd(const void* b, const uint64_t* sums, float* gate, int n, int HW, void* stream);
+int sf_effnet_pointwise_fwd(const sf_conv_w* w, const float* x, const float* gate, const float* residual, float* out, int swish, int n, int HW,
+                            void* stream);
 
 /* ---- N2 (first half): LiDAR hard voxelisation ------------------------------------------------------
  * hard_voxelize — mmdet3d/ops/voxel/src/voxelization.h:63-85, deterministic GPU path

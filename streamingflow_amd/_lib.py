@@ -88,6 +88,24 @@ class BottleneckW(C.Structure):
     _fields_ = [("down", ConvW), ("conv", ConvW), ("up", ConvW), ("proj", ConvW), ("downsample", C.c_int32)]
 
 
+# the two structs of include/sfnative_effnet.h (the EfficientNet trunk's extension header): passed as `const void*`, guarded by
+# SF_EFFNET_ABI_VERSION / sf_effnet_abi_sizeof (EFFNET_STRUCTS below, checked by lib())
+class MBConvW(C.Structure):
+    _fields_ = [("expand", ConvW), ("project", ConvW), ("dw_w", C.c_void_p), ("dw_scale", C.c_void_p), ("dw_bias", C.c_void_p),
+                ("se_reduce_w", C.c_void_p), ("se_reduce_b", C.c_void_p), ("se_expand_w", C.c_void_p), ("se_expand_b", C.c_void_p),
+                ("cin", C.c_int32), ("cexp", C.c_int32), ("cout", C.c_int32), ("cse", C.c_int32), ("k", C.c_int32), ("stride", C.c_int32),
+                ("pad_t", C.c_int32), ("pad_l", C.c_int32), ("pad_b", C.c_int32), ("pad_r", C.c_int32), ("skip", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class EffNetW(C.Structure):
+    _fields_ = [("stem_w", C.c_void_p), ("stem_scale", C.c_void_p), ("stem_bias", C.c_void_p), ("blocks", C.POINTER(MBConvW)),
+                ("c_stem", C.c_int32), ("n_blocks", C.c_int32), ("pad_t", C.c_int32), ("pad_l", C.c_int32), ("pad_b", C.c_int32),
+                ("pad_r", C.c_int32), ("index", C.c_int32), ("reserved", C.c_int32)]
+
+
+EFFNET_STRUCTS = (MBConvW, EffNetW)      # in SF_EFFNET_STRUCT_* order
+
 STRUCTS = {"sf_conv_w": ConvW, "sf_gru_w": GruW, "sf_dual_w": DualW, "sf_res_w": ResW, "sf_pmodel_w": PModelW, "sf_encoder_w": EncoderW,
            "sf_decoder_w": DecoderW, "sf_convnext_w": ConvNextW, "sf_deeplab_w": DeepLabW, "sf_bottleneck_w": BottleneckW, "sf_bottle_w": BottleW}
 assert set(STRUCTS) == set(_STRUCT_NAMES), set(STRUCTS) ^ set(_STRUCT_NAMES)
@@ -162,6 +180,8 @@ def lib():
             theirs = [h.sf_abi_sizeof(i) for i in range(len(ABI_STRUCTS))]
             raise RuntimeError(f"{LIB_PATH}: ABI mismatch (library ABI {h.sf_abi_version()}, sizes {theirs}; binding ABI "
                                f"{SF_ABI_VERSION}, sizes {list(sizes)}): rebuild with `python -m streamingflow_amd.build`")
+        if h.sf_effnet_abi_version() != SF_EFFNET_ABI_VERSION or [h.sf_effnet_abi_sizeof(i) for i in range(len(EFFNET_STRUCTS))] != [C.sizeof(t) for t in EFFNET_STRUCTS]:
+            raise RuntimeError(f"{LIB_PATH}: ABI mismatch of the EfficientNet trunk structs (include/sfnative_effnet.h): rebuild with `python -m streamingflow_amd.build`")
         _LIB = h
     return _LIB
 

@@ -7,7 +7,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsfnative.so")
-SOURCES = ["conv_igemm.hip", "conv_sp.hip", "conv_wino.hip", "convnext_mlp.hip", "aux_kernels.hip", "dispatch.hip", "api.hip", "lift_splat.hip", "camera_neck.hip", "voxelize.hip", "sparse_index.hip", "eval_kernels.hip", "instance_track.hip", "panoptic_score.hip", "plan_kernels.hip", "plan_sampler.hip", "flow_warp.hip", "pack.hip"]
+SOURCES = ["conv_igemm.hip", "conv_sp.hip", "conv_wino.hip", "convnext_mlp.hip", "aux_kernels.hip", "dispatch.hip", "api.hip", "lift_splat.hip", "camera_neck.hip", "effnet.hip", "voxelize.hip", "sparse_index.hip", "eval_kernels.hip", "instance_track.hip", "panoptic_score.hip", "plan_kernels.hip", "plan_sampler.hip", "flow_warp.hip", "pack.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
 
 
@@ -22,7 +22,7 @@ def build(force=False, verbose=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     if not os.path.exists(hipcc):
         hipcc = "hipcc"
-    headers = [os.path.join(CSRC, h) for h in ("sf_device.h", "sf_math.h", "sf_launch.h", "dispatch.h", "fresnel_tables.h")] + [ os.path.join(HERE, "..", "include", "sfnative.h")]
+    headers = [os.path.join(CSRC, h) for h in ("sf_device.h", "sf_math.h", "sf_launch.h", "dispatch.h", "fresnel_tables.h")] + [os.path.join(HERE, "..", "include", h) for h in ("sfnative.h", "sfnative_effnet.h")]
     objs, jobs = [], []
     for src in SOURCES:
         s = os.path.join(CSRC, src)

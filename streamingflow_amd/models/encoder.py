@@ -1,6 +1,7 @@
 """Camera ``Encoder`` (streamingflow/models/encoder.py): the neck on the MI355X, the EfficientNet trunk pluggable.
 
-The reference's encoder is an EfficientNet trunk (third-party ``efficientnet_pytorch``, not part of this build) followed by
+The reference's encoder is an EfficientNet trunk (third-party ``efficientnet_pytorch``; restated on the device in models/efficientnet.py:
+``backbone=EfficientNetTrunk("b4")``) followed by
 StreamingFlow's own neck: per branch (features, depth) one ``DeepLabHead(c_hi, c_hi, hidden_channel=64)`` on the /16 endpoint
 and one ``UpsamplingConcat(c_hi + c_lo, C or D)`` joining the /8 endpoint (encoder.py:34-39, :107-112).  ``Encoder`` keeps the
 reference's sub-module names and ``state_dict`` keys (``feature_layer_1/2``, ``depth_layer_1/2``): a released checkpoint's
@@ -195,7 +196,17 @@ class Encoder(nn.Module):
         if c_hi != self.c_hi or tuple(reduction_lo.shape) != (n, self.c_lo, 2 * H, 2 * W):
             raise ValueError("neck: endpoints %s / %s, expected [N, %d, H, W] / [N, %d, 2H, 2W]"
                              % (tuple(reduction_hi.shape), tuple(reduction_lo.shape), self.c_hi, self.c_lo))
-        hi, lo = runtime.to_nhwc(reduction_hi), runtime.to_nhwc(reduction_lo)
+        return self.neck_from_nhwc(runtime.to_nhwc(reduction_hi), runtime.to_nhwc(reduction_lo))
+
+    def neck_from_nhwc(self, hi, lo):
+        """``neck_nhwc`` on endpoints that are NHWC already — hi [N, H, W, c_hi], lo [N, 2H, 2W, c_lo], contiguous fp32, as
+        ``EfficientNetTrunk.endpoints_nhwc`` returns them: no layout conversion in front of the neck."""
+        runtime.require_cuda(hi, lo)
+        n, H, W, c_hi = hi.shape
+        if c_hi != self.c_hi or tuple(lo.shape) != (n, 2 * H, 2 * W, self.c_lo) or not (hi.is_contiguous() and lo.is_contiguous()):
+            raise ValueError("neck: NHWC endpoints %s / %s, expected contiguous [N, H, W, %d] / [N, 2H, 2W, %d]"
+                             % (tuple(hi.shape), tuple(lo.shape), self.c_hi, self.c_lo))
+        hi, lo = runtime.f32c(hi), runtime.f32c(lo)
         pk = self.packed(H, W)
         dev = hi.device
         rays = torch.empty((n * 4 * H * W, self.C), dtype=torch.float32, device=dev)
@@ -213,11 +224,13 @@ class Encoder(nn.Module):
 
     def _endpoints(self, x):
         if self.backbone is None:
-            raise RuntimeError("Encoder has no backbone: construct it with backbone=EfficientNetEndpoints(trunk, version, downsample) "
+            raise RuntimeError("Encoder has no backbone: construct it with backbone=EfficientNetTrunk(version) (models/efficientnet.py) "
                                "(or any module returning (reduction_hi, reduction_lo)), or call neck() on the two endpoints")
         return self.backbone(x)
 
     def forward_nhwc(self, x):
+        if hasattr(self.backbone, "endpoints_nhwc"):      # EfficientNetTrunk: its endpoints are NHWC as they leave the device code
+            return self.neck_from_nhwc(*self.backbone.endpoints_nhwc(x))
         return self.neck_nhwc(*self._endpoints(x))
 
     def forward(self, x):

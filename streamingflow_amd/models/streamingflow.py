@@ -1,13 +1,13 @@
-"""``streamingflow`` — the whole model after the image backbone, wired from the MI355X-native parts.
+"""``streamingflow`` — the whole model, from camera images and point clouds, wired from the MI355X-native parts.
 
 Mirrors ``streamingflow.forward`` (streamingflow/models/streamingflow.py:208-269) with the reference's
 attribute names (``temporal_model``, ``encoders.lidar.{voxelize,backbone}``, ``temporal_model_lidar``,
 ``future_prediction_ode``, ``decoder``, ``bev_resolution`` / ``bev_start_position`` / ``bev_dimension``,
-``frustum``), so a released ``model.*`` checkpoint slice loads with ``strict=False``.  The one part that
-is NOT here is the EfficientNet trunk of the image ``Encoder`` (streamingflow/models/encoder.py; needs
-``efficientnet_pytorch``, out of scope — SURVEY.md §8).  The encoder's neck is (models/encoder.py): pass
-``encoder=Encoder(cfg.MODEL.ENCODER, D, backbone=EfficientNetEndpoints(trunk, ...))`` or assign it to ``self.encoder`` — its
-outputs then reach the lift in the layouts the lift reads — or assign any module returning
+``frustum``), so a released ``model.*`` checkpoint slice loads with ``strict=False``.  The image ``Encoder``
+(streamingflow/models/encoder.py) is models/encoder.py (the neck) over models/efficientnet.py (the EfficientNet trunk, restated:
+``efficientnet_pytorch`` is not needed): pass ``encoder=camera_encoder(cfg)`` — ``Encoder(cfg.MODEL.ENCODER, D,
+backbone=EfficientNetTrunk("b4"))`` with the two keys ``default_cfg`` leaves out — or assign it to ``self.encoder``: its
+outputs then reach the lift in the layouts the lift reads.  The default stays ``encoder=None``; or assign any module returning
 ``(features [b*n, C, fH, fW], depth_logits [b*n, D, fH, fW])``, or pass that pair in place of ``image``.
 
 Camera:  (features, depth logits, rig) -> LiftSplat.lift_splat -> + ego-pose channels -> TemporalModel
@@ -61,6 +61,20 @@ def default_cfg(**over):
     return cfg
 
 
+def camera_encoder(cfg, version="b4", **trunk_kw):
+    """The reference's image ``Encoder`` for ``cfg`` on the device: the neck over ``EfficientNetTrunk(version)`` — pass it as
+    ``streamingflow(cfg, encoder=camera_encoder(cfg))``.  ``cfg.MODEL.ENCODER`` gives DOWNSAMPLE and OUT_CHANNELS; NAME and
+    USE_DEPTH_DISTRIBUTION, which ``Encoder`` reads and ``default_cfg`` does not carry, are taken from it when present and otherwise
+    supplied here (``efficientnet-<version>``, True); D is the number of depth bins of ``cfg.LIFT.D_BOUND``.  ``trunk_kw``: ``image_size``."""
+    from .efficientnet import EfficientNetTrunk
+    from .encoder import Encoder
+    e = cfg.MODEL.ENCODER
+    name = getattr(e, "NAME", "efficientnet-" + version)
+    enc_cfg = NS(NAME=name, OUT_CHANNELS=e.OUT_CHANNELS, DOWNSAMPLE=e.DOWNSAMPLE, USE_DEPTH_DISTRIBUTION=getattr(e, "USE_DEPTH_DISTRIBUTION", True))
+    D = len(torch.arange(*cfg.LIFT.D_BOUND, dtype=torch.float))
+    return Encoder(enc_cfg, D, backbone=EfficientNetTrunk(name.split("-")[1], e.DOWNSAMPLE, **trunk_kw))
+
+
 class streamingflow(nn.Module):
     def __init__(self, cfg, encoder=None):
         super().__init__()
@@ -75,8 +89,7 @@ class streamingflow(nn.Module):
         self.latent_dim = cfg.MODEL.DISTRIBUTION.LATENT_DIM
         self.planning_enabled = bool(getattr(getattr(cfg, "PLANNING", None), "ENABLED", False))
         self.bev_size = (int(self.bev_dimension[0]), int(self.bev_dimension[1]))
-        # image encoder: None unless given (or assigned later).  models/encoder.py has the reference's neck on the device; the
-        # EfficientNet trunk in front of it is not part of this build (see module docstring)
+        # image encoder: None unless given (or assigned later): camera_encoder(cfg) builds the reference's (neck + EfficientNet trunk)
         self.encoder = encoder
         tm = cfg.MODEL.TEMPORAL_MODEL
         if tm.NAME != "temporal_block":
