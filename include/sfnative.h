@@ -520,6 +520,36 @@ int sf_effnet_se_gate_fwd(const void* b, const uint64_t* sums, float* gate, int 
 int sf_effnet_pointwise_fwd(const sf_conv_w* w, const float* x, const float* gate, const float* residual, float* out, int swish, int n, int HW,
                             void* stream);
 
+/* ---- N9: camera image front end (streamingflow/datas/NuscenesData.py:251-269, utils/geometry.py:9-13) -----------------------------------
+ * Decoded frames to the trunk's input: src [n][Hs][Ws][3] uint8 -> PIL's resize((Wr, Hr), BILINEAR) — the antialiased triangle filter in
+ * 22-bit fixed point, horizontal then vertical pass with a uint8 image between them (Pillow, Resample.c) — -> crop((l, t, r, b)) in
+ * resized coordinates (any box; positions outside the resized image are 0) -> ((float)u / 255 - mean[c]) / std[c].  Bit for bit what PIL
+ * and torch (on the CPU) compute.
+ * sf_resample_ksize / sf_resample_table — one axis' table as Pillow's precompute_coeffs + normalize_coeffs_8bpc build it, host code, in
+ *   double: bounds [out_size][2] = (xmin, n), k [out_size][ksize] int32 (zero past n), ksize = ceil(max(in_size / out_size, 1)) * 2 + 1
+ *   (0 for sizes < 1).  SF_ERR_UNSUPPORTED: ksize > SF_IMAGE_FRONTEND_MAX_TAPS (33: downscales up to 16 x).
+ * sf_image_frontend_plan — fills host_blob (sf_image_frontend_plan_bytes(...) bytes; 0 for what the plan call refuses) with everything
+ *   the kernel reads: a header of 24 int32 words, both axes' tables and the 3 x 256 fp32 normalise table.  Built once per geometry; the
+ *   caller uploads the bytes as they are (16-byte aligned) and keeps the host copy: the forward call reads its launch sizes from it.
+ *   Header words: 0 magic, 1 Hs, 2 Ws, 3 Hr, 4 Wr, 5 l, 6 t, 7 w = r - l, 8 h = b - t, 9 ksize x, 10 ksize y, 11..13 LDS tile sizes,
+ *   14 / 15 word offsets of the x bounds / coefficients, 16 / 17 of the y ones, 18 of the normalise table [c][u], 19 words in all,
+ *   20 LDS bytes of a workgroup, 21 rows are 16-byte multiples.  mean, std: HOST arrays of 3 floats.
+ *   SF_ERR_INVALID: a NULL pointer, a size < 1 or > 32768, an empty box, a blob too small; SF_ERR_UNSUPPORTED: more taps than the cap.
+ * sf_image_frontend_fwd — one launch, no workspace, enqueues only (no allocation, copy, host read of device memory or synchronisation):
+ *   out fp32 [n][3][h][w] (planar != 0) or [n][h][w][3]; out_u8 [n][h][w][3] (may be NULL): the resized and cropped image before the
+ *   normalisation.  A workgroup stages the source rows and columns its 8 x 64 output tile needs in LDS — 16 bytes per lane when Ws * 3 is
+ *   a multiple of 16, byte by byte otherwise — and keeps the image between the two passes there; rows the crop drops are not read.
+ *   SF_ERR_INVALID, nothing enqueued: NULL src / out / plan_host / plan_dev, n or a size < 1, sizes that are not the plan's, plan_dev not
+ *   16-byte aligned, or src not 16-byte aligned where Ws * 3 is a multiple of 16. */
+#define SF_IMAGE_FRONTEND_MAX_TAPS 33
+int sf_resample_ksize(int in_size, int out_size);
+int sf_resample_table(int in_size, int out_size, int32_t* bounds, int32_t* k);
+size_t sf_image_frontend_plan_bytes(int Hs, int Ws, int Hr, int Wr, int l, int t, int r, int b);
+int sf_image_frontend_plan(int Hs, int Ws, int Hr, int Wr, int l, int t, int r, int b, const float* mean, const float* std, void* host_blob,
+                           size_t blob_bytes);
+int sf_image_frontend_fwd(const uint8_t* src, const void* plan_host, const void* plan_dev, float* out, int planar, uint8_t* out_u8, int n,
+                          int Hs, int Ws, int h, int w, void* stream);
+
 /* ---- N2 (first half): LiDAR hard voxelisation ------------------------------------------------------
  * hard_voxelize — mmdet3d/ops/voxel/src/voxelization.h:63-85, deterministic GPU path
  * voxelization_cuda.cu:262-420 (same result as voxelization_cpu.cpp:45-102): points [num_points][F]

@@ -14,3 +14,4 @@ __version__ = "0.1.0"
 from .packing import set_math_mode, math_mode, set_winograd, winograd, set_persistent_flow  # noqa: F401,E402  (opt-in "bf16x3"; the default "fp32" is exact)
 from .stream import StreamSession, FutureStreamSession  # noqa: F401,E402
 from .sampler import TrajectorySampler, sample, kappa_from_steering  # noqa: F401,E402
+from .image_frontend import ImageFrontend  # noqa: F401,E402

@@ -39,7 +39,7 @@ LIDAR_ENCODER = {"voxelize": {"max_num_points": 10, "point_cloud_range": [-50.0,
 def default_cfg(**over):
     """The configuration keys this stage reads, with the reference's defaults (streamingflow/config.py)."""
     cfg = NS(TIME_RECEPTIVE_FIELD=3, N_FUTURE_FRAMES=4,
-             IMAGE=NS(FINAL_DIM=(224, 480)),
+             IMAGE=NS(FINAL_DIM=(224, 480), ORIGINAL_HEIGHT=900, ORIGINAL_WIDTH=1600, RESIZE_SCALE=0.3, TOP_CROP=46),
              LIFT=NS(X_BOUND=[-50.0, 50.0, 0.5], Y_BOUND=[-50.0, 50.0, 0.5], Z_BOUND=[-10.0, 10.0, 20.0], D_BOUND=[2.0, 50.0, 1.0],
                      DISCOUNT=0.5),
              MODEL=NS(ENCODER=NS(DOWNSAMPLE=8, OUT_CHANNELS=64),
@@ -76,9 +76,11 @@ def camera_encoder(cfg, version="b4", **trunk_kw):
 
 
 class streamingflow(nn.Module):
-    def __init__(self, cfg, encoder=None):
+    def __init__(self, cfg, encoder=None, frontend=None):
         super().__init__()
         self.cfg = cfg
+        # image front end: None unless given (or assigned later): ImageFrontend.from_cfg(cfg) takes raw uint8 frames and raw intrinsics
+        self.image_frontend = frontend
         self.lift = LiftSplat.from_cfg(cfg)
         # the reference keeps these on the top-level module (streamingflow.py:31-33, :41)
         self.bev_resolution, self.bev_start_position, self.bev_dimension = self.lift.bev_resolution, self.lift.bev_start_position, self.lift.bev_dimension
@@ -193,6 +195,10 @@ class streamingflow(nn.Module):
             states = lidar_states
         if self.use_camera:
             rf = self.receptive_field
+            if isinstance(image, torch.Tensor) and image.dtype == torch.uint8:      # decoded frames [b, s, n, Hs, Ws, 3] and the cameras' own intrinsics
+                if self.image_frontend is None:
+                    raise RuntimeError("no image front end: set `.image_frontend` (ImageFrontend.from_cfg(cfg)) or pass float images instead of uint8 frames")
+                image, intrinsics = self.image_frontend(image[:, :rf], intrinsics[:, :rf])      # only the frames the model reads
             img = tuple(t[:, :rf].contiguous() for t in image) if isinstance(image, (tuple, list)) else image[:, :rf].contiguous()
             x, depth, cam_front = self.calculate_birds_eye_view_features(img, intrinsics[:, :rf].contiguous(), extrinsics[:, :rf].contiguous(),
                                                                          future_egomotion)

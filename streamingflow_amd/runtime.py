@@ -72,6 +72,26 @@ def conv2d_ex(w, in0, in0_cs, in0_co, n, h, wd, out, out_cs, out_co, in1=None, i
          out_cs, out_co, n, h, wd, 0, device=out.device, scratch=("conv2d_ex",))
 
 
+def image_frontend_plan(Hs, Ws, Hr, Wr, box, mean, std):
+    """``sf_image_frontend_plan``: the host blob (int32 words, include/sfnative.h N9) of the front end that resizes Hs x Ws frames to
+    Hr x Wr and crops ``box`` = (l, t, r, b): both axes' resample tables and the normalise table.  Host arithmetic only, no GPU."""
+    L = _lib.lib()
+    nbytes = L.sf_image_frontend_plan_bytes(Hs, Ws, Hr, Wr, *box)
+    blob = torch.zeros(max(nbytes // 4, 1), dtype=torch.int32)
+    m, s = ((ctypes.c_float * 3)(*[float(v) for v in t]) for t in (mean, std))
+    _lib.check(L.sf_image_frontend_plan(Hs, Ws, Hr, Wr, *box, m, s, ctypes.c_void_p(blob.data_ptr()), nbytes), "sf_image_frontend_plan")
+    return blob
+
+
+def image_frontend(src, plan_host, plan_dev, out, planar=True, out_u8=None):
+    """``sf_image_frontend_fwd``: src [n][Hs][Ws][3] uint8 -> out fp32 [n][3][h][w] (planar) or [n][h][w][3], and optionally the resized,
+    cropped bytes out_u8 [n][h][w][3]; ``plan_host`` from ``image_frontend_plan``, ``plan_dev`` its copy on src's device."""
+    n, Hs, Ws = src.shape[:3]
+    h, w = (out.shape[2], out.shape[3]) if planar else (out.shape[1], out.shape[2])
+    call("image_frontend", ptr(src), ctypes.c_void_p(plan_host.data_ptr()), ptr(plan_dev), ptr(out), int(bool(planar)), ptr(out_u8), n, Hs, Ws,
+         h, w, device=src.device)
+
+
 def require_no_grad(*tensors):
     """Inference only (the reference evaluates under torch.no_grad(), evaluate.py:117): the HIP path records no autograd
     history, so an input that asks for gradients while grad mode is on would silently get none — refuse it instead.
