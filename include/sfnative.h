@@ -448,6 +448,16 @@ int sf_lift_index_coords_fwd(const int32_t* coords, int n_points, int B, int Z, 
 int sf_lift_index_rig_fwd(const float* affine, const float* us, const float* vs, const float* ds, int n_batch,
                           int n_cam, int D, int fH, int fW, const float* lo, const float* res, const int32_t* dim,
                           int32_t* order, int32_t* cell_start, void* ws, size_t ws_bytes, void* stream);
+/* Those affines computed on the device, in one launch a graph can record (N10): intrinsics [b*s*n_cam][3][3] (a general 3x3, inverted by
+ * cofactors over the determinant), extrinsics [b*s*n_cam][4][4], future_egomotion [b][s][6] (tx, ty, tz, rx, ry, rz), all fp32 ->
+ * affine [b*s*n_cam][12] = R_cam * K^-1 | t_cam, left-multiplied by pose_vec2mat(future_egomotion[b][t]) for t = own frame .. s-2 in
+ * that order; fp64 throughout, rounded to fp32 once at the store.  A camera whose determinant is zero or non-finite, or whose inputs
+ * (its K, its extrinsics' first three rows, the poses of its chain) hold a non-finite value, gets twelve NaNs — sf_lift_index_rig_fwd
+ * sends its points outside the grid — and ORs SF_RIG_BAD_CAMERA into *flags (device, int32; the caller zeroes it and reads it when it
+ * chooses to synchronise).  SF_ERR_INVALID, nothing written: a NULL pointer, or b, s or n_cam <= 0. */
+#define SF_RIG_BAD_CAMERA 2
+int sf_rig_affines_fwd(const float* intrinsics, const float* extrinsics, const float* future_egomotion, int b, int s, int n_cam,
+                       float* affine, int32_t* flags, void* stream);
 
 /* Pooling proper (bev_pool_cuda.cu:20-42 over every cell, empty ones included) fused with the temporal
  * blend of projection_to_birds_eye_view (streamingflow.py:419): out = prev*discount + sum (prev NULL:

@@ -7,7 +7,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsfnative.so")
-SOURCES = ["conv_igemm.hip", "conv_sp.hip", "conv_wino.hip", "convnext_mlp.hip", "aux_kernels.hip", "dispatch.hip", "api.hip", "lift_splat.hip", "camera_neck.hip", "effnet.hip", "image_frontend.hip", "voxelize.hip", "sparse_index.hip", "eval_kernels.hip", "instance_track.hip", "panoptic_score.hip", "plan_kernels.hip", "plan_sampler.hip", "flow_warp.hip", "pack.hip"]
+SOURCES = ["conv_igemm.hip", "conv_sp.hip", "conv_wino.hip", "convnext_mlp.hip", "aux_kernels.hip", "dispatch.hip", "api.hip", "lift_splat.hip", "rig_affines.hip", "camera_neck.hip", "effnet.hip", "image_frontend.hip", "voxelize.hip", "sparse_index.hip", "eval_kernels.hip", "instance_track.hip", "panoptic_score.hip", "plan_kernels.hip", "plan_sampler.hip", "flow_warp.hip", "pack.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
 
 

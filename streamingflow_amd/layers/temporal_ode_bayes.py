@@ -182,6 +182,22 @@ class GRUObservationCell(nn.Module):
         return self.gru_d(X_obs, state), None
 
 
+class RolloutFeed:
+    """The operands a rollout builds on the host — the per-sample step sizes ``coef`` and the noise: the in-kernel record
+    {seed, call} or the injected source's eps rows — as device buffers their owner fills, for a caller that records the whole forward
+    into a graph of its own (model_graph.ModelGraphSession).  One slot per rollout of a forward, in call order.  Installed as
+    ``NNFOwithBayesianJumps.feed``: outside a capture the rollout fills the slot as it goes (making it on first use), inside one it
+    copies nothing and only hands the buffers to the kernels; before a replay the owner calls ``fill_feed_slot`` per slot.  ``ops`` and
+    ``sel`` stay host arrays read at enqueue: they are the structure such a graph is keyed by."""
+
+    def __init__(self):
+        self.slots, self.cursor = [], 0
+
+    def begin(self):
+        """Before every pass over the forward (eager, capture): the next rollout takes slot 0."""
+        self.cursor = 0
+
+
 def init_weights(m):
     if type(m) == torch.nn.Linear:
         torch.nn.init.xavier_uniform_(m.weight)
@@ -235,6 +251,9 @@ class NNFOwithBayesianJumps(nn.Module):
         self._graphs = runtime.GraphCache()
         self._graph_structures_seen = set()
         self._graph_gens = None
+        # a RolloutFeed while somebody else records the forward into a graph (ModelGraphSession): coef and the noise come from its
+        # buffers, this module's own graph cache steps aside
+        self.feed = None
         self.apply(init_weights)
 
     # ---- noise --------------------------------------------------------------------------------
@@ -343,6 +362,7 @@ class NNFOwithBayesianJumps(nn.Module):
         d["_graphs"] = runtime.GraphCache()
         d["_graph_structures_seen"] = set()
         d["_graph_gens"] = None
+        d["feed"] = None
         # a copy (copy.deepcopy, an EMA twin, torch.save / load) draws its OWN Philox stream: new instance serial, seed derived again on
         # first use, call counter restarted — unless seed_noise() pinned the seed, which a copy keeps on purpose
         if not d.get("_noise_pinned", False):
@@ -371,6 +391,56 @@ class NNFOwithBayesianJumps(nn.Module):
         if eps.shape[0] < need or tuple(eps.shape[1:]) != (B, h, w, C):
             raise ValueError(f"eps must be [{need}, {B}, {h}, {w}, {C}] for solver {self.solver!r}, got {tuple(eps.shape)}")
         return eps, None
+
+    # ---- operands as fed data (RolloutFeed) -------------------------------------------------------------
+    @staticmethod
+    def _coef_host(scs, per_image):
+        """The fp32 step-size records of a rollout, on the host: [steps, SF_COEF_STRIDE], or [steps, B, SF_COEF_STRIDE] per image."""
+        return np.ascontiguousarray(np.stack([x.coef_array() for x in scs], axis=1) if per_image else scs[0].coef_array())
+
+    def _feed_mode(self):
+        return "philox" if self._in_kernel(self.noise) else ("randn" if self.noise is None else "fed")
+
+    def fill_feed_slot(self, slot, scs):
+        """Write one rollout's host-built operands into its slot, as an eager call would have made them: the step sizes of ``scs``
+        (schedules of the slot's structure), the next {seed, call} record — ``_noise_calls`` advances, as it does per eager call — or
+        the injected source's next eps rows.  Ordinary copies on the current stream: never called inside a capture."""
+        s0 = scs[0]
+        per_image = len(scs) > 1 and any(x.dts != s0.dts for x in scs)
+        if (s0.key(), per_image, len(scs), self._feed_mode()) != slot["sig"][:4] or any(x.key() != s0.key() for x in scs):
+            raise ValueError("RolloutFeed: the schedules do not have the structure, grouping and noise mode the slot was made for")
+        slot["coef"].copy_(torch.from_numpy(self._coef_host(scs, per_image)))
+        if slot["philox"] is not None:
+            self._noise_calls += 1
+            slot["philox"].copy_(torch.tensor([self._philox_seed(), self._noise_calls], dtype=torch.int64))
+        elif slot["sig"][3] == "fed":
+            need, B, h, w, _ = slot["eps"].shape
+            slot["eps"].copy_(self._draw_eps(self.noise, need, B, h, w, "cpu"))
+
+    def _fed_operands(self, feed, scs, per_image, need, B, h, w, device):
+        """(eps, philox, coef) of the feed's next slot.  Outside a capture the slot is (made and) filled here, so an eager forward under
+        a feed computes what one without it computes; inside a capture nothing is copied and no counter moves."""
+        i = feed.cursor
+        feed.cursor += 1
+        capturing = torch.cuda.is_current_stream_capturing()
+        mode = self._feed_mode()
+        C = self.hidden_size
+        rows = need if mode == "fed" else 0      # (a schedule has at least one jump: need >= 1)
+        sig = (scs[0].key(), per_image, len(scs), mode, rows, B, h, w, str(device))
+        if i == len(feed.slots):
+            if capturing:
+                raise RuntimeError("RolloutFeed: rollout %d has no buffers yet: run the forward once outside the capture first" % i)
+            shape = self._coef_host(scs, per_image).shape
+            feed.slots.append({"sig": sig, "coef": torch.empty(shape, dtype=torch.float32, device=device),
+                               "philox": torch.empty((2,), dtype=torch.int64, device=device) if mode == "philox" else None,
+                               "eps": torch.empty((rows, B, h, w, C), dtype=torch.float32, device=device)})
+        slot = feed.slots[i]
+        if slot["sig"] != sig:
+            raise RuntimeError("RolloutFeed: rollout %d changed its structure, shape or noise mode since its buffers were made" % i)
+        if not capturing:
+            self.fill_feed_slot(slot, scs)
+        eps = torch.randn((need, B, h, w, C), dtype=torch.float32, device=device) if mode == "randn" else slot["eps"]
+        return eps, slot["philox"], slot["coef"]
 
     def _auto_graph(self, structure, pixels):
         """`use_graph` None: graphs for the launch-bound single-latent kernels, but not from inside somebody else's capture
@@ -455,6 +525,12 @@ class NNFOwithBayesianJumps(nn.Module):
         if len(scs) not in (1, B) or any(x.key() != s0.key() for x in scs):
             raise ValueError("batched rollout needs one schedule, or one per sample with identical structure")
         per_image = len(scs) > 1 and any(x.dts != s0.dts for x in scs)
+        if self.feed is not None:
+            if eps is not None:
+                raise ValueError("rollout_nhwc under a RolloutFeed takes its noise from the feed, not from `eps`")
+            need = s0.n_jumps + sched.DRAWS_PER_STEP[self.solver] * s0.n_steps
+            out, final = self._run_eager(s0, per_image, hx_obs, *self._fed_operands(self.feed, scs, per_image, need, B, h, w, dev))
+            return (out[:, 0], final[0]) if one else (out, final)
         auto_graph = self._auto_graph(s0.key(), B * h * w)
         # draws the kernels will read: one per jump, DRAWS_PER_STEP[solver] per step (a schedule built for another solver
         # would make them read past the end of eps)

@@ -165,6 +165,10 @@ class LiftSplat(nn.Module):
         R_cam K^-1 and the camera translation (get_geometry), then the cumulative ego-motion warps of
         projection_to_birds_eye_view, composed in float64 on the device.  intrinsics [b,s,n,3,3],
         extrinsics [b,s,n,4,4], future_egomotion [b,s,6] -> [b, s, n, 12] fp32."""
+        return self.rig_affines64(intrinsics, extrinsics, future_egomotion).float().contiguous()
+
+    def rig_affines64(self, intrinsics, extrinsics, future_egomotion):
+        """`rig_affines` before its one rounding to fp32: [b, s, n, 12] float64."""
         b, s, n = intrinsics.shape[:3]
         R = extrinsics[..., :3, :3].double().matmul(torch.inverse(intrinsics.double()))
         A = torch.cat([R, extrinsics[..., :3, 3:].double()], -1)                 # [b,s,n,3,4]
@@ -174,13 +178,55 @@ class LiftSplat(nn.Module):
         ego = pose_vec2mat(future_egomotion.double())                             # [b,s,4,4]
         for t in range(s - 1):
             A[:, :t + 1] = ego[:, t].view(b, 1, 1, 4, 4).matmul(A[:, :t + 1])
-        return A[..., :3, :].reshape(b, s, n, 12).float().contiguous()
+        return A[..., :3, :].reshape(b, s, n, 12)
 
-    def lift_splat(self, feat, depth_logits, intrinsics, extrinsics, future_egomotion, nhwc=False, rays_nhwc=None, depth_prob=None):
+    # opt-in: `lift_splat` takes its affines from sf_rig_affines_fwd (one launch, no host read, so a graph can record it) instead of
+    # `rig_affines`, which stays the statement and the default.  A singular or non-finite camera then raises nothing at enqueue: its
+    # affine is NaN, it feeds no BEV cell, and `check_rig()` reports it when the caller chooses to synchronise
+    device_affines = False
+
+    def _rig_flag_word(self, device):
+        """The int32 flag word of `device` the kernel ORs into: made (and zeroed) once, so a captured graph keeps its address."""
+        words = self.__dict__.setdefault("_sf_rig_flags", {})
+        key = str(torch.device(device))
+        if key not in words:
+            words[key] = torch.zeros((1,), dtype=torch.int32, device=device)
+        return words[key]
+
+    def rig_affines_device(self, intrinsics, extrinsics, future_egomotion):
+        """`rig_affines` in one launch (sf_rig_affines_fwd): same arguments, same [b, s, n, 12] fp32 result up to the last bit of the
+        fp64 work; K is inverted by cofactors, nothing synchronises, bad cameras come out NaN and set the flag `check_rig` reads."""
+        runtime.require_cuda(intrinsics, extrinsics, future_egomotion)
+        b, s, n = intrinsics.shape[:3]
+        if tuple(intrinsics.shape) != (b, s, n, 3, 3) or tuple(extrinsics.shape) != (b, s, n, 4, 4) or tuple(future_egomotion.shape) != (b, s, 6):
+            raise RuntimeError("rig_affines_device: intrinsics [b,s,n,3,3], extrinsics [b,s,n,4,4], future_egomotion [b,s,6]; got %s, %s, %s"
+                               % (tuple(intrinsics.shape), tuple(extrinsics.shape), tuple(future_egomotion.shape)))
+        dev = intrinsics.device
+        K, E, ego = runtime.f32c(intrinsics), runtime.f32c(extrinsics), runtime.f32c(future_egomotion)
+        out = torch.empty((b, s, n, 12), dtype=torch.float32, device=dev)
+        runtime.call("rig_affines", ptr(K), ptr(E), ptr(ego), b, s, n, ptr(out), ptr(self._rig_flag_word(dev)), device=dev)
+        return out
+
+    def check_rig(self):
+        """The one synchronising call of the device affines: reads the flag words, clears them, and raises ValueError when a camera of
+        any `rig_affines_device` call since the last check was singular or held a non-finite value."""
+        bad = 0
+        for word in self.__dict__.get("_sf_rig_flags", {}).values():
+            bad |= int(word.item())
+            word.zero_()
+        if bad & _lib.SF_RIG_BAD_CAMERA:
+            raise ValueError("camera rig: an intrinsics matrix is singular (zero or non-finite determinant) or a camera's intrinsics, "
+                             "extrinsics or ego-motion hold a non-finite value; that camera's affine is NaN and it fed no BEV cell")
+        if bad:
+            raise ValueError("camera rig: unknown flag word 0x%x" % bad)
+
+    def lift_splat(self, feat, depth_logits, intrinsics, extrinsics, future_egomotion, nhwc=False, rays_nhwc=None, depth_prob=None,
+                   device_affines=None):
         """get_geometry + depth softmax (x) features + projection_to_birds_eye_view in one pass.
         feat [b,s,n,C,fH,fW] image features, depth_logits [b,s,n,D,fH,fW] -> [b, s, C, X, Y].
         ``rays_nhwc`` [b*s*n*fH*fW, C] (the features already in the gather layout; ``feat`` may then be None) and ``depth_prob``
-        [b*s*n, D, fH*fW] (the softmax already taken) replace the transpose and the softmax launch: what the camera neck hands over."""
+        [b*s*n, D, fH*fW] (the softmax already taken) replace the transpose and the softmax launch: what the camera neck hands over.
+        ``device_affines``: None = ``self.device_affines``; True takes the affines from ``rig_affines_device``."""
         runtime.require_cuda(feat, depth_logits, intrinsics, extrinsics, future_egomotion, rays_nhwc, depth_prob)
         b, s, n, D, fH, fW = depth_logits.shape
         C = feat.shape[3] if rays_nhwc is None else rays_nhwc.shape[-1]
@@ -208,7 +254,8 @@ class LiftSplat(nn.Module):
             rays = runtime.f32c(rays_nhwc)
             if tuple(rays.shape) != (rows * fHW, C):
                 raise RuntimeError("rays_nhwc %s: expected [%d, C]" % (tuple(rays.shape), rows * fHW))
-        aff = self.rig_affines(intrinsics, extrinsics, future_egomotion).view(rows, 12)
+        on_device = self.device_affines if device_affines is None else device_affines
+        aff = (self.rig_affines_device if on_device else self.rig_affines)(intrinsics, extrinsics, future_egomotion).view(rows, 12)
         fr = self.frustum
         us, vs, ds = fr[0, 0, :, 0].contiguous(), fr[0, :, 0, 1].contiguous(), fr[:, 0, 0, 2].contiguous()
         npts = rows * D * fHW

@@ -82,6 +82,9 @@ class streamingflow(nn.Module):
         # image front end: None unless given (or assigned later): ImageFrontend.from_cfg(cfg) takes raw uint8 frames and raw intrinsics
         self.image_frontend = frontend
         self.lift = LiftSplat.from_cfg(cfg)
+        # opt-in, the camera's counterpart of `static_lidar`: the lift takes the rig's affines from the device kernel (LiftSplat.device_affines),
+        # no host read, so `forward` can be recorded into a graph from raw intrinsics; `lift.check_rig()` reports a bad camera
+        self.static_camera = False
         # the reference keeps these on the top-level module (streamingflow.py:31-33, :41)
         self.bev_resolution, self.bev_start_position, self.bev_dimension = self.lift.bev_resolution, self.lift.bev_start_position, self.lift.bev_dimension
         self.frustum = self.lift.frustum
@@ -168,7 +171,8 @@ class streamingflow(nn.Module):
                 rays, logits, prob = self.encoder.forward_nhwc(flat)
                 D, (fH, fW) = logits.shape[1], self.frustum.shape[1:3]
                 depth = logits.view(b, s, n, D, fH, fW)
-                x = self.lift.lift_splat(None, depth, intrinsics, extrinsics, future_egomotion, rays_nhwc=rays, depth_prob=prob)
+                x = self.lift.lift_splat(None, depth, intrinsics, extrinsics, future_egomotion, rays_nhwc=rays, depth_prob=prob,
+                                         device_affines=self.static_camera or None)
                 cam_front = None
                 if self.planning_enabled:      # only the front camera of the present frame goes back to NCHW
                     from .. import runtime
@@ -176,9 +180,15 @@ class streamingflow(nn.Module):
                 return x, depth, cam_front
             feat, depth = self.encoder(flat)
             feat, depth = feat.view(b, s, n, *feat.shape[1:]), depth.view(b, s, n, *depth.shape[1:])
-        x = self.lift.lift_splat(feat, depth, intrinsics, extrinsics, future_egomotion)
+        x = self.lift.lift_splat(feat, depth, intrinsics, extrinsics, future_egomotion, device_affines=self.static_camera or None)
         cam_front = feat[:, -1, 1].contiguous() if self.planning_enabled else None
         return x, depth, cam_front
+
+    def graphed(self, max_graphs=4):
+        """``forward`` as one replayable graph (streamingflow_amd.model_graph.ModelGraphSession): ``session(*args)`` takes forward's
+        arguments and returns forward's dict in the session's static outputs; at most ``max_graphs`` graphs are kept."""
+        from ..model_graph import ModelGraphSession
+        return ModelGraphSession(self, max_graphs=max_graphs)
 
     def forward(self, image, intrinsics, extrinsics, future_egomotion, padded_voxel_points=None, camera_timestamp=None, points=None,
                 lidar_timestamp=None, target_timestamp=None):
